@@ -134,6 +134,48 @@ def timed_run(step, steps, warmup, timer, every, fence):
     return out, elapsed, host_enqueue, clock
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this many bytes of .npy files in all (headers included)
+NPY_HEADER = 256            # room left per file for its .npy header (numpy writes 128 bytes for a 1-D float32 array)
+
+
+def capture_outputs(model, out):
+    """What the timed path handed its caller in its last step, copied to the host before anything else runs on the model: the loss
+    record the engine returns (nce_out: loss, max score, ... include/cpc_hip.h cpc_nce_loss), every parameter's gradient and every
+    parameter after the Adam update (named_parameters order, each flattened, concatenated) and the floating-point buffers
+    (BatchNorm running statistics), all float32.  Call after a fence."""
+    names = [n for n, _ in model.named_parameters()]
+    arrays = {"loss_stats": out.detach().reshape(-1),
+              "grads": torch.cat([model._grad[n].reshape(-1) for n in names]),
+              "params": torch.cat([model._param[n].detach().reshape(-1) for n in names])}
+    bufs = [b.detach().reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()]
+    if bufs:
+        arrays["buffers"] = torch.cat([b.float() for b in bufs])
+    return {k: v.float().cpu() for k, v in arrays.items()}
+
+
+def write_outputs(path, arrays, budget=DUMP_BYTES):
+    """arrays -> path/<name>.npy (float32).  When the whole set, headers included, exceeds `budget` bytes, arrays under 1 MB stay whole
+    and every larger one keeps a fixed sample of its elements (torch.randperm with seed 0, in ascending index order) sized to its share of
+    what is left, so that two runs with the same arguments write the same positions.  Returns {name: [elements written, elements computed]}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    small = {k for k, v in arrays.items() if v.numel() * 4 < (1 << 20)}
+    budget -= NPY_HEADER * len(arrays)
+    total = sum(v.numel() * 4 for v in arrays.values())
+    large = sum(v.numel() for k, v in arrays.items() if k not in small)
+    room = (budget - sum(arrays[k].numel() * 4 for k in small)) // 4
+    written = {}
+    for name, v in arrays.items():
+        v = v.reshape(-1)
+        if total > budget and name not in small:
+            k = v.numel() * room // large
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            v = v[idx]
+        np.save(os.path.join(path, name + ".npy"), v.numpy().astype(np.float32))
+        written[name] = [int(v.numel()), int(arrays[name].numel())]
+    return written
+
+
 def build_model(dtype, device, seed=0):
     from cpc_audio_amd.audio_model import AudioEncoder, AudioGRUModel, AudioPredictiveCodingModel
     torch.manual_seed(seed)
@@ -509,6 +551,8 @@ def measure_secondary(name, args, world, rank, device, dist, brief=False):
     _hip.set_timer(timer)
     every = max(1, args.steps // 4)
     out, elapsed, host_enqueue, clock = timed_run(step, args.steps, args.prewarm + args.warmup, timer, every, fence)
+    if args.dump_outputs is not None and rank == 0 and name == args.workload:
+        write_outputs(args.dump_outputs, capture_outputs(model, out))
     sampled = len([i for i in range(args.steps) if i % every == every // 2])
     _hip.set_timer(None)
     loss = float(out[0])
@@ -671,7 +715,12 @@ def main():
     ap.add_argument("--graph", action="store_true", help="diagnostic: replay the step from a captured hipGraph (single GPU only)")
     ap.add_argument("--all-timesteps", action="store_true",
                     help="diagnostic: score_over_all_timesteps=True (the full (B*K)^2 score matrix); not the headline configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss record, gradients, updated parameters, BatchNorm "
+                         "statistics) as DIR/<name>.npy, float32, at most 64 MB in all (rank 0; see write_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.batch is None:
         args.batch = 128 if args.workload == "scalogram" else 256
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -762,6 +811,8 @@ def main():
         torch.cuda.synchronize()
 
     out, elapsed, host_enqueue, clock = timed_run(step, args.steps, args.prewarm + args.warmup, timer, every, fence)
+    if args.dump_outputs is not None and rank == 0:          # before the extra untimed steps below move the model on
+        write_outputs(args.dump_outputs, capture_outputs(model, out))
     if sync is not None and args.prewarm + args.warmup:
         exposed = exposed[1:]                   # the first pair belongs to the sampled warm-up step
     _hip.set_timer(None)

@@ -399,3 +399,37 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(tmp_path):
     r = subprocess.run([sys.executable, "-c", src], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert r.stdout.strip() == '{"metric": "x", "n_gpus": 4}' and "W0 noise" in r.stderr
+
+
+def test_bench_dump_outputs_are_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files of the last step's loss record, gradients, parameters and buffers; a set larger than the
+    budget keeps small arrays whole and the same seeded sample of every large one on every call."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    torch.manual_seed(0)
+    model = AudioPredictiveCodingModel(AudioEncoder(), AudioGRUModel(512, 256), enc_size=512, ar_size=256, visible_steps=100,
+                                       prediction_steps=12)
+    model._flatten_parameters("cpu")
+    model._flat_grad.normal_(generator=torch.Generator().manual_seed(1))
+    arrays = bench.capture_outputs(model, torch.arange(8, dtype=torch.float32))
+    n = model.parameter_count()
+    assert sorted(arrays) == ["grads", "loss_stats", "params"]
+    assert arrays["grads"].numel() == arrays["params"].numel() == n and arrays["loss_stats"].tolist() == list(range(8))
+    assert torch.equal(arrays["params"][:model.encoder.layers[0].weight.numel()], model.encoder.layers[0].weight.detach().reshape(-1))
+
+    whole = bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert whole == {k: [v.numel(), v.numel()] for k, v in arrays.items()}
+    g = np.load(tmp_path / "whole" / "grads.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, arrays["grads"].numpy())
+
+    budget = 8 << 20
+    for run in ("a", "b"):
+        written = bench.write_outputs(str(tmp_path / run), arrays, budget=budget)
+        assert written["loss_stats"] == [8, 8] and 0 < written["grads"][0] < n
+    size = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert size <= budget
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    assert np.isin(np.load(tmp_path / "a" / "grads.npy"), g).all()

@@ -1736,3 +1736,25 @@ def test_gru_state_carried_across_calls(golden_dir, dtype):
     zg = z[:, :, 6:].contiguous().requires_grad_(True)
     with pytest.raises(RuntimeError, match="carried"):
         gru(zg).sum().backward()
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """bench.py --steps K --dump-outputs DIR (a fresh process): exactly K timed steps, and DIR holds the last one's loss record, gradients
+    and updated parameters in float32 within 64 MB, its loss the one the JSON line reports."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+                        "--no-trainer-loop", "--no-secondary", "--no-score-gemm", "--dump-outputs", str(out)],
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-4000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and len(line["step_ms"]) == 3
+    files = sorted(os.listdir(out))
+    assert files == ["grads.npy", "loss_stats.npy", "params.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+    d = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+    assert d["grads"].size == d["params"].size == 7414784 and np.abs(d["grads"]).max() > 0
+    assert d["loss_stats"][0] == pytest.approx(line["config"]["loss_last_step"], abs=2e-6)

@@ -161,7 +161,6 @@ _SIGNATURES = {
     "cpc_gru_gp_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_gp_bwd": ([_P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_set_streaming": ([_I], _I),
-    "cpc_debug_set": ([_I, _I], _I),
     "cpc_nce_workspace_floats": ([_I, _I], _L),
     "cpc_nce_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P], _I),
     "cpc_nce_all_workspace_floats": ([_I, _I], _L),
@@ -195,7 +194,7 @@ def lib():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
-        if handle.cpc_abi_version() != 8:
+        if handle.cpc_abi_version() != 9:
             raise HipLibraryMissing("libcpc_hip.so ABI version mismatch; rebuild it")
         _lib = handle
     return _lib
@@ -328,23 +327,9 @@ def gemm_tn(A, B, Cout, M, I, J, lda, ldb, ldc, dtype, *, a_rpi=0, a_item=0, b_r
     _check(lib().cpc_gemm_tn(C.byref(args), stream_ptr()), "cpc_gemm_tn")
 
 
-# Timing probes (tools/): CPC_PROBE_SKIP=<entry point>,... drops those launches, so the step's RESULTS ARE GARBAGE.  Honoured only
-# together with CPC_ENABLE_PROBES=1, and announced on stderr; without the opt-in a stray CPC_PROBE_SKIP is refused loudly.
-_PROBE_SKIP = frozenset(v for v in os.environ.get("CPC_PROBE_SKIP", "").split(",") if v)
-PROBES_ENABLED = os.environ.get("CPC_ENABLE_PROBES", "0") == "1"
-if _PROBE_SKIP:
-    import sys as _sys
-    if not PROBES_ENABLED:
-        raise RuntimeError("CPC_PROBE_SKIP is set but CPC_ENABLE_PROBES=1 is not: timing probes drop kernel launches and make every "
-                           "result wrong; unset CPC_PROBE_SKIP, or opt in explicitly for a timing run")
-    print(f"[cpc_hip] WARNING: timing probe active, launches of {sorted(_PROBE_SKIP)} are SKIPPED -- results are garbage", file=_sys.stderr)
-
-
 def call(name, *args, key=None, work=0.0, shape=None):
     """Generic call of an exported function; appends the current stream and checks the status.
     ``key`` / ``work``: kernel symbol and algorithmic FLOPs (or bytes) this launch is booked under by a KernelTimer."""
-    if _PROBE_SKIP and name in _PROBE_SKIP:      # CPC_PROBE_SKIP=name,name: timing probes (the step's results are garbage)
-        return
     fn = getattr(lib(), name)
     if _timer is not None:
         _timer.run(key or name, work, lambda: _check(fn(*args, stream_ptr()), name), shape=shape)

@@ -708,8 +708,7 @@ int launch_attn_fwd(const void* qkv, void* out, void* P, int B, int S, int C, in
     if (!attn_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
     const Drop dr = make_drop(drop_p, seed, site);
     const float scale = 1.f / sqrtf((float)(C / heads));
-    static const bool use_mfma = !(getenv("CPC_ATTN_MFMA") && atoi(getenv("CPC_ATTN_MFMA")) == 0);
-    if (use_mfma && dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 8 == 0) &&
+    if (dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 8 == 0) &&
         ((uintptr_t)P % 8 == 0)) {
         hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(B * heads), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)out, (bf16_t*)P, S, C, heads,
                            scale, dr);
@@ -728,8 +727,7 @@ int launch_attn_bwd(const void* qkv, const void* P, const void* dout, void* dqkv
     if (!attn_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
     const Drop dr = make_drop(drop_p, seed, site);
     const float scale = 1.f / sqrtf((float)(C / heads));
-    static const bool use_mfma = !(getenv("CPC_ATTN_MFMA") && atoi(getenv("CPC_ATTN_MFMA")) == 0);
-    if (use_mfma && dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) &&
+    if (dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) &&
         ((uintptr_t)dqkv % 8 == 0)) {
         hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(B * heads), dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)P, (const bf16_t*)dout,
                            (bf16_t*)dqkv, S, C, heads, scale, dr);

@@ -17,7 +17,7 @@ static inline int esize(int dtype) { return dtype == CPC_DTYPE_BF16 ? 2 : 4; }
 
 extern "C" {
 
-int cpc_abi_version(void) { return 8; }
+int cpc_abi_version(void) { return 9; }
 
 int cpc_gemm_nt(const cpc_gemm_nt_args* a, void* stream) {
     if (!a || !a->A || !a->Bt || !a->C) return CPC_EINVAL;
@@ -635,36 +635,10 @@ int cpc_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA
 }
 
 extern int g_gru_force_streaming;
-extern int g_gru_waves;
-extern int g_gru_debug;
 int cpc_gru_set_streaming(int on) {
     const int old = g_gru_force_streaming;
-    if (on == 8 || on == 16) { g_gru_waves = on; return old; }      // 8 / 16: waves per workgroup at H = 256 (tuning knob)
-    if (on >= 100 && on < 108) { g_gru_debug = on - 100; return old; } // 100 + bits: timing experiments (see gru.hip)
     g_gru_force_streaming = on ? 1 : 0;
     return old;
-}
-
-int cpc_debug_set(int key, int value) {
-    // Keys 4 / 5 select timing-probe variants of the NT K loop whose RESULTS ARE GARBAGE: honoured only in a process that opted in
-    // with CPC_ENABLE_PROBES=1, and announced on stderr once, so that a stray call cannot silently corrupt a training run.
-    if (key == 4 || key == 5) {
-        const char* on = getenv("CPC_ENABLE_PROBES");
-        if (!on || on[0] != '1') {
-            fprintf(stderr, "[cpc_hip] cpc_debug_set(%d, %d) refused: timing probes need CPC_ENABLE_PROBES=1 (their results are garbage)\n", key, value);
-            return CPC_EINVAL;
-        }
-        static bool warned = false;
-        if (!warned && value != 0) {
-            fprintf(stderr, "[cpc_hip] WARNING: NT-GEMM timing probe active (cpc_debug_set %d = %d): results are garbage until it is reset\n", key, value);
-            warned = true;
-        }
-    }
-    if (key == 1) { const int old = g_nt_stagger64; g_nt_stagger64 = value; return old; }
-    if (key == 4) { const int old = g_nt_probe; g_nt_probe = value; return old; }
-    if (key == 6) { const int old = g_nt_wt; g_nt_wt = value; return old; }
-    if (key == 5) { const int old = g_nt_probe_taps; g_nt_probe_taps = value > 0 ? value : 1; return old; }
-    return CPC_EINVAL;
 }
 
 long long cpc_nce_workspace_floats(int B, int K) { return nce_workspace_floats(B, K); }

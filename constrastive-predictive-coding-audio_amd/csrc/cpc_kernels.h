@@ -18,8 +18,7 @@
                                 // range index: the launch is refused unless a_rpi * max(a_rpi2, 1) is a multiple of the tile height the launcher picks
 #define GEMM_LINEAR_K 256       // NT fast path: visit K in storage order even for overlapped-row operands (A-B check, see GemmNT::k_taps)
 #define GEMM_BIG_TILE 0x100000  // internal: the 256x256 tile also where fewer than 200 of them exist (a row-range launch that needs the per-tile column sums)
-#define GEMM_WT_AGENT 0x40000   // internal (cpc_debug_set key 6): output stores of the NT fast kernels write through at agent scope (sc1)
-#define GEMM_WT_SYSTEM 0x80000  // ... at system scope (sc0 sc1): the default
+#define GEMM_WT_SYSTEM 0x80000  // internal: set by the launcher: output stores of the NT fast kernels write through at system scope (sc0 sc1)
 #define GEMM_FORCE_GENERIC 8   // use the register-staged generic kernel even when the LDS-DMA fast path applies (A-B check)
 
 struct GemmNT {
@@ -104,11 +103,6 @@ struct GemmTN {
     int flags;
 };
 
-// tuning knobs (cpc_debug_set): key 1 = stagger of the 256x256 NT kernel in 1/64 of a tile time (default see gemm.hip)
-extern int g_nt_stagger64;
-extern int g_nt_probe_taps;     // key 5: taps of the chunk-major A operand of probe 32
-extern int g_nt_wt;             // key 6: output stores of the NT fast kernels written through the L2 (1: sc1, 2: sc0 sc1)
-extern int g_nt_probe;          // key 4: timing probes of the 256x256 NT kernel (DBG in gemm.hip; the results are garbage)
 int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream);
 int launch_score_lse(const void* P, const void* Tg, void* Sb, float* pm, float* ps, float* valid, int M, int N, int E, long long ldp,
                      long long ldt, long long lds_, int diag_off, hipStream_t stream);

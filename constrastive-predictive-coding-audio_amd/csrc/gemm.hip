@@ -349,22 +349,18 @@ __device__ __forceinline__ int direct_b_col(int r) {
     return (r & ~63) + 32 * (j >> 1) + 8 * (q >> 2) + 4 * (j & 1) + (q & 3);
 }
 
-// Output store of the fast kernels: written through the XCD's L2 at once (default, GEMM_WT_SYSTEM) or plain.  A large output left dirty
-// in the L2s is written back when the kernel ends, before the next one may start; with the stores written through as they are issued
-// the step takes 4.469 instead of 4.478-4.490 ms (tools/wt_ab.py, interleaved A/B on one box; agent scope: 4.474-4.479).
+// Output store of the fast kernels: written through the XCD's L2 at once (GEMM_WT_SYSTEM, which the launchers set) or plain.  A large
+// output left dirty in the L2s is written back when the kernel ends, before the next one may start; with the stores written through as
+// they are issued the step takes 4.469 instead of 4.478-4.490 ms (interleaved A/B on one box; agent scope: 4.474-4.479).
 __device__ __forceinline__ void store_out16(uint4* dst, uint4 v, int flags) {
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const v4u d = {v.x, v.y, v.z, v.w};
     if (flags & GEMM_WT_SYSTEM) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(d) : "memory");
-    else if (flags & GEMM_WT_AGENT) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(d) : "memory");
     else *dst = v;
 }
 
-template <typename T, typename TO, int WM, int WN, int TI, int TJ, bool DMA, bool C1 = false, bool DIRECT = false, int DBG = 0>
+template <typename T, typename TO, int WM, int WN, int TI, int TJ, bool DMA, bool C1 = false, bool DIRECT = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
-    // DBG: timing probes for tools/nt_probe.py (cpc_debug_set key 4; never in the product path, the results are garbage):
-    // 1 = K loop without its LDS-DMA requests, 2 = without its MFMAs, 16 = only the B tile is requested, 32 = the A operand stored
-    // stage-major ([K / 64][M][64], a_item = elements per stage: a stage's A tile is then ONE dense 32 KiB range)
     static_assert(!DIRECT || (DMA && !C1 && sizeof(T) == 2 && sizeof(TO) == 2 && TJ == 4), "direct epilogue: bf16 LDS-DMA variants");
     constexpr int CH = Elem<T>::CH;
     constexpr int BK = 8 * CH;
@@ -543,11 +539,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
         const T* gb1 = Bb + row_off(min(n0 + br1, p.N - 1), p.b_rpi, p.b_item, p.ldb) + sch * CH;
         const T* gb2 = Bb + row_off(min(n0 + br2, p.N - 1), p.b_rpi, p.b_item, p.ldb) + sch * CH;
         const T* gb3 = Bb + row_off(min(n0 + br3, p.N - 1), p.b_rpi, p.b_item, p.ldb) + sch * CH;
-        // (timing probe DBG 64: the B operand as if stored stage-major, [N / 256][K / 64][256][64] — a stage's B tile one dense 32 KiB)
-        const T* gd0 = Bb + (long long)(n0 / 256) * 256 * p.K + br0 * 64 + sch * CH;
-        const T* gd1 = Bb + (long long)(n0 / 256) * 256 * p.K + br1 * 64 + sch * CH;
-        const T* gd2 = Bb + (long long)(n0 / 256) * 256 * p.K + br2 * 64 + sch * CH;
-        const T* gd3 = Bb + (long long)(n0 / 256) * 256 * p.K + br3 * 64 + sch * CH;
         typedef __attribute__((address_space(3))) unsigned char lds_byte;
         lds_byte* const lds3 = (lds_byte*)lds;
         const unsigned wdst = wave_u * 4096;                   // this wave's 4 KiB slice of an operand tile
@@ -557,17 +548,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
 #define NT_DMA_STAGE(buf, ka, k0)                                                                                \
     do {                                                                                                         \
         const unsigned da = (buf) * STAGE + wdst, db = da + ATILE;                                               \
-        NT_DMA1(ga0 + ((DBG & 32) ? (long long)((buf) / taps) * p.a_item + ((buf) % taps) * 64 : (ka)), da);            \
-        NT_DMA1(ga1 + ((DBG & 32) ? (long long)((buf) / taps) * p.a_item + ((buf) % taps) * 64 : (ka)), da + 1024);     \
-        NT_DMA1(ga2 + ((DBG & 32) ? (long long)((buf) / taps) * p.a_item + ((buf) % taps) * 64 : (ka)), da + 2048);     \
-        NT_DMA1(ga3 + ((DBG & 32) ? (long long)((buf) / taps) * p.a_item + ((buf) % taps) * 64 : (ka)), da + 3072);     \
-        if constexpr (DBG & 64) {                                                                                \
-            NT_DMA1(gd0 + (long long)(k0) * 256, db);        NT_DMA1(gd1 + (long long)(k0) * 256, db + 1024);    \
-            NT_DMA1(gd2 + (long long)(k0) * 256, db + 2048); NT_DMA1(gd3 + (long long)(k0) * 256, db + 3072);    \
-        } else {                                                                                                 \
-            NT_DMA1(gb0 + (k0), db);        NT_DMA1(gb1 + (k0), db + 1024);                                      \
-            NT_DMA1(gb2 + (k0), db + 2048); NT_DMA1(gb3 + (k0), db + 3072);                                      \
-        }                                                                                                        \
+        NT_DMA1(ga0 + (ka), da);        NT_DMA1(ga1 + (ka), da + 1024);                                          \
+        NT_DMA1(ga2 + (ka), da + 2048); NT_DMA1(ga3 + (ka), da + 3072);                                          \
+        NT_DMA1(gb0 + (k0), db);        NT_DMA1(gb1 + (k0), db + 1024);                                          \
+        NT_DMA1(gb2 + (k0), db + 2048); NT_DMA1(gb3 + (k0), db + 3072);                                          \
     } while (0)
         const unsigned lds_u32 = (unsigned)(unsigned long long)(lds3);
         // fragment addresses: rows i*16 apart differ by 2048 B with the same swizzle term -> one base per (operand, kk)
@@ -618,13 +602,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
     do {                                                                                                         \
         const unsigned da = (buf) * STAGE + wdst, db = da + ATILE;                                               \
         switch (idx) {                                                                                           \
-        case 0: if constexpr (!(DBG & 16)) NT_DMA1(ga0 + ((DBG & 32) ? kA_ : (ka)), da); break;                                       \
+        case 0: NT_DMA1(ga0 + (ka), da); break;                                                                  \
         case 1: NT_DMA1(gb0 + (k0), db); break;                                                                  \
-        case 2: if constexpr (!(DBG & 16)) NT_DMA1(ga1 + ((DBG & 32) ? kA_ : (ka)), da + 1024); break;                                \
+        case 2: NT_DMA1(ga1 + (ka), da + 1024); break;                                                           \
         case 3: NT_DMA1(gb1 + (k0), db + 1024); break;                                                           \
-        case 4: if constexpr (!(DBG & 16)) NT_DMA1(ga2 + ((DBG & 32) ? kA_ : (ka)), da + 2048); break;                                \
+        case 4: NT_DMA1(ga2 + (ka), da + 2048); break;                                                           \
         case 5: NT_DMA1(gb2 + (k0), db + 2048); break;                                                           \
-        case 6: if constexpr (!(DBG & 16)) NT_DMA1(ga3 + ((DBG & 32) ? kA_ : (ka)), da + 3072); break;                                \
+        case 6: NT_DMA1(ga3 + (ka), da + 3072); break;                                                           \
         case 7: NT_DMA1(gb3 + (k0), db + 3072); break;                                                           \
         default: break;                                                                                          \
         }                                                                                                        \
@@ -649,13 +633,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
     do {                                                                                                         \
         const unsigned cur = (t & 1) * STAGE, nxt = ((t + 1) & 1) * STAGE;                                       \
         const long long k2 = kb + kj * tstride, k2a = kb + kj * tstride_a;                                       \
-        /* DBG 32: A stored chunk-major, [K / (64 taps)][rows][64]; the taps of a chunk are 64 elements (one row) apart */ \
-        const long long kA_ = (long long)((t + 2) / taps) * p.a_item + (long long)((t + 2) % taps) * 64;         \
-        (void)kA_;                                                                                               \
         if (DO_DMA) NT_KSTEP();                                                                                  \
         _Pragma("unroll") for (int i = 0; i < TI; ++i) {                                                         \
             _Pragma("unroll") for (int j = 0; j < TJ; ++j) {                                                     \
-                if constexpr (!(DBG & 2)) mfma_chunk<T>(acc[i][j], as_uint4(fb0[j]), as_uint4(fa0[i]));          \
+                mfma_chunk<T>(acc[i][j], as_uint4(fb0[j]), as_uint4(fa0[i]));                                    \
                 NT_READ1(i * TJ + j, fa1, fb1, aA1, aB1, cur);                                                   \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
@@ -665,8 +646,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
         __syncthreads();                                                                                         \
         _Pragma("unroll") for (int i = 0; i < TI; ++i) {                                                         \
             _Pragma("unroll") for (int j = 0; j < TJ; ++j) {                                                     \
-                if constexpr (!(DBG & 2)) mfma_chunk<T>(acc[i][j], as_uint4(fb1[j]), as_uint4(fa1[i]));          \
-                if constexpr (!(DBG & 1)) { if (DO_DMA) NT_DMA_PIECE(i * TJ + j, t & 1, k2a, k2); }                   \
+                mfma_chunk<T>(acc[i][j], as_uint4(fb1[j]), as_uint4(fa1[i]));                                    \
+                if (DO_DMA) NT_DMA_PIECE(i * TJ + j, t & 1, k2a, k2);                                            \
                 if (DO_READ) NT_READ1(i * TJ + j - (DO_DMA ? 8 : 0), fa0, fb0, aA0, aB0, nxt);                   \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
@@ -1053,7 +1034,7 @@ __device__ __forceinline__ float dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
-template <int DBG, bool LSE = false>
+template <bool LSE = false>
 __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmNT p) {
     typedef bf16_t T;
     typedef bf16_t TO;
@@ -1102,7 +1083,6 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(GemmNT p) {
 #define gb1 (gb0 + bo1)
 #define gb2 (gb0 + bo2)
 #define gb3 (gb0 + bo3)
-    const T *gd0 = Bb, *gd1 = Bb, *gd2 = Bb, *gd3 = Bb;          // (timing-probe operands of the shared macros; never used with DBG = 0)
     // tile index -> first row / column (false: a padding block of the 8-XCD grid, no tile)
 #define PS_TILE_OF(bid, m0_, n0_, ok_)                                   \
     do {                                                                 \
@@ -1988,15 +1968,10 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_f32_kernel(GemmNT p) {
 
 // start stagger of the 256x256 kernel (GemmNT::stagger) in 1/64 of a tile time: applied to launches with a ReLU-backward mask and
 // at least three rounds of tiles, whose every tile ends in a 2 x 32 MB burst (mask read + store) when all CUs run in step
-// (tools/nt_ab.py --stagger: layer-3 data gradient 285 -> 278 us, layer-2 1036 -> 1021 us; no gain without a mask)
-int g_nt_stagger64 = 32;
-int g_nt_probe = 0, g_nt_probe_taps = 1;
-int g_nt_wt = 2;       // output stores of the NT fast kernels: 0 plain, 1 written through at agent scope, 2 at system scope (default)
-
-static bool nt_persist_enabled() {          // CPC_NT_PERSIST=0: one workgroup per tile everywhere (A/B switch)
-    static const bool on = [] { const char* v = getenv("CPC_NT_PERSIST"); return !(v && v[0] == '0'); }();
-    return on;
-}
+// (layer-3 data gradient 285 -> 278 us, layer-2 1036 -> 1021 us; no gain without a mask)
+constexpr int NT_STAGGER64 = 32;
+// start stagger of the persistent kernel's first round of tiles, in the same unit
+constexpr int NT_PERSIST_STAGGER64 = 64;
 
 int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || batch <= 0) return CPC_EINVAL;
@@ -2028,23 +2003,22 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
     const bool big = fast && dtype == CPC_DTYPE_BF16 && p.N >= 256 && !(p.flags & GEMM_SMALL_TILE) &&
                      ((p.M >= 1024 && (big_tiles >= 200 || big_tiles * batch >= 200)) || ((p.flags & GEMM_BIG_TILE) && p.M >= 256));
     GemmNT q = p;
-    if (g_nt_wt == 1) q.flags |= GEMM_WT_AGENT; else if (g_nt_wt == 2) q.flags |= GEMM_WT_SYSTEM;
+    q.flags |= GEMM_WT_SYSTEM;
     // overlapped-row A operand (strided-conv view): visit K tap-innermost, see GemmNT::k_taps
     const int bk = 8 * ch;
     if (fast && !p.k_ranges && p.k_taps == 0 && p.lda > 0 && p.lda < p.K && p.K % p.lda == 0 && p.lda % bk == 0 && !(p.flags & GEMM_LINEAR_K)) {
         q.k_taps = (int)(p.K / p.lda);
         q.k_tap_stride = p.lda;
     }
-    if (g_nt_probe == 32) { q.k_taps = g_nt_probe_taps; q.k_tap_stride = p.K / g_nt_probe_taps; }      // (timing probe: see DBG 32)
     if (q.k_taps > 1 && (!fast || (long long)q.k_taps * q.k_tap_stride != p.K || q.k_tap_stride % bk || q.k_tap_stride_a % ch)) return CPC_EINVAL;
     if (q.k_tap_stride_a && q.k_taps <= 1) return CPC_EINVAL;
     if (fast && dtype == CPC_DTYPE_BF16 && !of32 && !(p.flags & GEMM_NARROW_EPI) && p.N % 8 == 0 && p.ldc % 8 == 0 &&
         p.c_item % 8 == 0 && p.c_item2 % 8 == 0 && p.c_batch % 8 == 0 && ((uintptr_t)p.C % 16 == 0) && (!p.mask || (uintptr_t)p.mask % 16 == 0))
         q.flags |= GEMM_WIDE_EPI;
-    if (big && g_nt_stagger64 > 0 && (p.mask || p.mask_bits) && big_tiles * batch >= 3 * 256) {
-        // a tile takes about nk * 3600 + 20000 cycles; the largest phase (7) starts g_nt_stagger64 / 64 of that late
+    if (big && (p.mask || p.mask_bits) && big_tiles * batch >= 3 * 256) {
+        // a tile takes about nk * 3600 + 20000 cycles; the largest phase (7) starts NT_STAGGER64 / 64 of that late
         const long long tile_cycles = (long long)(p.K / bk) * 3600 + 20000;
-        q.stagger = (int)std::max<long long>(1, tile_cycles * g_nt_stagger64 / 64 / 7 / 4096);
+        q.stagger = (int)std::max<long long>(1, tile_cycles * NT_STAGGER64 / 64 / 7 / 4096);
     }
     const int tbm = big ? 256 : BM, tbn = big ? 256 : BN;
     const int numM = (p.M - p.m_off + tbm - 1) / tbm;
@@ -2088,20 +2062,14 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
     if (dtype == CPC_DTYPE_BF16) {
         if (big) {
             if (of32) NT_LAUNCH(bf16_t, float, 2, 4, 8, 4, 512, q);
-            else if (direct && g_nt_probe == 1) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true, 1>), grid, dim3(512), 0, stream, q);
-            else if (direct && g_nt_probe == 2) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true, 2>), grid, dim3(512), 0, stream, q);
-            else if (direct && g_nt_probe == 16) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true, 16>), grid, dim3(512), 0, stream, q);
-            else if (direct && g_nt_probe == 32) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true, 32>), grid, dim3(512), 0, stream, q);
-            else if (direct && g_nt_probe == 64) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true, 64>), grid, dim3(512), 0, stream, q);
             // (short K only: a tile of up to 16 stages spends a third of its time outside the K loop.  The convolution launches of the train
             // step, K = 2 048 / 4 096, were measured SLOWER this way — 4.675 against 4.605 ms per configs[1] step, interleaved — the dispatcher's
             // dynamic tile order balances the CUs better than a fixed walk, and their fixed cost is under a tenth of a tile.)
-            else if (direct && nt_persist_enabled() && !p.mask && !banded && batch == 1 && p.m_off == 0 && p.K / bk >= 2 && p.K / bk <= 16 && blocks > 2 * 256 &&
+            else if (direct && !p.mask && !banded && batch == 1 && p.m_off == 0 && p.K / bk >= 2 && p.K / bk <= 16 && blocks > 2 * 256 &&
                      p.M % 32 == 0 && (p.a_rpi == 0 || p.a_rpi % 32 == 0) && p.b_rpi == 0 && p.N % 256 == 0) {
-                static const int ps = [] { const char* v = getenv("CPC_NT_PERSIST_STAGGER"); return v ? atoi(v) : 64; }();
                 const long long tile_cycles = (long long)(p.K / bk) * 3600 + 20000;
-                q.stagger = ps > 0 ? (int)std::max<long long>(1, tile_cycles * ps / 64 / 7 / 4096) : 0;
-                hipLaunchKernelGGL((gemm_nt_persist_kernel<0>), dim3(256), dim3(512), 0, stream, q);      // one workgroup per CU walks the tiles
+                q.stagger = (int)std::max<long long>(1, tile_cycles * NT_PERSIST_STAGGER64 / 64 / 7 / 4096);
+                hipLaunchKernelGGL((gemm_nt_persist_kernel<>), dim3(256), dim3(512), 0, stream, q);      // one workgroup per CU walks the tiles
             }
             else if (direct) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true>), grid, dim3(512), 0, stream, q);
             else NT_LAUNCH(bf16_t, bf16_t, 2, 4, 8, 4, 512, q);
@@ -2136,13 +2104,12 @@ int launch_score_lse(const void* P, const void* Tg, void* Sb, float* pm, float* 
     q.M = M; q.N = N; q.K = E;
     q.lda = ldp; q.ldb = ldt; q.ldc = Sb ? lds_ : N;
     q.lse_pm = pm; q.lse_ps = ps; q.lse_valid = valid; q.lse_diag_off = diag_off;
-    if (g_nt_wt == 1) q.flags |= GEMM_WT_AGENT; else if (g_nt_wt == 2) q.flags |= GEMM_WT_SYSTEM;
+    q.flags |= GEMM_WT_SYSTEM;
     const long long blocks = nt_grid_blocks(M / 256, N / 256);
     if (blocks > 0x7fffffffLL) return CPC_EINVAL;
-    static const int ps_ = [] { const char* v = getenv("CPC_NT_PERSIST_STAGGER"); return v ? atoi(v) : 64; }();
     const long long tile_cycles = (long long)(E / 64) * 3600 + 20000;
-    q.stagger = (ps_ > 0 && blocks > 2 * 256) ? (int)std::max<long long>(1, tile_cycles * ps_ / 64 / 7 / 4096) : 0;
-    hipLaunchKernelGGL((gemm_nt_persist_kernel<0, true>), dim3((unsigned)std::min<long long>(256, blocks)), dim3(512), 0, stream, q);
+    q.stagger = blocks > 2 * 256 ? (int)std::max<long long>(1, tile_cycles * NT_PERSIST_STAGGER64 / 64 / 7 / 4096) : 0;
+    hipLaunchKernelGGL((gemm_nt_persist_kernel<true>), dim3((unsigned)std::min<long long>(256, blocks)), dim3(512), 0, stream, q);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }

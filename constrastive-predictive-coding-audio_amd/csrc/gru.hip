@@ -458,7 +458,7 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_fwd_res_kernel(const bf16_t* 
 template <int KC>
 __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* __restrict__ dc, const bf16_t* __restrict__ tape,
                                                                   const bf16_t* __restrict__ WTfrag, bf16_t* __restrict__ dG,
-                                                                  int B, int V, int dbg) {
+                                                                  int B, int V) {
     typedef GruCfg<KC> Cfg;
     constexpr int H = Cfg::H, NT = Cfg::NT, NJT = Cfg::NJT, NW = GRU_NW, NTHR = 64 * NW;
     constexpr bool FULL = Cfg::FULL;
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
     __syncthreads();
 
     for (int t = V - 1; t >= 0; --t) {
-        if (t > 0 && !(dbg & 2)) {
+        if (t > 0) {
             const bf16_t* tp = tape + ((tape_bt + (t - 1)) * NW + wave) * Cfg::SLOTS * 64 * 8 + lane * 8;
 #pragma unroll
             for (int k = 0; k < Cfg::SLOTS; ++k) svn[k] = *(const uint4*)(tp + k * 64 * 8);
@@ -557,19 +557,17 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
         f32x4 acc[NJT];
 #pragma unroll
         for (int q = 0; q < NJT; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (!(dbg & 4)) {
 #pragma unroll
-            for (int kc = 0; kc < KC3; ++kc) {
-                // k-chunk kc of dgh = (dr, du, dn*r): columns [0, 2H) of the tile, then [3H, 4H)
-                const int chunk = (kc < 2 * KC ? kc * 4 : (3 * H / 8) + (kc - 2 * KC) * 4) + fg;
-                const uint4 gf = *(const uint4*)(gcur + frow * ROWB + chunk * 16);
+        for (int kc = 0; kc < KC3; ++kc) {
+            // k-chunk kc of dgh = (dr, du, dn*r): columns [0, 2H) of the tile, then [3H, 4H)
+            const int chunk = (kc < 2 * KC ? kc * 4 : (3 * H / 8) + (kc - 2 * KC) * 4) + fg;
+            const uint4 gf = *(const uint4*)(gcur + frow * ROWB + chunk * 16);
 #pragma unroll
-                for (int q = 0; q < NJT; ++q) {
-                    uint4 w;
-                    if (kc < KCR) w = wr[q][kc < KCR ? kc : 0];
-                    else w = *(const uint4*)(wl + (((wave * NJT + q) * KCL + (kc - KCR)) * 64 + lane) * 16);
-                    mfma_chunk<bf16_t>(acc[q], w, gf);
-                }
+            for (int q = 0; q < NJT; ++q) {
+                uint4 w;
+                if (kc < KCR) w = wr[q][kc < KCR ? kc : 0];
+                else w = *(const uint4*)(wl + (((wave * NJT + q) * KCL + (kc - KCR)) * 64 + lane) * 16);
+                mfma_chunk<bf16_t>(acc[q], w, gf);
             }
         }
 #pragma unroll
@@ -581,13 +579,11 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
         // also wait for the acknowledgement of the stores issued just before it (gru_fwd_res_kernel has the same arrangement).
         __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0), the other counters open
         asm volatile("" ::: "memory");
-        if (!(dbg & 1)) {
 #pragma unroll
-            for (int u = 0; u < GST; ++u) {
-                const int i = tid + u * NTHR;
-                const int rb = i / (4 * H / 8), cc = i % (4 * H / 8);
-                if ((GCH % NTHR == 0 || i < GCH) && b0 + rb < B) *(uint4*)(dG + ((long long)(b0 + rb) * V + t) * 4 * H + cc * 8) = gst[u];
-            }
+        for (int u = 0; u < GST; ++u) {
+            const int i = tid + u * NTHR;
+            const int rb = i / (4 * H / 8), cc = i % (4 * H / 8);
+            if ((GCH % NTHR == 0 || i < GCH) && b0 + rb < B) *(uint4*)(dG + ((long long)(b0 + rb) * V + t) * 4 * H + cc * 8) = gst[u];
         }
 #pragma unroll
         for (int k = 0; k < Cfg::SLOTS; ++k) sv[k] = svn[k];
@@ -623,8 +619,6 @@ __global__ __launch_bounds__(256) void prep_frag_kernel(const float* __restrict_
 
 // Debug / A-B switch: 1 = always use the weight-streaming kernels (set through cpc_gru_set_streaming).
 int g_gru_force_streaming = 0;
-int g_gru_debug = 0;             // timing experiments only (bit0: no gradient stores, bit1: no prefetch, bit2: no MFMA phase)
-int g_gru_waves = 8;   // (unused since the tape layout fixes 8 waves)            // waves per workgroup of the weight-resident kernels at H = 256 (8 or 16)
 
 static bool gru_ok(int B, int V, int H, int dtype) {
     const int ch = dtype == CPC_DTYPE_BF16 ? 8 : 4;
@@ -674,7 +668,7 @@ int launch_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* 
     if (dtype == CPC_DTYPE_BF16 && !g_gru_force_streaming && (H == 32 || H == 64 || H == 128 || H == 256)) {
 #define GRU_B(KC) \
     hipLaunchKernelGGL((gru_bwd_res_kernel<KC>), grid, dim3(64 * GRU_NW), 0, stream, dc, (const bf16_t*)tape, (const bf16_t*)WTfrag, \
-                       (bf16_t*)dG, B, V, g_gru_debug)
+                       (bf16_t*)dG, B, V)
         if (H == 256) GRU_B(8); else if (H == 128) GRU_B(4); else if (H == 64) GRU_B(2); else GRU_B(1);
 #undef GRU_B
         CPC_CHECK_LAUNCH();

@@ -370,8 +370,7 @@ int launch_conv_w_prep(const float* W, void* fwd, void* dgrd, int Cout, int Cin,
     while (tco > 1 && (long long)tco * (32 * kw + 1) > 16384) tco >>= 1;
     // (a 512 x 512 x 8 weight is 256 tiles of 32 x 32 channels: one workgroup per CU, each walking 96 elements per thread through index
     // arithmetic with nothing to hide its latency behind — 65 us for 2 M elements; 4 output channels per tile, eight times the workgroups: 25 us; 45 / 31 / 27 / 25 / 25 us at 32 / 16 / 8 / 4 / 2)
-    static const int tco_max = [] { const char* v = getenv("CPC_W_PREP_TCO"); return v ? atoi(v) : 4; }();
-    while (tco > tco_max && (long long)((Cin + 31) / 32) * ((Cout + tco - 1) / tco) < 2048) tco >>= 1;
+    while (tco > 4 && (long long)((Cin + 31) / 32) * ((Cout + tco - 1) / tco) < 2048) tco >>= 1;
     const dim3 grid((Cin + 31) / 32, (Cout + tco - 1) / tco);
     const size_t lds = (size_t)tco * (32 * kw + 1) * sizeof(float);
     if (dtype == CPC_DTYPE_BF16)
@@ -390,8 +389,7 @@ int launch_cast2d(const float* src, void* dst, int R, int C, long long sr, long 
     if (R <= 0 || C <= 0) return CPC_EINVAL;
     const long long n = (long long)R * C;
     const int blocks = (int)min((long long)2048, (n + 255) / 256);
-    static const int tiled = [] { const char* v = getenv("CPC_CAST2D_TILE"); return v ? atoi(v) : 1; }();
-    if (tiled && n >= 4096 && (C + 31) / 32 <= 65535 && (R + 31) / 32 <= 65535) {
+    if (n >= 4096 && (C + 31) / 32 <= 65535 && (R + 31) / 32 <= 65535) {
         const dim3 grid((C + 31) / 32, (R + 31) / 32);
         if (dtype == CPC_DTYPE_BF16)
             hipLaunchKernelGGL((cast2d_tile_kernel<bf16_t>), grid, dim3(256), 0, stream, src, (bf16_t*)dst, R, C, sr, sc);

@@ -1380,16 +1380,11 @@ static bool crop_ok(const int* ga, const int* gr, const int* go, int oh, int ow)
            oh >= 0 && ow >= 0 && oh + go[2] <= gr[2] && ow + go[1] <= gr[1];
 }
 
-static bool res8_enabled() {          // CPC_RES8=0: the 8-byte residual kernels (A/B switch)
-    static const bool on = [] { const char* v = getenv("CPC_RES8"); return !(v && v[0] == '0'); }();
-    return on;
-}
-
 int launch_residual_add(const void* a, const int* ga, const void* r, const int* gr, void* out, const int* go, int oh, int ow, int relu,
                         int r_f32, int dtype, hipStream_t st) {
     if (!crop_ok(ga, gr, go, oh, ow)) return CPC_EINVAL;
     const int nb = blocks_for((long long)go[0] * go[1] * go[2] * (go[5] / 4));
-    if (dtype == CPC_DTYPE_BF16 && !r_f32 && go[5] % 8 == 0 && res8_enabled()) {
+    if (dtype == CPC_DTYPE_BF16 && !r_f32 && go[5] % 8 == 0) {
         const int nb8 = blocks_for((long long)go[0] * go[1] * go[2] * (go[5] / 8));
         hipLaunchKernelGGL(residual_add8_kernel, dim3(nb8), dim3(256), 0, st, (const bf16_t*)a, mk(ga), (const bf16_t*)r, mk(gr), (bf16_t*)out, mk(go),
                            oh, ow, relu);
@@ -1410,7 +1405,7 @@ int launch_residual_add_bwd(const void* dout, const void* out, const int* go, vo
                             int ow, int relu, int r_f32, int dtype, hipStream_t st) {
     if (!crop_ok(ga, gr, go, oh, ow)) return CPC_EINVAL;
     const int nb = blocks_for((long long)go[0] * go[1] * go[2] * (go[5] / 4));
-    if (dtype == CPC_DTYPE_BF16 && !r_f32 && go[5] % 8 == 0 && res8_enabled()) {
+    if (dtype == CPC_DTYPE_BF16 && !r_f32 && go[5] % 8 == 0) {
         const int nb8 = blocks_for((long long)go[0] * go[1] * go[2] * (go[5] / 8));
         hipLaunchKernelGGL(residual_add_bwd8_kernel, dim3(nb8), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)out, mk(go), (bf16_t*)da, mk(ga),
                            (bf16_t*)dr, mk(gr), oh, ow, relu);

@@ -41,7 +41,8 @@ extern "C" {
 #define CPC_GEMM_BIG_TILE 0x100000 /* NT/bf16: the 256x256 tile also where fewer than 200 of them exist (M >= 256): a launch that is ONE nearly
                                     * full round of such tiles (layer 2's target rows at the headline size: 196) runs 0.11 instead of 0.135 ms */
 
-/* 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
+/* 9: the tuning-knob entry point (stagger, store policy, timing probes of the NT GEMM) is gone; cpc_gru_set_streaming is on / off only.
+ * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
  * cpc_stem_residual_wgrad_bits; cpc_gemm_tn_args grew a_rpi2 / a_item2.
@@ -264,8 +265,7 @@ int cpc_dropout_mask(float* mask, long long n, float drop_p, unsigned long long 
  *   before dropout; element index of the dropout mask = its offset in P).
  * Limits: S <= 64, C/heads <= 64 (-EINVAL otherwise).  The backward gives dqkv in the layout of qkv.
  * bf16 with C/heads == 64 (the reference's attention architectures) runs on the matrix pipe: scores, P V, dP, dq, dk, dv as 16x16x32
- * MFMAs with P / ds rounded to bf16 for the second products; other head sizes and f32 use vector kernels (f32 accumulation throughout).
- * CPC_ATTN_MFMA=0 in the environment forces the vector kernels (A/B). */
+ * MFMAs with P / ds rounded to bf16 for the second products; other head sizes and f32 use vector kernels (f32 accumulation throughout). */
 int cpc_attn_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int heads, float drop_p, unsigned long long seed,
                  unsigned site, int dtype, void* stream);
 int cpc_attn_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
@@ -531,14 +531,8 @@ int cpc_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const flo
 int cpc_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA, int B, int V, int H, void* stream);
 
 /* A/B switch: on != 0 forces the weight-streaming GRU kernels where the weight-resident bf16 ones would be used
- * (H in {32,64,128,256}); returns the previous setting.  Not stream-ordered (host-side flag). */
+ * (H in {32,64,128,256}), on == 0 restores the default; returns the previous setting (0 or 1).  Not stream-ordered (host-side flag). */
 int cpc_gru_set_streaming(int on);
-/* Tuning knobs for A/B measurements (tools/): key 1 = start stagger of the 256x256 NT GEMM in 1/64 of a tile time (0 = off);
- * keys 4, 5 = timing probes of that kernel's K loop (results are garbage, tools/nt_probe.py); key 6 = output stores of the NT fast
- * kernels: 2 (default) written through the L2 at system scope, 1 at agent scope, 0 plain stores — same results in every mode.
- * Returns the previous value, CPC_EINVAL for an unknown key.  Not part of the product path.  The probe keys 4 / 5 are refused
- * (CPC_EINVAL + a line on stderr) unless the process runs with CPC_ENABLE_PROBES=1, and announce themselves on stderr. */
-int cpc_debug_set(int key, int value);
 
 /* InfoNCE loss of ContrastiveEstimationTrainer.train, default branch score_over_all_timesteps=False
  * (contrastive_estimation_training.py:116-122, :141) on the equal-step scores S[k][b][b'] (f32, rows of ld >= B

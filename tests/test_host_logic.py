@@ -77,8 +77,8 @@ def test_model_surface_and_state_dict_keys():
         model(torch.zeros(2, 1, 18385))
 
 
-def test_c_abi_exports_every_declared_symbol():
-    """libcpc_hip.so loads on a CPU-only host and exports exactly what include/cpc_hip.h declares."""
+def test_c_abi_v9_exports_every_declared_symbol():
+    """libcpc_hip.so (ABI version 9) loads on a CPU-only host and exports exactly what include/cpc_hip.h declares."""
     header = open(os.path.join(ROOT, "include", "cpc_hip.h")).read()
     declared = set(re.findall(r"^\s*(?:int|long long)\s+(cpc_\w+)\s*\(", header, flags=re.M))
     assert declared, "no declarations parsed"
@@ -86,7 +86,7 @@ def test_c_abi_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(handle, name), f"{name} declared in the header but not exported"
     assert declared == set(_hip.EXPORTED_SYMBOLS)
-    assert handle.cpc_abi_version() == 8
+    assert handle.cpc_abi_version() == 9
     nm = subprocess.run(["nm", "-D", _hip.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (cpc_\w+)", nm))
     assert exported == declared

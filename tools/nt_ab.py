@@ -16,7 +16,6 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--fit", action="store_true")
 ap.add_argument("--B", type=int, default=256)
-ap.add_argument("--stagger", type=lambda t: [int(v) for v in t.split(",") if v], default=[])
 a = ap.parse_args()
 dev, bf, P = "cuda:0", torch.bfloat16, _hip.ptr
 B, C = a.B, 512
@@ -74,18 +73,8 @@ for name, Lo, kw, s in LAYERS:
     def dgrad(flags):
         _hip.gemm_nt(P(dy, guard - (D - 1) * C), P(wd), P(xo, guard), M, s * C, D * C, C, D * C, s * C, 1, mask=P(x, guard), flags=flags)
 
-    def stag(fn, v):
-        def run():
-            _hip.lib().cpc_debug_set(1, v)
-            fn(0)
-            _hip.lib().cpc_debug_set(1, 0)
-        return run
-
     fv = {"default": lambda: fwd(0), "lds": lambda: fwd(_hip.GEMM_NO_PERS), "lds-lin": lambda: fwd(_hip.GEMM_NO_PERS | _hip.GEMM_LINEAR_K)}
     dv = {"default": lambda: dgrad(0), "lds": lambda: dgrad(_hip.GEMM_NO_PERS), "lds-lin": lambda: dgrad(_hip.GEMM_NO_PERS | _hip.GEMM_LINEAR_K)}
-    for v in a.stagger:
-        fv[f"st{v}"] = stag(fwd, v)
-        dv[f"st{v}"] = stag(dgrad, v)
     ab(f"{name} fwd", fv, 2.0 * M * C * kw * C)
     ab(f"{name} dgrad", dv, 2.0 * M * s * C * D * C)
     del y, dy

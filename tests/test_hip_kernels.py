@@ -1,4 +1,7 @@
-"""GPU unit tests of every C-ABI entry point against plain PyTorch CPU references (float64 where cheap).
+"""GPU unit tests of the C-ABI entry points of the GEMMs, the encoder / context / score kernels and the scalogram grid primitives against
+plain PyTorch CPU references (float64 where cheap).  The scalogram stem, depthwise and gradient-penalty kernels are tested in
+test_scalogram_kernels_gpu.py; test_host_logic.py::test_every_abi_entry_point_is_named_by_a_test lists the entry points that only
+whole-model tests reach.
 
 Tolerances: f32 mode 2e-5 relative to the operand scale (exact-f32 MFMA, different summation order);
 bf16 mode 1e-2 (inputs rounded to 8 significant bits, f32 accumulation).
@@ -253,7 +256,7 @@ def test_gemm_nt_gathered_rows_are_a_conv2d(dt, B, W, H, C, cout, kh, kw, sh, sw
 
 @pytest.mark.parametrize("dt", DTYPES)
 def test_conv_w_prep_batch_and_group(dt):
-    """cpc_conv_w_prep_plan / _batch: several convolutions' operand layouts in one launch, bitwise equal to one cpc_conv_w_prep each
+    """cpc_conv_w_prep_plan / cpc_conv_w_prep_batch (through _hip.ConvPrepBatch): several convolutions' operand layouts in one launch, bitwise equal to one cpc_conv_w_prep each
     (different shapes, one without a data-gradient operand).  cpc_conv_w_prep_group: the G shifted kernel copies of a tall (kh,1)
     convolution computed G rows per GEMM row, against their definition."""
     g = torch.Generator().manual_seed(5)

@@ -118,6 +118,106 @@ def test_over_read_contract_is_checked_before_any_launch():
     assert lib.cpc_gemm_nt(C.byref(args), s) == -22
 
 
+# (Cin, kh, kw, sh) window shapes with stem kernels (csrc/stem.hip STEM_SHAPES)
+STEM_SHAPES = [(2, 3, 3, 2), (1, 3, 3, 2), (2, 3, 3, 1), (1, 3, 3, 1), (1, 5, 1, 1), (2, 5, 1, 1), (1, 2, 2, 1), (2, 2, 2, 1)]
+
+
+def _stem_height_limit(lib, cin, cout, kh, kw, sh, ph=1):
+    hs = [h for h in range(1, 4096) if lib.cpc_stem_supported(cin, cout, kh, kw, sh, h, ph)]
+    assert hs and hs == list(range(1, hs[-1] + 1)), "supported heights are not one range starting at 1"
+    return hs[-1]
+
+
+def test_stem_supported_truth_table():
+    """cpc_stem_supported (a host function): every compiled window shape with every admitted Cout at small heights; no other Cout,
+    Cin or stride; and no height beyond the LDS limit."""
+    lib = _hip.lib()
+    for cin, kh, kw, sh in STEM_SHAPES:
+        for cout in (4, 8, 16, 32, 64):
+            for hin in (1, 16, 64):
+                for ph in (0, 1):
+                    assert lib.cpc_stem_supported(cin, cout, kh, kw, sh, hin, ph) == 1, (cin, cout, kh, kw, sh, hin, ph)
+        for cout in (12, 48, 68, 0, 2, 128):
+            assert lib.cpc_stem_supported(cin, cout, kh, kw, sh, 16, 1) == 0, (cin, cout, kh, kw, sh)
+        assert lib.cpc_stem_supported(3, 16, kh, kw, sh, 16, 1) == 0
+        hmax = _stem_height_limit(lib, cin, 16, kh, kw, sh)
+        assert hmax >= 128, "the stem no longer takes a 128-bin scalogram"
+        assert lib.cpc_stem_supported(cin, 16, kh, kw, sh, hmax + 1, 1) == 0
+        assert _stem_height_limit(lib, cin, 64, kh, kw, sh) == hmax          # Cout does not enter the input-column bound
+    assert lib.cpc_stem_supported(1, 16, 3, 3, 3, 16, 1) == 0
+    assert lib.cpc_stem_supported(2, 16, 3, 3, 3, 16, 1) == 0
+
+
+def test_stem_arguments_are_checked_before_any_launch():
+    """cpc_stem_stats returns CPC_EINVAL (-22) for shapes without kernels, for input grids the stem does not take and for nblocks <= 0:
+    argument checks that return before a launch, so this runs without a GPU."""
+    import ctypes as C
+    lib = _hip.lib()
+    P = C.c_void_p(0x1000)        # never dereferenced
+    s = C.c_void_p(0)
+
+    def stats(cin, H, kh, kw, sh, ph, nblocks, cout=16, top=0):
+        W = 4
+        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) + 1
+        gx = (C.c_int * 6)(2, W, H, top + H, top, cin)
+        conv = (C.c_int * 9)(cout, kh, kw, sh, 1, ph, ph, Ho, Wo)
+        return lib.cpc_stem_stats(P, C.cast(gx, C.c_void_p), P, None, C.cast(conv, C.c_void_p), P, nblocks, s)
+
+    assert stats(3, 16, 3, 3, 1, 1, 4) == -22                       # Cin 3
+    assert stats(1, 16, 3, 3, 3, 1, 4) == -22                       # stride 3
+    assert stats(1, 16, 3, 3, 1, 1, 4, cout=12) == -22              # Cout 12
+    assert stats(1, 16, 3, 3, 1, 1, 0) == -22                       # nblocks 0
+    assert stats(2, 16, 3, 3, 2, 1, -3) == -22                      # nblocks < 0
+    assert stats(1, 16, 3, 3, 1, 1, 4, top=2) == -22                # input grid with top rows
+    hmax = _stem_height_limit(lib, 2, 16, 3, 3, 2)
+    assert stats(2, hmax + 1, 3, 3, 2, 1, 4) == -22                 # beyond the LDS limit
+
+
+# Entry points of include/cpc_hip.h that no test names, each with the reason.  Only entry points outside the scalogram path may stand
+# here; the list may only shrink (a name that a test mentions must leave it).
+ABI_NAMES_WITHOUT_A_TEST = {
+    "cpc_abi_version": "checked by the library loader (_hip.lib) and by test_c_abi_v9_exports_every_declared_symbol in this file",
+    "cpc_conv1_fwd_rows": "encoder row-range launch: only through test_model_gpu.py::test_target_lanes_equal_the_single_lane_step",
+    "cpc_conv_dgrad_rows": "encoder row-range launch: only through test_target_lanes_equal_the_single_lane_step",
+    "cpc_conv_dgrad_conv1_rows": "encoder row-range launch: only through test_target_lanes_equal_the_single_lane_step",
+    "cpc_conv1_fused_reduce_tiles": "encoder row-range reduction: only through test_target_lanes_equal_the_single_lane_step",
+    "cpc_maxpool_fwd": "ConvAr context pooling: only through whole-model runs",
+    "cpc_maxpool_bwd": "ConvAr context pooling backward: only through whole-model runs",
+    "cpc_relu_row_bwd": "ConvAr context ReLU backward: only through whole-model runs",
+    "cpc_gru_fwd_h0": "GRU forward from a given initial state: only through whole-model runs",
+    "cpc_gru_set_streaming": "GRU launch-mode switch: only through whole-model runs",
+    "cpc_nce_eval": "evaluation-mode NCE scores: only through the trainer's validation path",
+    "cpc_nce_eval_workspace_floats": "workspace size of cpc_nce_eval: only through the trainer's validation path",
+    "cpc_cast2d": "weight casts of the context network: only through whole-model runs",
+    "cpc_cast2d_batch": "batched weight casts: only through whole-model runs",
+    "cpc_dropout": "attention dropout: only through test_gradient_penalty_attention_context_with_dropout_against_oracle",
+    "cpc_split3_bf16": "bf16x3 CQT operand split: only through test_cqt_full_size_against_oracle",
+    "cpc_scalogram_pointwise": "scalogram pointwise chain: only through the CQT / preprocessing tests against reference fixtures",
+}
+
+
+def test_every_abi_entry_point_is_named_by_a_test():
+    """Every cpc_* function of include/cpc_hip.h is named by a test module other than this one, or listed above with a reason; a listed
+    name that a test does name must leave the list."""
+    header = open(os.path.join(ROOT, "include", "cpc_hip.h")).read()
+    declared = set(re.findall(r"^\s*(?:int|long long)\s+(cpc_\w+)\s*\(", header, flags=re.M))
+    assert len(declared) > 90, "header parse found too few entry points"
+    here = os.path.abspath(__file__)
+    tests_dir = os.path.dirname(here)
+    text = ""
+    for name in sorted(os.listdir(tests_dir)):
+        path = os.path.join(tests_dir, name)
+        if name.endswith(".py") and os.path.abspath(path) != here:
+            text += open(path).read()
+    named = {n for n in declared if re.search(r"\b" + n + r"\b", text)}
+    untested = sorted(declared - named - set(ABI_NAMES_WITHOUT_A_TEST))
+    assert not untested, f"entry points named by no test: {untested}"
+    stale = sorted(set(ABI_NAMES_WITHOUT_A_TEST) & named)
+    assert not stale, f"named by a test now, remove from ABI_NAMES_WITHOUT_A_TEST: {stale}"
+    unknown = sorted(set(ABI_NAMES_WITHOUT_A_TEST) - declared)
+    assert not unknown, f"not declared in include/cpc_hip.h: {unknown}"
+
+
 def test_engine_guard_rows_cover_every_over_read():
     """EncoderGeometry / CPCEngine._buf: the guard in front of and behind every activation buffer is at least what the
     overlapped-row GEMMs of its consumers read there, also for kernels much wider than their stride."""

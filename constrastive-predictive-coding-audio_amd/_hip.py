@@ -173,6 +173,9 @@ _SIGNATURES = {
     "cpc_gp_score_coeff": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
     "cpc_nce_eval_workspace_floats": ([_I, _I], _L),
     "cpc_nce_eval": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
+    "cpc_diff_scores": ([_P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _L, _L, _L, _L, _I, _I, _I, _P], _I),
+    "cpc_diff_scores_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _P], _I),
+    "cpc_diff_scores_rank1": ([_P, _P, _P, _I, _I, _I, _L, _L, _I, _P], _I),
     "cpc_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P], _I),
     "cpc_adam_dev": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _F, _P, _P], _I),
 }

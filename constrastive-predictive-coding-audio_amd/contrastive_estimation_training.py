@@ -4,7 +4,7 @@ Mirrors the reference's ``contrastive_estimation_training.py`` (score functions 
 DeterministicSampler :363-382, grad_mean_var :385-391).  ``train`` has two routes:
 
 * fused (the hot path): AudioEncoder + AudioGRUModel model, softplus/linear score (either ``score_over_all_timesteps``
-  setting), Adam.  Forward, InfoNCE loss, analytic backward and the Adam update all run as
+  setting), Adam; the difference score with Adam takes it too (``_engine_difference``), except under global negatives.  Forward, InfoNCE loss, analytic backward and the Adam update all run as
   HIP kernels (engine.CPCEngine); with torch.distributed initialised, one process per GPU, the flat gradient buffer is
   all-reduced over RCCL before the update (per-GPU in-batch negatives).
 * generic: any other score function or optimizer: the model forward and backward run on the HIP path through the autograd
@@ -13,6 +13,7 @@ DeterministicSampler :363-382, grad_mean_var :385-391).  ``train`` has two route
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import random
@@ -134,10 +135,57 @@ def softplus_score_function(predicted_z, targets):
     return F.softplus(_ScoreContraction.apply(predicted_z, targets))
 
 
+class _DifferenceScores(torch.autograd.Function):
+    """scores[b, k, b', k'] = 1 / sum_e (predicted_z[b, k, e] - targets[b', e, k'])^2 as ONE cpc_diff_scores launch over the (B K) x E
+    operands (f32, differences formed first, as the reference does); memory O((B K)^2): the scores and their transpose are kept for
+    the backward, which is cpc_diff_scores_bwd (G = 2 g s^2 and its row / column sums), the two contractions of the linear score's
+    gradient with G and the rank-1 terms (cpc_diff_scores_rank1)."""
+
+    @staticmethod
+    def forward(ctx, predicted_z, targets):
+        from . import _hip
+        _need_gpu(predicted_z, "the difference score function")
+        B, K, E = predicted_z.shape
+        if tuple(targets.shape) != (B, E, K) or E % 4 or (B * K) % 4:
+            raise ValueError("difference scores: expected predicted_z (B, K, E) and targets (B, E, K) with E and B*K multiples of 4")
+        R = B * K
+        A = predicted_z.detach().reshape(R, E).float().contiguous()
+        Tt = targets.detach().permute(0, 2, 1).reshape(R, E).float().contiguous()
+        S = torch.empty(R, R, device=A.device, dtype=torch.float32)
+        ST = torch.empty(R, R, device=A.device, dtype=torch.float32)
+        L = ctypes.c_longlong
+        _hip.call("cpc_diff_scores", _hip.ptr(A), _hip.ptr(Tt), _hip.ptr(S), _hip.ptr(ST), R, R, E, L(E), L(E), 0, L(0), L(0), L(0), L(0),
+                  1, R, _hip.F32, work=2.0 * R * R * E)
+        ctx.save_for_backward(A, Tt, S, ST)
+        ctx.shape = (B, K, E)
+        return S.view(B, K, B, K)
+
+    @staticmethod
+    def backward(ctx, d_scores):
+        from . import _hip
+        A, Tt, S, ST = ctx.saved_tensors
+        B, K, E = ctx.shape
+        R = B * K
+        G = torch.empty(R, R, device=S.device, dtype=torch.float32)           # overwritten in place below: never autograd's own buffer
+        G.copy_(d_scores.reshape(R, R))
+        GT = G.t().contiguous()
+        sums = torch.empty(2, R, device=S.device, dtype=torch.float32)
+        L, P = ctypes.c_longlong, _hip.ptr
+        _hip.call("cpc_diff_scores_bwd", P(G), P(S), P(sums[0]), P(GT), P(ST), P(sums[1]), R, R, R, L(0), 1, _hip.F32)
+        dA = torch.empty(R, E, device=S.device, dtype=torch.float32)
+        dT = torch.empty(R, E, device=S.device, dtype=torch.float32)
+        TtT = Tt.t().contiguous()                                                        # [E][R]
+        _hip.gemm_nt(P(G), P(TtT), P(dA), R, E, R, R, R, E, _hip.F32)                   # dA = G Tt
+        _hip.gemm_tn(P(G), P(A), P(dT), R, R, E, R, E, E, _hip.F32, flags=_hip.GEMM_OUT_F32)   # dT = G^T A
+        _hip.call("cpc_diff_scores_rank1", P(sums[0]), P(A), P(dA), R, E, 0, L(0), L(E), _hip.F32)    # - rowsum(G) * predicted_z
+        _hip.call("cpc_diff_scores_rank1", P(sums[1]), P(Tt), P(dT), R, E, 0, L(0), L(E), _hip.F32)   # - colsum(G) * targets
+        return dA.view(B, K, E), dT.view(B, K, E).permute(0, 2, 1)
+
+
 def difference_score_function(predicted_z, targets):
-    """1 / squared distance between every prediction and every target (reference :25-33); O(B^2 K^2 E) memory."""
-    diff = predicted_z.unsqueeze(3).unsqueeze(4) - targets.permute(1, 0, 2).unsqueeze(0).unsqueeze(1)
-    return 1 / torch.sum(diff ** 2, dim=2)
+    """1 / squared distance between every prediction and every target (reference :25-33), as HIP kernels (_DifferenceScores):
+    O((B K)^2) memory instead of the reference broadcast's O(B^2 K^2 E)."""
+    return _DifferenceScores.apply(predicted_z, targets)
 
 
 def _score_layout(scores4, all_timesteps):
@@ -267,6 +315,16 @@ class ContrastiveEstimationTrainer:
     def _fused(self):
         return self.score_function in (softplus_score_function, linear_score_function) and self.optimizer is torch.optim.Adam
 
+    def _engine_difference(self):
+        """difference_score_function + Adam also runs the whole step on the engine (cpc_diff_scores and its backward, FusedAdam, the
+        device NaN guard); under global negatives it keeps the generic route."""
+        return self.score_function is difference_score_function and self.optimizer is torch.optim.Adam and not self.global_negatives
+
+    def _score_kind(self):
+        if self.score_function is difference_score_function:
+            return "difference"
+        return "softplus" if self.score_function is softplus_score_function else "linear"
+
     @staticmethod
     def _world():
         import torch.distributed as dist
@@ -331,7 +389,8 @@ class ContrastiveEstimationTrainer:
         device = self._device()
         rank, world = self._world()
         self.model.train()
-        fused = self._fused()
+        fused = self._fused() or self._engine_difference()
+        kind = self._score_kind()
         if fused:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
             self.model._flatten_parameters(device)
@@ -470,7 +529,7 @@ class ContrastiveEstimationTrainer:
                         key = (batch.shape[0], batch.shape[1])
                         if key not in graph_steps:
                             graph_steps[key] = GraphedStep(eng, optimizer, self.score_function is softplus_score_function,
-                                                           float(self.regularization), bool(self.score_over_all_timesteps))
+                                                           float(self.regularization), bool(self.score_over_all_timesteps), score=kind)
                         if id(eng) not in guarded:
                             eng.nan_flag().zero_()
                             guarded.add(id(eng))
@@ -520,7 +579,8 @@ class ContrastiveEstimationTrainer:
                                                      regularization=float(self.regularization),
                                                      all_timesteps=bool(self.score_over_all_timesteps),
                                                      grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
-                                                     global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None)
+                                                     global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
+                                                     score=kind)
                         if sync is not None:
                             sync.finish()
                         # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
@@ -595,7 +655,7 @@ class ContrastiveEstimationTrainer:
                                    verbose=self.verbose)
         sums = torch.zeros(2 * K + 1, device=device, dtype=torch.float32)
         ws = torch.empty(int(_hip.lib().cpc_nce_eval_workspace_floats(batch_size, K)), device=device, dtype=torch.float32)
-        kernel_scores = self.score_function in (softplus_score_function, linear_score_function)
+        kernel_scores = self.score_function in (softplus_score_function, linear_score_function, difference_score_function)
         self.model.eval()
         done = 0
         with torch.no_grad():
@@ -606,7 +666,7 @@ class ContrastiveEstimationTrainer:
                 if kernel_scores:
                     eng = self.model.engine_for(x)
                     eng.forward(x.float() if x.dim() == 4 else x[:, 0, :].contiguous().float())
-                    eng.nce_eval(self.score_function is softplus_score_function, all_t, sums, ws)
+                    eng.nce_eval(self.score_function is softplus_score_function, all_t, sums, ws, score=self._score_kind())
                 else:
                     predicted_z, targets, _, _ = self.model(x)
                     S, ld = _score_layout(self.score_function(predicted_z, targets), all_t)

@@ -695,6 +695,30 @@ int cpc_nce_eval(const float* S, float* out, float* workspace, int B, int K, int
     return launch_nce_eval(S, out, workspace, B, K, ld, softplus, all_timesteps, accumulate, (hipStream_t)stream);
 }
 
+int cpc_diff_scores(const void* P, const void* T, float* S, float* ST, int M, int N, int E, long long ldp, long long ldt, int t_rpi,
+                    long long t_item, long long p_batch, long long t_batch, long long s_batch, int batch, int lds, int dtype, void* stream) {
+    if (!P || !T || !S || M <= 0 || N <= 0 || E <= 0 || batch <= 0 || t_rpi < 0 || lds < N || (ST && lds < M)) return CPC_EINVAL;
+    if (batch > 1 && s_batch < (long long)lds * (ST ? std::max(M, N) : M)) return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_F32 && dtype != CPC_DTYPE_BF16) return CPC_EINVAL;
+    return launch_diff_scores(P, T, S, ST, M, N, E, ldp, ldt, t_rpi, t_item, p_batch, t_batch, s_batch, batch, lds, dtype, (hipStream_t)stream);
+}
+
+int cpc_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const float* ST, float* sumsT, int M, int N, int lds,
+                        long long s_batch, int batch, int dtype, void* stream) {
+    if (!G || !S || !sums || M <= 0 || N <= 0 || batch <= 0 || lds < N) return CPC_EINVAL;
+    if (GT && (!ST || !sumsT || lds < M)) return CPC_EINVAL;
+    if (batch > 1 && s_batch < (long long)lds * (GT ? std::max(M, N) : M)) return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_F32 && dtype != CPC_DTYPE_BF16) return CPC_EINVAL;
+    return launch_diff_scores_bwd(G, S, sums, GT, ST, sumsT, M, N, lds, s_batch, batch, dtype, (hipStream_t)stream);
+}
+
+int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
+                          void* stream) {
+    if (!mu || !X || !out || rows <= 0 || E <= 0 || rpi < 0) return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_F32 && dtype != CPC_DTYPE_BF16) return CPC_EINVAL;
+    return launch_diff_scores_rank1(mu, X, out, rows, E, rpi, item, ld, dtype, (hipStream_t)stream);
+}
+
 int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
              float grad_scale, const float* skip, void* stream) {
     if (!p || !g || !m || !v) return CPC_EINVAL;

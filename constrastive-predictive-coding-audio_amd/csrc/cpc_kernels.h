@@ -156,6 +156,13 @@ int launch_gp_score_coeff(const float* S, const float* St1, const float* St2, fl
 long long nce_eval_workspace_floats(int B, int K);
 int launch_nce_eval(const float* S, float* out, float* workspace, int B, int K, int ld, int softplus, int all_timesteps,
                     int accumulate, hipStream_t stream);
+int launch_diff_scores(const void* P, const void* Tg, float* S, float* ST, int M, int N, int E, long long ldp, long long ldt, int t_rpi,
+                       long long t_item, long long p_batch, long long t_batch, long long s_batch, int batch, int lds, int dtype,
+                       hipStream_t stream);
+int launch_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const float* ST, float* sumsT, int M, int N, int lds,
+                           long long s_batch, int batch, int dtype, hipStream_t stream);
+int launch_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
+                             hipStream_t stream);
 int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype, hipStream_t stream);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, const float* skip, hipStream_t stream);

@@ -28,6 +28,18 @@ from . import _hip
 
 _SIDE_STREAMS = {}
 
+SCORE_KINDS = ("softplus", "linear", "difference")
+
+
+def score_kind(softplus: bool, score: Optional[str] = None) -> str:
+    """The score function a loss call runs: ``score`` ("softplus" | "linear" | "difference") when given, else the ``softplus`` flag's
+    choice between the two dot-product scores (contrastive_estimation_training.py:12-33)."""
+    if score is None:
+        return "softplus" if softplus else "linear"
+    if score not in SCORE_KINDS:
+        raise ValueError(f"score must be one of {SCORE_KINDS}, got {score!r}")
+    return score
+
 
 def side_stream(device):
     """ONE high-priority side stream per device for the whole process, shared by every engine: HIP multiplexes its streams
@@ -530,11 +542,14 @@ class CPCEngine:
                      b_rpi=K, b_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
         return 2.0 * R * R * E
 
-    def nce_forward_backward(self, softplus: bool, regularization: float):
+    def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None):
         """Equal-step scores, InfoNCE loss + regulariser, and d loss / d (predicted_z, targets).
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
-        (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs)."""
+        (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs).
+        ``score``: see score_kind; "difference" runs _diff_forward_backward."""
+        if score_kind(softplus, score) == "difference":
+            return self._diff_forward_backward(False, regularization)
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         top, dtop = self.act[-1], self.dact[-1]
@@ -593,16 +608,9 @@ class CPCEngine:
                   C.c_float(B), K, C.c_float(regularization), 1 if softplus else 0, P(self.nce_out))
         self._score_grads_all(f.dS, f.dST, self.pred, top, self.dpred, dtop)
 
-    def nce_all_forward_backward(self, softplus: bool, regularization: float):
-        """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
-        matrix (and its transpose, as a second tiny GEMM, so that both gradient layouts are written coalesced), the
-        log-sum-exp over ALL predictions for every (target item, step), and d loss / d (predicted_z, targets).
-        bf16 storage and tile-sized problems take the fused route (_nce_all_fused) instead."""
-        if self.fused_scores_ok():
-            return self._nce_all_fused(softplus, regularization)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        top, dtop = self.act[-1], self.dact[-1]
+    def _all_buffers(self):
+        """Score, gradient and workspace buffers of the unfused all-timesteps loss (allocated on first use)."""
+        B, K = self.B, self.K
         R = B * K
         ld = _ceil_div(R, 8) * 8
         if getattr(self, "ST_all", None) is None:
@@ -613,6 +621,23 @@ class CPCEngine:
             self.dS_all = torch.zeros(R * ld, device=self.device, dtype=self.dt)
             self.dST_all = torch.zeros(R * ld, device=self.device, dtype=self.dt)
             self.nce_all_ws = torch.empty(int(_hip.lib().cpc_nce_all_workspace_floats(B, K)), device=self.device, dtype=f32)
+        return ld
+
+    def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None):
+        """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
+        matrix (and its transpose, as a second tiny GEMM, so that both gradient layouts are written coalesced), the
+        log-sum-exp over ALL predictions for every (target item, step), and d loss / d (predicted_z, targets).
+        bf16 storage and tile-sized problems take the fused route (_nce_all_fused) instead; difference scores never do
+        (cpc_score_lse is a dot-product kernel): they run _diff_forward_backward."""
+        if score_kind(softplus, score) == "difference":
+            return self._diff_forward_backward(True, regularization)
+        if self.fused_scores_ok():
+            return self._nce_all_fused(softplus, regularization)
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        top, dtop = self.act[-1], self.dact[-1]
+        R = B * K
+        ld = self._all_buffers()
         tg = (T - K) * E
         self.score_gemm_all()
         _hip.gemm_nt(_hip.ptr(top, tg), _hip.ptr(self.pred), _hip.ptr(self.ST_all), R, R, E, E, E, ld, code,
@@ -640,23 +665,91 @@ class CPCEngine:
         _hip.gemm_nt(_hip.ptr(WT), _hip.ptr(self.predT), _hip.ptr(out_top, tg), R, E, ld, ld, ld, E, code,
                      c_rpi=K, c_item=Ltop * E, c_valid=K)
 
-    def nce_eval(self, softplus: bool, all_timesteps: bool, sums, workspace):
+    def nce_eval(self, softplus: bool, all_timesteps: bool, sums, workspace, score: Optional[str] = None):
         """Adds this batch's validation quantities (per-step losses, per-step accuracies, mean score: include/cpc_hip.h,
-        cpc_nce_eval) to ``sums`` (2 K + 1 floats) — from the score matrices of the train step (forward() must have run)."""
+        cpc_nce_eval) to ``sums`` (2 K + 1 floats) — from the score matrices of the train step (forward() must have run).
+        ``score``: see score_kind (difference scores are formed by cpc_diff_scores, then read as linear scores)."""
         code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        top = self.act[-1]
-        tg = (T - K) * E
+        kind = score_kind(softplus, score)
+        diff = kind == "difference"
         if all_timesteps:
             ld = _ceil_div(B * K, 8) * 8
-            self.score_gemm_all()
+            if diff:
+                if getattr(self, "S_all", None) is None:
+                    self.S_all = torch.zeros(B * K * ld, device=self.device, dtype=torch.float32)
+                self.diff_scores_all(self.S_all, None)
+            else:
+                self.score_gemm_all()
             S = self.S_all
         else:
             ld = self.ldS
-            self.score_gemm()
+            if diff:
+                self.diff_scores(self.S, None)
+            else:
+                self.score_gemm()
             S = self.S
-        _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), B, K, ld, 1 if softplus else 0,
+        _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), B, K, ld, 1 if kind == "softplus" else 0,
                   1 if all_timesteps else 0, 1)
+
+    # ---- difference scores (contrastive_estimation_training.py:25-33; include/cpc_hip.h, cpc_diff_scores) ----
+    def diff_scores(self, S, ST):
+        """Default branch: S[k][b][b'] = 1 / |predicted_z[b, k] - targets[b', :, k]|^2 (and ST[k][b'][b], unless None) from the
+        engine's own layouts.  Returns the launch's algorithmic FLOPs (one sub + one fma per feature and pair)."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
+        work = 2.0 * K * B * B * E
+        _hip.call("cpc_diff_scores", _hip.ptr(self.pred), _hip.ptr(self.act[-1], (T - K) * E), _hip.ptr(S), _hip.ptr(ST), B, B, E,
+                  C.c_longlong(K * E), C.c_longlong(Ltop * E), 0, C.c_longlong(0), C.c_longlong(E), C.c_longlong(E),
+                  C.c_longlong(B * ld), K, ld, code, work=work)
+        return work
+
+    def diff_scores_all(self, S, ST):
+        """score_over_all_timesteps=True: the (B K) x (B K) difference scores S (and ST, unless None) from one pass."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        R = B * K
+        ld = _ceil_div(R, 8) * 8
+        work = 2.0 * R * R * E
+        _hip.call("cpc_diff_scores", _hip.ptr(self.pred), _hip.ptr(self.act[-1], (T - K) * E), _hip.ptr(S), _hip.ptr(ST), R, R, E,
+                  C.c_longlong(E), C.c_longlong(E), K, C.c_longlong(Ltop * E), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), 1, ld,
+                  code, work=work)
+        return work
+
+    def _diff_forward_backward(self, all_timesteps: bool, regularization: float):
+        """InfoNCE loss + regulariser on difference scores and d loss / d (predicted_z, targets).  The loss kernels take the scores
+        as linear scores (softplus = 0, as contrastive_estimation_training._InfoNCE does); with d = |p - t|^2 and s = 1 / d,
+        d loss / d d = -g s^2 for g = d loss / d s, so the gradient is the linear score's two contractions with G = 2 g s^2
+        minus the rank-1 terms (row / column sums of G) * (p / t): cpc_diff_scores_bwd, _score_grads(_all), cpc_diff_scores_rank1.
+        In bf16 storage G is rounded to bf16 (the operand type of the contractions) and its sums are taken of the rounded values."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        top, dtop = self.act[-1], self.dact[-1]
+        R = B * K
+        if getattr(self, "_diff_mu", None) is None:
+            self._diff_mu = torch.empty(2, R, device=self.device, dtype=torch.float32)
+        mu, nu = self._diff_mu[0], self._diff_mu[1]
+        P = _hip.ptr
+        if all_timesteps:
+            ld = self._all_buffers()
+            S, ST, dS, dST = self.S_all, self.ST_all, self.dS_all, self.dST_all
+            self.diff_scores_all(S, ST)
+            _hip.call("cpc_nce_loss_all", P(S), P(ST), P(dS), P(dST), P(self.nce_out), P(self.nce_all_ws), B, K, ld, 0,
+                      C.c_float(regularization), code)
+            _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), R, R, ld, C.c_longlong(0), 1, code)
+            self._score_grads_all(dS, dST, self.pred, top, self.dpred, dtop)
+        else:
+            ld = self.ldS
+            if getattr(self, "ST", None) is None:
+                self.ST = torch.zeros_like(self.S)
+            S, ST, dS, dST = self.S, self.ST, self.dS, self.dST
+            self.diff_scores(S, ST)
+            _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_ws), B, K, ld, 0, C.c_float(regularization), code)
+            _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), B, B, ld, C.c_longlong(B * ld), K, code)
+            self._score_grads(dS, dST, self.pred, top, self.dpred, dtop)
+        # mu / nu are indexed like predicted_z's and the targets' (b, k) rows in both branches
+        _hip.call("cpc_diff_scores_rank1", P(mu), P(self.pred), P(self.dpred), R, E, 0, C.c_longlong(0), C.c_longlong(E), code)
+        tg = (T - K) * E
+        _hip.call("cpc_diff_scores_rank1", P(nu), P(top, tg), P(dtop, tg), R, E, K, C.c_longlong(Ltop * E), C.c_longlong(E), code)
 
     # ------------------------------------------------------------------------------------------ backward
     def _tn_to_grad(self, A, B_, grad, M, I, J, lda, ldb, nsplit, grad_offset=0, scratch=None, **kw):
@@ -906,19 +999,24 @@ class CPCEngine:
 
     # ------------------------------------------------------------------------------------------ whole step
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
-                       global_negatives=None, after_loss=None):
+                       global_negatives=None, after_loss=None, score: Optional[str] = None):
         """Forward + loss + backward; returns the device tensor [loss, max_score, -mean valid, mean lse, reg, NaN indicator of
         this step, sticky NaN flag, -] (no sync; include/cpc_hip.h, cpc_nce_loss).
         ``global_negatives``: a GlobalNegatives object — the loss is then taken over the batches of ALL ranks.
         ``after_loss(nce_out)`` is called once the loss kernels are queued and before the backward pass is: data-parallel runs
-        start the reduction of the NaN flag over the ranks there (GradAllReduce.reduce_flag)."""
+        start the reduction of the NaN flag over the ranks there (GradAllReduce.reduce_flag).
+        ``score``: "softplus" | "linear" | "difference" (score_kind; None: the ``softplus`` flag decides)."""
+        kind = score_kind(softplus, score)
+        if kind == "difference" and global_negatives is not None:
+            raise NotImplementedError("difference scores under global negatives are not on the HIP path: the trainer takes the generic "
+                                      "route there (contrastive_estimation_training.difference_score_function)")
         self.forward(x)
         if global_negatives is not None:
             global_negatives.forward_backward(softplus, regularization, all_timesteps)
         elif all_timesteps:
-            self.nce_all_forward_backward(softplus, regularization)
+            self.nce_all_forward_backward(softplus, regularization, score=kind)
         else:
-            self.nce_forward_backward(softplus, regularization)
+            self.nce_forward_backward(softplus, regularization, score=kind)
         if after_loss is not None:
             after_loss(self.nce_out)
         self.backward(x, grad_ready_hook=grad_ready_hook)
@@ -2246,7 +2344,7 @@ class GraphedStep:
     launch overhead.  Kept as an option for hosts with slower launch paths.  Requirements: single process (no collective inside the graph), no host-side per-step state
     (dropout seeds)."""
 
-    def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False):
+    def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None):
         if opt.state is None:
             raise ValueError("GraphedStep needs FusedAdam(device_step=True)")
         ctx = eng.ctx
@@ -2256,6 +2354,8 @@ class GraphedStep:
         shape = getattr(eng, "in_shape", None) or (eng.B, eng.L)
         self.x = torch.zeros(*shape, device=eng.device, dtype=torch.float32)
         args = dict(softplus=softplus, regularization=regularization, all_timesteps=all_timesteps)
+        if score is not None:
+            args["score"] = score
         # no warm-up run: nothing here initialises lazily on first use except buffers, which the capture allocates from the
         # graph's own pool — and a real step on a dummy batch would move BatchNorm's running statistics
         # captured on ONE stream: a capture with the side-stream forks replays slower (6.4 vs 5.0 ms at B = 256), and the graph

@@ -17,7 +17,7 @@ from typing import List, Optional
 import torch
 
 from . import _hip
-from .engine import CPCEngine, Float32Context, _ceil_div, make_context, side_stream
+from .engine import CPCEngine, Float32Context, _ceil_div, make_context, score_kind, side_stream
 
 
 class Grid:
@@ -1452,9 +1452,12 @@ class ScalogramCPCEngine(CPCEngine):
 
     # ------------------------------------------------------------------ Wasserstein gradient penalty
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
-                       global_negatives=None, after_loss=None, gradient_penalty=None):
+                       global_negatives=None, after_loss=None, gradient_penalty=None, score: Optional[str] = None):
         if gradient_penalty is None:
-            return super().loss_and_grads(x, softplus, regularization, all_timesteps, grad_ready_hook, global_negatives, after_loss)
+            return super().loss_and_grads(x, softplus, regularization, all_timesteps, grad_ready_hook, global_negatives, after_loss,
+                                          score=score)
+        if score_kind(softplus, score) == "difference":
+            raise NotImplementedError("the gradient penalty covers linear_score_function / softplus_score_function; see DESIGN.md section 8")
         return self._gp_step(x, softplus, regularization, all_timesteps, float(gradient_penalty), global_negatives, after_loss)
 
     def _gp_softplus_buffers(self, all_timesteps):

@@ -42,6 +42,8 @@ extern "C" {
                                     * full round of such tiles (layer 2's target rows at the headline size: 196) runs 0.11 instead of 0.135 ms */
 
 /* 9: the tuning-knob entry point (stagger, store policy, timing probes of the NT GEMM) is gone; cpc_gru_set_streaming is on / off only.
+ *    Added later under 9 (backward compatible, no entry point changed): the difference scores cpc_diff_scores, cpc_diff_scores_bwd,
+ *    cpc_diff_scores_rank1.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -603,6 +605,28 @@ int cpc_nce_fused_finalize(const float* colp, int ncolp, const float* valid, int
 long long cpc_nce_eval_workspace_floats(int B, int K);
 int cpc_nce_eval(const float* S, float* out, float* workspace, int B, int K, int ld, int softplus, int all_timesteps, int accumulate,
                  void* stream);
+
+/* Difference scores, difference_score_function (contrastive_estimation_training.py:25-33): s[r][c] = 1 / sum_e (p[r][e] - t[c][e])^2,
+ * f32 accumulation of the squared DIFFERENCES (the reference subtracts first; |p|^2 + |t|^2 - 2 p.t would cancel exactly where the
+ * score is largest).  Inputs P, T: storage type T; outputs f32, rows of lds floats (lds >= N for S, >= M for ST).
+ *   cpc_diff_scores   S[z][m][n] = s(P row m of batch z, T row n of batch z) for m < M, n < N, z < batch, and, when ST != NULL, its
+ *                     transpose ST[z][n][m] from the same pass.  P row m of batch z at z * p_batch + m * ldp; T row n at
+ *                     z * t_batch + row address (n, t_rpi, t_item, ldt) (row addressing above); S / ST matrix z at z * s_batch.
+ *                     Default branch: M = N = B, batch = K (S[k][b][b'] as cpc_nce_loss reads it); score_over_all_timesteps: M = N =
+ *                     B K, batch = 1 (S and ST as cpc_nce_loss_all reads them).  Pad columns are left untouched.
+ *   cpc_diff_scores_bwd   with g = d loss / d s (dS / dST of the loss kernels, T, same layouts), overwrites G[z][m][n] with
+ *                     2 g s^2 = -(d loss / d squared distance), rounded to T, and writes its row sums (of the rounded values) to
+ *                     sums[m * batch + z], f32; when GT != NULL the same for (GT, ST) -> sumsT[n * batch + z] in the same launch.
+ *                     Then d predicted_z[r] = sum_c G[r][c] t[c] - sums[r] p[r] and d targets[c] = sum_r G[r][c] p[r] - sumsT[c] t[c]:
+ *                     the two contractions of the linear score's gradient, followed by cpc_diff_scores_rank1 for the last terms.
+ *   cpc_diff_scores_rank1 out[row][e] -= mu[row] * X[row][e] for row < rows, e < E; out and X rows at the row address
+ *                     (row, rpi, item, ld); f32 arithmetic, one rounding to T. */
+int cpc_diff_scores(const void* P, const void* T, float* S, float* ST, int M, int N, int E, long long ldp, long long ldt, int t_rpi,
+                    long long t_item, long long p_batch, long long t_batch, long long s_batch, int batch, int lds, int dtype, void* stream);
+int cpc_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const float* ST, float* sumsT, int M, int N, int lds,
+                        long long s_batch, int batch, int dtype, void* stream);
+int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
+                          void* stream);
 
 /* torch.optim.Adam.step with default betas/eps semantics over one flat f32 buffer
  * (contrastive_estimation_training.py:83, :162).  step counts from 1; g is multiplied by grad_scale first.

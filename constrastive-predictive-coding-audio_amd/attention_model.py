@@ -65,9 +65,14 @@ def _standalone_input(module, src, mask):
 def _layer_check(layer, S):
     attn = layer.self_attn
     C, heads, FF = attn.embed_dim, attn.num_heads, layer.linear1.out_features
-    if S > 64 or C % heads or C // heads > 64 or C % 8 or FF % 8 or C > 2048:
-        raise NotImplementedError("HIP attention kernels: at most 64 steps, head size <= 64, channel counts multiples of 8 (<= 2048)")
+    if S > 128 or C % heads or C // heads > 64 or C % 8 or FF % 8 or C > 2048:
+        raise NotImplementedError("HIP attention kernels: at most 128 steps, head size <= 64, channel counts multiples of 8 (<= 2048)")
     return C, heads, FF
+
+
+def _attn_abi(S):
+    """The attention core's entry points: the short-sequence kernels up to 64 steps, the cpc_attn128_* ones beyond."""
+    return "cpc_attn" if S <= 64 else "cpc_attn128"
 
 
 def _colsum(X, M, N):
@@ -116,7 +121,7 @@ class _LayerFn(torch.autograd.Function):
         qkv, att, probs, y, r1, x1, f1, r2, out = new(M, 3 * C), new(M, C), new(B * heads, S, S), new(M, C), new(M, C), new(M, C), new(M, FF), new(M, C), new(M, C)
         st1, st2 = new(M, 2), new(M, 2)
         _hip.gemm_nt(P(X), P(w_in), P(qkv), M, 3 * C, C, C, C, 3 * C, F32, bias=P(b_in))
-        _hip.call("cpc_attn_fwd", P(qkv), P(att), P(probs), B, S, C, heads, dp, seed, site0 + 0, F32)
+        _hip.call(_attn_abi(S) + "_fwd", P(qkv), P(att), P(probs), B, S, C, heads, dp, seed, site0 + 0, F32)
         _hip.gemm_nt(P(att), P(w_o), P(y), M, C, C, C, C, C, F32, bias=P(b_o))
         _hip.call("cpc_add_ln_fwd", P(X), P(y), P(n1w), P(n1b), P(r1), P(x1), P(st1), M, C, eps1, dp, seed, site0 + 1, F32)
         _hip.gemm_nt(P(x1), P(w1), P(f1), M, FF, C, C, C, FF, F32, bias=P(b1), flags=_hip.GEMM_RELU)
@@ -160,7 +165,7 @@ class _LayerFn(torch.autograd.Function):
         dwo, dbo = linear_grads(gy1, att, C, C)
         datt, dqkv, gD = new(M, C), new(M, 3 * C), new(M, C)
         _hip.gemm_nt(P(gy1), P(w_o.t().contiguous()), P(datt), M, C, C, C, C, C, F32)
-        _hip.call("cpc_attn_bwd", P(qkv), P(probs), P(datt), P(dqkv), B, S, C, heads, dp, seed, site0 + 0, F32)
+        _hip.call(_attn_abi(S) + "_bwd", P(qkv), P(probs), P(datt), P(dqkv), B, S, C, heads, dp, seed, site0 + 0, F32)
         dwin, dbin = linear_grads(dqkv, X, 3 * C, C)
         _hip.gemm_nt(P(dqkv), P(w_in.t().contiguous()), P(gD), M, C, 3 * C, 3 * C, 3 * C, C, F32)
         return gA + gD, dwin, dbin, dwo, dbo, dw1, db1, dw2, db2, dn1w, dn1b, dn2w, dn2b, None

@@ -1042,3 +1042,498 @@ int launch_attn_gp(const float* qkv, const float* qkvt, const float* P, const fl
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }
+
+// =====================================================================================================================
+// The same attention core for sequences of up to 128 steps (cpc_attn128_*: same layouts, P and dropout indexing as cpc_attn_*).
+// At S = 128 one (item, head) no longer fits the short kernels' LDS images (f32 q/k/v plus an f32 S x S matrix: ~170 KB), so:
+//   matrix pipe (bf16, head size 64): one 512-thread workgroup (8 waves, one 16-row query band each) per (item, head); operand
+//     tiles of 128 rows, P / ds tiles of 128 columns; key tiles wholly above a band's diagonal are neither read nor multiplied;
+//   vector kernels (f32, other head sizes; the penalty passes): the S x S matrices are kept as their lower triangles, packed
+//     row after row (tri(i, j) = i (i + 1) / 2 + j, 8256 floats = 33 KB at S = 128); the operands that no longer fit are read
+//     from global memory.
+namespace {
+
+constexpr int A128_S = 128;                        // max sequence length of the cpc_attn128_* kernels
+constexpr int A128_T = A128_S * (A128_S + 1) / 2;  // entries of a packed lower triangle
+constexpr int A128_LDP = A128_S + 8;               // LDS row stride of the 128-column P / ds tiles (272 B: 16-byte chunks aligned)
+
+__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
+// (i, j) of packed entry idx
+__device__ __forceinline__ void tri_ij(int idx, int& i, int& j) {
+    int r = (int)((sqrtf(8.f * (float)idx + 1.f) - 1.f) * 0.5f);
+    while (r * (r + 1) / 2 > idx) --r;
+    while ((r + 1) * (r + 2) / 2 <= idx) ++r;
+    i = r;
+    j = idx - r * (r + 1) / 2;
+}
+
+__global__ __launch_bounds__(512) void attn128_fwd_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                               bf16_t* __restrict__ P, int S, int C, int heads, float scale, Drop dr) {
+    constexpr int LD = 72, D = 64;
+    __shared__ __attribute__((aligned(16))) bf16_t q[A128_S][LD], k[A128_S][LD], v[A128_S][LD], pt[A128_S][A128_LDP];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int SR = (S + 31) & ~31;               // rows held: the k-steps of the second product read 32 rows; rows >= S are zero
+    for (int idx = tid; idx < SR * 8; idx += 512) {
+        const int t = idx >> 3, ch = (idx & 7) * 8;
+        uint4 zq = make_uint4(0, 0, 0, 0), zk = zq, zv = zq;
+        if (t < S) {
+            const bf16_t* row = qkv + ((long long)b * S + t) * 3 * C + h * D + ch;
+            zq = *(const uint4*)row; zk = *(const uint4*)(row + C); zv = *(const uint4*)(row + 2 * C);
+        }
+        *(uint4*)&q[t][ch] = zq; *(uint4*)&k[t][ch] = zk; *(uint4*)&v[t][ch] = zv;
+    }
+    __syncthreads();
+    if (16 * wave >= S) return;                  // a band wholly past the sequence (no barrier follows)
+    const int g = lane >> 4, il = lane & 15, i = wave * 16 + il;
+    const bool rowok = i < S;
+    // scores of the band against key tiles ct <= wave (the rest lies above the diagonal): acc[ct][r] = s[i][j = 16 ct + 4 g + r]
+    f32x4 sc[8];
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct) {
+        sc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (ct <= wave) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const uint4 fq = *(const uint4*)&q[i][32 * ks + 8 * g];
+                const uint4 fk = *(const uint4*)&k[16 * ct + il][32 * ks + 8 * g];
+                mfma_chunk<bf16_t>(sc[ct], fk, fq);
+            }
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = 16 * ct + 4 * g + r;
+            sc[ct][r] = (ct <= wave && j <= i && j < S) ? sc[ct][r] * scale : -INFINITY;
+            mx = fmaxf(mx, sc[ct][r]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float e = sc[ct][r] == -INFINITY ? 0.f : expf(sc[ct][r] - mx);
+            sc[ct][r] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = 1.f / sum;
+    // P rows in full (zeros above the diagonal); the dropped-out P tile up to the end of the last k-step the band reads
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct) {
+        const int j0 = 16 * ct + 4 * g;
+        bf16x4 pv, pd;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float pr = rowok ? sc[ct][r] * inv : 0.f;
+            pv[r] = (bf16_t)pr;
+            pd[r] = (bf16_t)(ct <= wave ? pr * drop_factor(dr, (unsigned long long)bh * S * S + (unsigned long long)i * S + j0 + r) : 0.f);
+        }
+        if (rowok && j0 < S) {
+            bf16_t* dst = P + (long long)bh * S * S + (long long)i * S + j0;
+            if (S % 4 == 0) *(bf16x4*)dst = pv;
+            else
+                for (int r = 0; r < 4 && j0 + r < S; ++r) dst[r] = pv[r];
+        }
+        if (ct <= wave + 1) *(bf16x4*)&pt[i][j0] = pd;
+    }
+    __builtin_amdgcn_wave_barrier();             // a wave reads back only the 16 rows it wrote itself
+    const int nks = wave / 2 + 1;                // k-steps of 32 keys that reach the band's diagonal
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        for (int ks = 0; ks < nks; ++ks) {
+            const uint2 plo = *(const uint2*)&pt[i][32 * ks + 4 * g], phi = *(const uint2*)&pt[i][32 * ks + 16 + 4 * g];
+            const uint4 fp = make_uint4(plo.x, plo.y, phi.x, phi.y);
+            const uint4 fv = attn_frag_tr((const unsigned char*)&v[0][0], LD * 2, 16 * cb, ks, lane);
+            mfma_chunk<bf16_t>(o, fv, fp);
+        }
+        if (rowok) store4(out + ((long long)b * S + i) * C + h * D + 16 * cb + 4 * g, o);
+    }
+}
+
+// Backward on the matrix pipe: phase 1 as attn_bwd_mfma_kernel per band (dP over the key tiles ct <= wave, softmax backward in
+// registers, ds and P m as full 128-column bf16 rows, zeros above the diagonal); phase 2 dq over the k-steps up to the band's diagonal,
+// dk / dv over the k-steps from it down to the last row.
+__global__ __launch_bounds__(512) void attn128_bwd_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ P,
+                                                               const bf16_t* __restrict__ dout, bf16_t* __restrict__ dqkv, int S, int C,
+                                                               int heads, float scale, Drop dr) {
+    constexpr int LD = 72, D = 64;
+    __shared__ __attribute__((aligned(16))) bf16_t q[A128_S][LD], k[A128_S][LD], v[A128_S][LD], go[A128_S][LD];
+    __shared__ __attribute__((aligned(16))) bf16_t dst[A128_S][A128_LDP], pmt[A128_S][A128_LDP];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int SR = (S + 31) & ~31;
+    for (int idx = tid; idx < SR * 8; idx += 512) {
+        const int t = idx >> 3, ch = (idx & 7) * 8;
+        uint4 zq = make_uint4(0, 0, 0, 0), zk = zq, zv = zq, zg = zq;
+        if (t < S) {
+            const bf16_t* row = qkv + ((long long)b * S + t) * 3 * C + h * D + ch;
+            zq = *(const uint4*)row; zk = *(const uint4*)(row + C); zv = *(const uint4*)(row + 2 * C);
+            zg = *(const uint4*)(dout + ((long long)b * S + t) * C + h * D + ch);
+        }
+        *(uint4*)&q[t][ch] = zq; *(uint4*)&k[t][ch] = zk; *(uint4*)&v[t][ch] = zv; *(uint4*)&go[t][ch] = zg;
+    }
+    __syncthreads();
+    const int g = lane >> 4, il = lane & 15, i = wave * 16 + il;
+    const bool rowok = i < S, live = 16 * wave < S;
+    if (16 * wave < SR) {
+        f32x4 dp[8], pr[8];
+        float dot = 0.f;
+#pragma unroll
+        for (int ct = 0; ct < 8; ++ct) {
+            dp[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (live && ct <= wave) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const uint4 fg_ = *(const uint4*)&go[i][32 * ks + 8 * g];
+                    const uint4 fv = *(const uint4*)&v[16 * ct + il][32 * ks + 8 * g];
+                    mfma_chunk<bf16_t>(dp[ct], fv, fg_);
+                }
+            }
+            const int j0 = 16 * ct + 4 * g;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + r;
+                const bool on = rowok && ct <= wave && j <= i;
+                const float pv = on ? (float)P[(long long)bh * S * S + (long long)i * S + j] : 0.f;
+                const float mf = on ? drop_factor(dr, (unsigned long long)bh * S * S + (unsigned long long)i * S + j) : 0.f;
+                pr[ct][r] = pv;
+                dp[ct][r] = on ? dp[ct][r] * mf : 0.f;
+                dot = fmaf(dp[ct][r], pv, dot);
+            }
+        }
+        dot += __shfl_xor(dot, 16, 64);
+        dot += __shfl_xor(dot, 32, 64);
+#pragma unroll
+        for (int ct = 0; ct < 8; ++ct) {
+            const int j0 = 16 * ct + 4 * g;
+            bf16x4 dsv, pmv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                dsv[r] = (bf16_t)(pr[ct][r] * (dp[ct][r] - dot) * scale);
+                pmv[r] = (bf16_t)(pr[ct][r] == 0.f ? 0.f
+                                  : pr[ct][r] * drop_factor(dr, (unsigned long long)bh * S * S + (unsigned long long)i * S + j0 + r));
+            }
+            *(bf16x4*)&dst[i][j0] = dsv;
+            *(bf16x4*)&pmt[i][j0] = pmv;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const unsigned char* kb = (const unsigned char*)&k[0][0];
+    const unsigned char* qb = (const unsigned char*)&q[0][0];
+    const unsigned char* gb = (const unsigned char*)&go[0][0];
+    const unsigned char* db = (const unsigned char*)&dst[0][0];
+    const unsigned char* pb = (const unsigned char*)&pmt[0][0];
+    const int kq = wave / 2 + 1, k0 = wave / 2, k1 = SR / 32;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        f32x4 aq = {0.f, 0.f, 0.f, 0.f}, ak = aq, av = aq;
+        for (int ks = 0; ks < kq; ++ks) {       // dq: reduction over j <= the band's last row
+            const uint2 dlo = *(const uint2*)&dst[i][32 * ks + 4 * g], dhi = *(const uint2*)&dst[i][32 * ks + 16 + 4 * g];
+            mfma_chunk<bf16_t>(aq, attn_frag_tr(kb, LD * 2, 16 * cb, ks, lane), make_uint4(dlo.x, dlo.y, dhi.x, dhi.y));
+        }
+        for (int ks = k0; ks < k1; ++ks) {      // dk, dv: reduction over i >= the band's first row
+            mfma_chunk<bf16_t>(ak, attn_frag_tr(qb, LD * 2, 16 * cb, ks, lane), attn_frag_tr(db, A128_LDP * 2, 16 * wave, ks, lane));
+            mfma_chunk<bf16_t>(av, attn_frag_tr(gb, LD * 2, 16 * cb, ks, lane), attn_frag_tr(pb, A128_LDP * 2, 16 * wave, ks, lane));
+        }
+        if (rowok) {
+            bf16_t* row = dqkv + ((long long)b * S + i) * 3 * C + h * D + 16 * cb + 4 * g;
+            store4(row, aq);
+            store4(row + C, ak);
+            store4(row + 2 * C, av);
+        }
+    }
+}
+
+// Vector forward: q, k, v tiles in the storage type, the scores as a packed triangle.
+template <typename T>
+__global__ __launch_bounds__(256) void attn128_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out, T* __restrict__ P, int S,
+                                                          int C, int heads, float scale, Drop dr) {
+    __shared__ __attribute__((aligned(16))) T q[A128_S][ATT_LD], k[A128_S][ATT_LD], v[A128_S][ATT_LD];
+    __shared__ float p[A128_T];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, d = C / heads, tid = threadIdx.x;
+    const int d4 = d / 4, nt = S * (S + 1) / 2;
+    const unsigned long long pbase = (unsigned long long)bh * S * S;
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int t = idx / d4, c = (idx % d4) * 4;
+        const T* row = qkv + ((long long)b * S + t) * 3 * C + h * d + c;
+        store4(&q[t][c], load4(row));
+        store4(&k[t][c], load4(row + C));
+        store4(&v[t][c], load4(row + 2 * C));
+    }
+    __syncthreads();
+    for (int idx = tid; idx < nt; idx += 256) {
+        int i, j;
+        tri_ij(idx, i, j);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < d; c += 4) acc += load4(&q[i][c]) * load4(&k[j][c]);
+        p[idx] = (acc[0] + acc[1] + acc[2] + acc[3]) * scale;
+    }
+    __syncthreads();
+    for (int i = tid >> 2, part = tid & 3; i < S; i += 64) {      // four lanes per row
+        float* pr = p + tri(i, 0);
+        float mx = -INFINITY;
+        for (int j = part; j <= i; j += 4) mx = fmaxf(mx, pr[j]);
+        mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+        float sum = 0.f;
+        for (int j = part; j <= i; j += 4) { const float e = expf(pr[j] - mx); pr[j] = e; sum += e; }
+        sum += __shfl_xor(sum, 1, 64);
+        sum += __shfl_xor(sum, 2, 64);
+        const float inv = 1.f / sum;
+        for (int j = part; j <= i; j += 4) pr[j] *= inv;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < S * S; idx += 256) {
+        const int i = idx / S, j = idx % S;
+        P[pbase + idx] = from_f32<T>(j <= i ? p[tri(i, j)] : 0.f);
+    }
+    if (dr.thresh) {        // the saved P stays undropped
+        __syncthreads();
+        for (int idx = tid; idx < nt; idx += 256) {
+            int i, j;
+            tri_ij(idx, i, j);
+            p[idx] *= drop_factor(dr, pbase + (unsigned long long)i * S + j);
+        }
+        __syncthreads();
+    }
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int i = idx / d4, c = (idx % d4) * 4;
+        const float* pr = p + tri(i, 0);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j <= i; ++j) o += pr[j] * load4(&v[j][c]);
+        store4(out + ((long long)b * S + i) * C + h * d + c, o);
+    }
+}
+
+// Vector backward: v and dO tiles and the triangles of P and ds in LDS; q and k read from global memory.
+template <typename T>
+__global__ __launch_bounds__(256) void attn128_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ P, const T* __restrict__ dout,
+                                                          T* __restrict__ dqkv, int S, int C, int heads, float scale, Drop dr) {
+    __shared__ __attribute__((aligned(16))) T v[A128_S][ATT_LD], go[A128_S][ATT_LD];
+    __shared__ float p[A128_T], ds[A128_T];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, d = C / heads, tid = threadIdx.x;
+    const int d4 = d / 4, nt = S * (S + 1) / 2;
+    const unsigned long long pbase = (unsigned long long)bh * S * S;
+    const T* base = qkv + (long long)b * S * 3 * C + h * d;
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int t = idx / d4, c = (idx % d4) * 4;
+        store4(&v[t][c], load4(base + (long long)t * 3 * C + 2 * C + c));
+        store4(&go[t][c], load4(dout + ((long long)b * S + t) * C + h * d + c));
+    }
+    for (int idx = tid; idx < nt; idx += 256) {
+        int i, j;
+        tri_ij(idx, i, j);
+        p[idx] = to_f32(P[pbase + (unsigned long long)i * S + j]);
+    }
+    __syncthreads();
+    for (int idx = tid; idx < nt; idx += 256) {     // dP = m (dO V^T)
+        int i, j;
+        tri_ij(idx, i, j);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < d; c += 4) acc += load4(&go[i][c]) * load4(&v[j][c]);
+        ds[idx] = (acc[0] + acc[1] + acc[2] + acc[3]) * drop_factor(dr, pbase + (unsigned long long)i * S + j);
+    }
+    __syncthreads();
+    for (int i = tid >> 2, part = tid & 3; i < S; i += 64) {
+        const float* pr = p + tri(i, 0);
+        float* dr_ = ds + tri(i, 0);
+        float dot = 0.f;
+        for (int j = part; j <= i; j += 4) dot = fmaf(dr_[j], pr[j], dot);
+        dot += __shfl_xor(dot, 1, 64);
+        dot += __shfl_xor(dot, 2, 64);
+        for (int j = part; j <= i; j += 4) dr_[j] = pr[j] * (dr_[j] - dot) * scale;      // d (raw q.k score)
+    }
+    __syncthreads();
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int t = idx / d4, c = (idx % d4) * 4;
+        f32x4 dq = {0.f, 0.f, 0.f, 0.f}, dk = dq, dv = dq;
+        const float* dsr = ds + tri(t, 0);
+        for (int j = 0; j <= t; ++j) dq += dsr[j] * load4(base + (long long)j * 3 * C + C + c);
+        for (int i = t; i < S; ++i) {
+            const int o = tri(i, t);
+            dk += ds[o] * load4(base + (long long)i * 3 * C + c);
+            dv += (p[o] * drop_factor(dr, pbase + (unsigned long long)i * S + t)) * load4(&go[i][c]);
+        }
+        T* row = dqkv + ((long long)b * S + t) * 3 * C + h * d + c;
+        store4(row, dq);
+        store4(row + C, dk);
+        store4(row + 2 * C, dv);
+    }
+}
+
+// Penalty passes (f32): attn_tangent_kernel / attn_gp_kernel with their S x S matrices as packed triangles.
+__global__ __launch_bounds__(256) void attn128_tangent_kernel(const float* __restrict__ qkv, const float* __restrict__ qkvt,
+                                                              const float* __restrict__ P, float* __restrict__ out_t, int S, int C,
+                                                              int heads, float scale, Drop dr) {
+    __shared__ float u[A128_T], pm[A128_T];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, d = C / heads, tid = threadIdx.x, nt = S * (S + 1) / 2;
+    const unsigned long long pbase = (unsigned long long)bh * S * S;
+    const float* base = qkv + (long long)b * S * 3 * C + h * d;
+    const float* tbase = qkvt + (long long)b * S * 3 * C + h * d;
+    const float* Pb = P + pbase;
+    auto row = [&](const float* p0, int t, int which) { return p0 + (long long)t * 3 * C + which * C; };
+    for (int idx = tid; idx < nt; idx += 256) {
+        int i, j;
+        tri_ij(idx, i, j);
+        u[idx] = scale * (dot_rows(row(tbase, i, 0), row(base, j, 1), d) + dot_rows(row(base, i, 0), row(tbase, j, 1), d));
+    }
+    __syncthreads();
+    for (int i = tid >> 2, part = tid & 3; i < S; i += 64) {
+        float* ur = u + tri(i, 0);
+        float* pmr = pm + tri(i, 0);
+        float mrow = 0.f;
+        for (int j = part; j <= i; j += 4) mrow = fmaf(Pb[i * S + j], ur[j], mrow);
+        mrow += __shfl_xor(mrow, 1, 64);
+        mrow += __shfl_xor(mrow, 2, 64);
+        for (int j = part; j <= i; j += 4) {
+            const float pv = Pb[i * S + j];
+            const float mf = drop_factor(dr, pbase + (unsigned long long)i * S + j);
+            ur[j] = pv * (ur[j] - mrow) * mf;
+            pmr[j] = pv * mf;
+        }
+    }
+    __syncthreads();
+    const int d4 = d / 4;
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int i = idx / d4, c = (idx % d4) * 4;
+        const float* ur = u + tri(i, 0);
+        const float* pmr = pm + tri(i, 0);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j <= i; ++j) o += ur[j] * *(const f32x4*)(row(base, j, 2) + c) + pmr[j] * *(const f32x4*)(row(tbase, j, 2) + c);
+        *(f32x4*)(out_t + ((long long)b * S + i) * C + h * d + c) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void attn128_gp_kernel(const float* __restrict__ qkv, const float* __restrict__ qkvt,
+                                                         const float* __restrict__ P, const float* __restrict__ dout,
+                                                         float* __restrict__ dqkv, int S, int C, int heads, float scale, Drop dr) {
+    __shared__ float u[A128_T], a[A128_T], e[A128_T];
+    const int bh = blockIdx.x, b = bh / heads, h = bh % heads, d = C / heads, tid = threadIdx.x, nt = S * (S + 1) / 2;
+    const unsigned long long pbase = (unsigned long long)bh * S * S;
+    const float* base = qkv + (long long)b * S * 3 * C + h * d;
+    const float* tbase = qkvt + (long long)b * S * 3 * C + h * d;
+    const float* go = dout + (long long)b * S * C + h * d;
+    const float* Pb = P + pbase;
+    auto row = [&](const float* p0, int t, int which) { return p0 + (long long)t * 3 * C + which * C; };
+    for (int idx = tid; idx < nt; idx += 256) {
+        int i, j;
+        tri_ij(idx, i, j);
+        const float mf = drop_factor(dr, pbase + (unsigned long long)i * S + j);
+        u[idx] = scale * (dot_rows(row(tbase, i, 0), row(base, j, 1), d) + dot_rows(row(base, i, 0), row(tbase, j, 1), d));
+        a[idx] = mf * dot_rows(go + (long long)i * C, row(base, j, 2), d);
+        e[idx] = mf * dot_rows(go + (long long)i * C, row(tbase, j, 2), d);
+    }
+    __syncthreads();
+    for (int i = tid >> 2, part = tid & 3; i < S; i += 64) {
+        float* ur = u + tri(i, 0);
+        float* ar = a + tri(i, 0);
+        float* er = e + tri(i, 0);
+        float mrow = 0.f, cc = 0.f;
+        for (int j = part; j <= i; j += 4) { const float pv = Pb[i * S + j]; mrow = fmaf(pv, ur[j], mrow); cc = fmaf(pv, ar[j], cc); }
+        mrow += __shfl_xor(mrow, 1, 64); mrow += __shfl_xor(mrow, 2, 64);
+        cc += __shfl_xor(cc, 1, 64); cc += __shfl_xor(cc, 2, 64);
+        float pw = 0.f;
+        for (int j = part; j <= i; j += 4) {
+            const float wv = er[j] + (ar[j] - cc) * (ur[j] - mrow);
+            er[j] = wv;
+            pw = fmaf(Pb[i * S + j], wv, pw);
+        }
+        pw += __shfl_xor(pw, 1, 64); pw += __shfl_xor(pw, 2, 64);
+        for (int j = part; j <= i; j += 4) {
+            const float pv = Pb[i * S + j];
+            const float mf = drop_factor(dr, pbase + (unsigned long long)i * S + j);
+            ur[j] = pv * (ur[j] - mrow) * mf;       // pt m
+            ar[j] = pv * (ar[j] - cc);              // dS
+            er[j] = pv * (er[j] - pw);              // sig
+        }
+    }
+    __syncthreads();
+    const int d4 = d / 4;
+    for (int idx = tid; idx < S * d4; idx += 256) {
+        const int t = idx / d4, c = (idx % d4) * 4;
+        f32x4 sq = {0.f, 0.f, 0.f, 0.f}, sk = sq, sv = sq;
+        const int rt = tri(t, 0);
+        for (int j = 0; j <= t; ++j)
+            sq += e[rt + j] * *(const f32x4*)(row(base, j, 1) + c) + a[rt + j] * *(const f32x4*)(row(tbase, j, 1) + c);
+        for (int i = t; i < S; ++i) {
+            const int o = tri(i, t);
+            sk += e[o] * *(const f32x4*)(row(base, i, 0) + c) + a[o] * *(const f32x4*)(row(tbase, i, 0) + c);
+            sv += u[o] * *(const f32x4*)(go + (long long)i * C + c);
+        }
+        float* o = dqkv + ((long long)b * S + t) * 3 * C + h * d + c;
+        *(f32x4*)o += sq * scale;
+        *(f32x4*)(o + C) += sk * scale;
+        *(f32x4*)(o + 2 * C) += sv;
+    }
+}
+
+}  // namespace
+
+static bool attn128_ok(int B, int S, int C, int heads) {
+    return B > 0 && S > 0 && S <= A128_S && heads > 0 && C % heads == 0 && C / heads <= ATT_D && (C / heads) % 4 == 0;
+}
+
+int launch_attn128_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int heads, float drop_p, unsigned long long seed,
+                       unsigned site, int dtype, hipStream_t st) {
+    if (!attn128_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
+    const Drop dr = make_drop(drop_p, seed, site);
+    const float scale = 1.f / sqrtf((float)(C / heads));
+    if (dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)out % 8 == 0) &&
+        ((uintptr_t)P % 8 == 0)) {
+        hipLaunchKernelGGL(attn128_fwd_mfma_kernel, dim3(B * heads), dim3(512), 0, st, (const bf16_t*)qkv, (bf16_t*)out, (bf16_t*)P, S, C,
+                           heads, scale, dr);
+        CPC_CHECK_LAUNCH();
+        return CPC_OK;
+    }
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((attn128_fwd_kernel<bf16_t>), dim3(B * heads), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)out, (bf16_t*)P, S, C, heads, scale, dr),
+               hipLaunchKernelGGL((attn128_fwd_kernel<float>), dim3(B * heads), dim3(256), 0, st, (const float*)qkv, (float*)out, (float*)P, S, C, heads, scale, dr));
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_attn128_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
+                       unsigned long long seed, unsigned site, int dtype, hipStream_t st) {
+    if (!attn128_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
+    const Drop dr = make_drop(drop_p, seed, site);
+    const float scale = 1.f / sqrtf((float)(C / heads));
+    if (dtype == CPC_DTYPE_BF16 && C / heads == 64 && C % 8 == 0 && ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) &&
+        ((uintptr_t)dqkv % 8 == 0)) {
+        hipLaunchKernelGGL(attn128_bwd_mfma_kernel, dim3(B * heads), dim3(512), 0, st, (const bf16_t*)qkv, (const bf16_t*)P,
+                           (const bf16_t*)dout, (bf16_t*)dqkv, S, C, heads, scale, dr);
+        CPC_CHECK_LAUNCH();
+        return CPC_OK;
+    }
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((attn128_bwd_kernel<bf16_t>), dim3(B * heads), dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)P, (const bf16_t*)dout, (bf16_t*)dqkv, S, C, heads, scale, dr),
+               hipLaunchKernelGGL((attn128_bwd_kernel<float>), dim3(B * heads), dim3(256), 0, st, (const float*)qkv, (const float*)P, (const float*)dout, (float*)dqkv, S, C, heads, scale, dr));
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_attn128_tangent(const float* qkv, const float* qkvt, const float* P, float* out_t, int B, int S, int C, int heads,
+                           float drop_p, unsigned long long seed, unsigned site, hipStream_t st) {
+    if (!attn128_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
+    const Drop dr = make_drop(drop_p, seed, site);
+    hipLaunchKernelGGL(attn128_tangent_kernel, dim3(B * heads), dim3(256), 0, st, qkv, qkvt, P, out_t, S, C, heads,
+                       1.f / sqrtf((float)(C / heads)), dr);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_attn128_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
+                      float drop_p, unsigned long long seed, unsigned site, hipStream_t st) {
+    if (!attn128_ok(B, S, C, heads) || drop_p < 0.f || drop_p >= 1.f) return CPC_EINVAL;
+    const Drop dr = make_drop(drop_p, seed, site);
+    hipLaunchKernelGGL(attn128_gp_kernel, dim3(B * heads), dim3(256), 0, st, qkv, qkvt, P, dout, dqkv, S, C, heads,
+                       1.f / sqrtf((float)(C / heads)), dr);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}

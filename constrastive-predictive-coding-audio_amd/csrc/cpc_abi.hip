@@ -359,6 +359,30 @@ int cpc_attn_gp(const float* qkv, const float* qkvt, const float* P, const float
     return launch_attn_gp(qkv, qkvt, P, dout, dqkv, B, S, C, heads, drop_p, seed, site, (hipStream_t)stream);
 }
 
+int cpc_attn128_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int heads, float drop_p, unsigned long long seed,
+                    unsigned site, int dtype, void* stream) {
+    if (!qkv || !out || !P) return CPC_EINVAL;
+    return launch_attn128_fwd(qkv, out, P, B, S, C, heads, drop_p, seed, site, dtype, (hipStream_t)stream);
+}
+
+int cpc_attn128_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
+                    unsigned long long seed, unsigned site, int dtype, void* stream) {
+    if (!qkv || !P || !dout || !dqkv) return CPC_EINVAL;
+    return launch_attn128_bwd(qkv, P, dout, dqkv, B, S, C, heads, drop_p, seed, site, dtype, (hipStream_t)stream);
+}
+
+int cpc_attn128_tangent(const float* qkv, const float* qkvt, const float* P, float* out_t, int B, int S, int C, int heads, float drop_p,
+                        unsigned long long seed, unsigned site, void* stream) {
+    if (!qkv || !qkvt || !P || !out_t) return CPC_EINVAL;
+    return launch_attn128_tangent(qkv, qkvt, P, out_t, B, S, C, heads, drop_p, seed, site, (hipStream_t)stream);
+}
+
+int cpc_attn128_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
+                   float drop_p, unsigned long long seed, unsigned site, void* stream) {
+    if (!qkv || !qkvt || !P || !dout || !dqkv) return CPC_EINVAL;
+    return launch_attn128_gp(qkv, qkvt, P, dout, dqkv, B, S, C, heads, drop_p, seed, site, (hipStream_t)stream);
+}
+
 int cpc_dropout(void* x, long long n, float drop_p, unsigned long long seed, unsigned site, int dtype, void* stream) {
     if (!x) return CPC_EINVAL;
     return launch_dropout(x, n, drop_p, seed, site, dtype, (hipStream_t)stream);

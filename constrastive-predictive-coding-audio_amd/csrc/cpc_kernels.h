@@ -204,6 +204,14 @@ int launch_attn_tangent(const float* qkv, const float* qkvt, const float* P, flo
                         float drop_p, unsigned long long seed, unsigned site, hipStream_t st);
 int launch_attn_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
                    float drop_p, unsigned long long seed, unsigned site, hipStream_t st);
+int launch_attn128_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int heads, float drop_p, unsigned long long seed,
+                       unsigned site, int dtype, hipStream_t stream);
+int launch_attn128_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
+                       unsigned long long seed, unsigned site, int dtype, hipStream_t stream);
+int launch_attn128_tangent(const float* qkv, const float* qkvt, const float* P, float* out_t, int B, int S, int C, int heads,
+                           float drop_p, unsigned long long seed, unsigned site, hipStream_t st);
+int launch_attn128_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
+                      float drop_p, unsigned long long seed, unsigned site, hipStream_t st);
 int launch_dropout(void* x, long long n, float drop_p, unsigned long long seed, unsigned site, int dtype, hipStream_t stream);
 int launch_dropout_mask(float* mask, long long n, float drop_p, unsigned long long seed, unsigned site, hipStream_t stream);
 int launch_mean_time(const void* x, void* out, int B, int S, int C, int dtype, hipStream_t stream);

@@ -1386,8 +1386,10 @@ class AttentionContext:
             raise ValueError("AttentionModel channels / output_size do not match enc_size / ar_size")
         if self.S > ar.sequence_length:
             raise ValueError("visible_steps exceeds the AttentionModel's sequence_length (positional table)")
-        if self.S > 64 or self.C % self.heads or self.C // self.heads > 64:
-            raise NotImplementedError("HIP attention kernel: visible_steps <= 64 and head size <= 64")
+        if self.S > 128 or self.C % self.heads or self.C // self.heads > 64:
+            raise NotImplementedError("HIP attention kernels: visible_steps <= 128 and head size <= 64")
+        # the attention core: the short-sequence kernels up to 64 steps, the cpc_attn128_* ones beyond
+        self.attn_abi = "cpc_attn" if self.S <= 64 else "cpc_attn128"
         ch = 8 if eng.dt == torch.bfloat16 else 4
         if self.C % 8 or self.FF % 8 or self.out % ch or self.C > 2048:
             raise NotImplementedError("AttentionModel sizes must be multiples of 8 (channels <= 2048)")
@@ -1515,7 +1517,7 @@ class AttentionContext:
             X, w = self.X[l], self.w[l]
             bias = {k: P(p[self._lname(l, n)]) for k, n in self._BNAMES.items()}
             _hip.gemm_nt(P(X), P(w["in"]), P(self.qkv[l]), M, 3 * C, C, C, C, 3 * C, code, bias=bias["in"])
-            _hip.call("cpc_attn_fwd", P(self.qkv[l]), P(self.att[l]), P(self.P[l]), B, S, C, self.heads, dp, seed, 4 * l + self.SITE_ATTN,
+            _hip.call(self.attn_abi + "_fwd", P(self.qkv[l]), P(self.att[l]), P(self.P[l]), B, S, C, self.heads, dp, seed, 4 * l + self.SITE_ATTN,
                       code)
             _hip.gemm_nt(P(self.att[l]), P(w["o"]), P(self.ytmp), M, C, C, C, C, C, code, bias=bias["o"])
             self._ln(X, self.ytmp, self._lname(l, "norm1"), self.r1[l], self.x1[l], self.st1[l], site=4 * l + self.SITE_DROP1)
@@ -1589,7 +1591,7 @@ class AttentionContext:
         for l in range(self.N):
             Xt, w = gp.Xt[l], self.w[l]
             _hip.gemm_nt(P(Xt), P(w["in"]), P(gp.qkvt[l]), M, 3 * C, C, C, C, 3 * C, code)
-            _hip.call("cpc_attn_tangent", P(self.qkv[l]), P(gp.qkvt[l]), P(self.P[l]), P(gp.attt[l]), B, S, C, self.heads, dp, seed,
+            _hip.call(self.attn_abi + "_tangent", P(self.qkv[l]), P(gp.qkvt[l]), P(self.P[l]), P(gp.attt[l]), B, S, C, self.heads, dp, seed,
                       4 * l + self.SITE_ATTN)
             _hip.gemm_nt(P(gp.attt[l]), P(w["o"]), P(gp.ytmp), M, C, C, C, C, C, code)
             ln_t(Xt, gp.ytmp, self.r1[l], self.st1[l], self._lname(l, "norm1"), gp.r1t[l], gp.x1t[l], 4 * l + self.SITE_DROP1)
@@ -1665,10 +1667,10 @@ class AttentionContext:
             _hip.gemm_nt(P(lam_y), P(wt["o"]), P(self.datt), M, C, C, C, C, C, code)
             _hip.gemm_nt(P(dl_y), P(wt["o"]), P(gp.datt), M, C, C, C, C, C, code)
             site = 4 * l + self.SITE_ATTN
-            _hip.call("cpc_attn_bwd", P(self.qkv[l]), P(self.P[l]), P(self.datt), P(self.dqkv[0]), B, S, C, self.heads, dp, seed, site, code)
-            _hip.call("cpc_attn_gp", P(self.qkv[l]), P(gp.qkvt[l]), P(self.P[l]), P(gp.datt), P(self.dqkv[0]), B, S, C, self.heads, dp,
+            _hip.call(self.attn_abi + "_bwd", P(self.qkv[l]), P(self.P[l]), P(self.datt), P(self.dqkv[0]), B, S, C, self.heads, dp, seed, site, code)
+            _hip.call(self.attn_abi + "_gp", P(self.qkv[l]), P(gp.qkvt[l]), P(self.P[l]), P(gp.datt), P(self.dqkv[0]), B, S, C, self.heads, dp,
                       seed, site)
-            _hip.call("cpc_attn_bwd", P(self.qkv[l]), P(self.P[l]), P(gp.datt), P(gp.dqkv), B, S, C, self.heads, dp, seed, site, code)
+            _hip.call(self.attn_abi + "_bwd", P(self.qkv[l]), P(self.P[l]), P(gp.datt), P(gp.dqkv), B, S, C, self.heads, dp, seed, site, code)
             linear_grads(self.dqkv[0], gp.dqkv, self.X[l], gp.Xt[l], "in", l, 3 * C, C)
             _hip.gemm_nt(P(self.dqkv[0]), P(wt["in"]), P(self.gD), M, C, 3 * C, 3 * C, 3 * C, C, code)
             _hip.gemm_nt(P(gp.dqkv), P(wt["in"]), P(gp.gD), M, C, 3 * C, 3 * C, 3 * C, C, code)
@@ -1732,7 +1734,7 @@ class AttentionContext:
                 e._colsum_to_grad(P(gAd), gname("o", self._BNAMES), M, C, scratch=sc)
                 e._tn_to_grad(P(gAd), P(self.att[l]), gname("o", self._WNAMES), M, C, C, C, C, self.split["o"], scratch=sc)
             _hip.gemm_nt(P(gAd), P(wt["o"]), P(self.datt), M, C, C, C, C, C, code)
-            _hip.call("cpc_attn_bwd", P(self.qkv[l]), P(self.P[l]), P(self.datt), P(dqkv), B, S, C, self.heads, self.drop_p,
+            _hip.call(self.attn_abi + "_bwd", P(self.qkv[l]), P(self.P[l]), P(self.datt), P(dqkv), B, S, C, self.heads, self.drop_p,
                       self.drop_seed, 4 * l + self.SITE_ATTN, code)
             with e.side(ev[3]):
                 e._colsum_to_grad(P(dqkv), gname("in", self._BNAMES), M, 3 * C, scratch=sc)

@@ -44,6 +44,8 @@ extern "C" {
 /* 9: the tuning-knob entry point (stagger, store policy, timing probes of the NT GEMM) is gone; cpc_gru_set_streaming is on / off only.
  *    Added later under 9 (backward compatible, no entry point changed): the difference scores cpc_diff_scores, cpc_diff_scores_bwd,
  *    cpc_diff_scores_rank1.
+ *    Added later under 9 (backward compatible, no entry point changed): the attention core for up to 128 steps cpc_attn128_fwd,
+ *    cpc_attn128_bwd, cpc_attn128_tangent, cpc_attn128_gp.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -272,6 +274,15 @@ int cpc_attn_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int h
                  unsigned site, int dtype, void* stream);
 int cpc_attn_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
                  unsigned long long seed, unsigned site, int dtype, void* stream);
+/* The same core for longer sequences (AudioPredictiveCodingModel's default visible_steps = 100; the reference's PositionalEncoder
+ * max_seq_len = 128, attention_model.py:9-27): same layouts, P and dropout element index as cpc_attn_fwd / cpc_attn_bwd.
+ * Limits: 1 <= S <= 128, C/heads <= 64 (-EINVAL otherwise).  bf16 with C/heads == 64 on the matrix pipe (one 8-wave workgroup per
+ * (item, head), a 16-row query band per wave; key tiles above a band's diagonal are skipped); f32 and other head sizes on vector
+ * kernels that keep the S x S matrices as packed lower triangles in LDS. */
+int cpc_attn128_fwd(const void* qkv, void* out, void* P, int B, int S, int C, int heads, float drop_p, unsigned long long seed,
+                    unsigned site, int dtype, void* stream);
+int cpc_attn128_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
+                    unsigned long long seed, unsigned site, int dtype, void* stream);
 /* r = a + dropout(b) (b may be NULL; r_out may be NULL), y = LayerNorm(r) * w + bias (transformer.py:262-271, eps inside
  * the sqrt); stats f32 [M][2] = (mean, rstd) saved for the backward; dropout element index = m*C + c. */
 int cpc_add_ln_fwd(const void* a, const void* b, const float* w, const float* bias, void* r_out, void* y, float* stats, int M,
@@ -304,6 +315,11 @@ int cpc_attn_tangent(const float* qkv, const float* qkvt, const float* P, float*
                      unsigned long long seed, unsigned site, void* stream);
 int cpc_attn_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
                 float drop_p, unsigned long long seed, unsigned site, void* stream);
+/* cpc_attn128_tangent / cpc_attn128_gp: cpc_attn_tangent / cpc_attn_gp for 1 <= S <= 128 (limits as cpc_attn128_fwd). */
+int cpc_attn128_tangent(const float* qkv, const float* qkvt, const float* P, float* out_t, int B, int S, int C, int heads, float drop_p,
+                        unsigned long long seed, unsigned site, void* stream);
+int cpc_attn128_gp(const float* qkv, const float* qkvt, const float* P, const float* dout, float* dqkv, int B, int S, int C, int heads,
+                   float drop_p, unsigned long long seed, unsigned site, void* stream);
 /* out[b][c] = mean_t x[(b,t)][c]  (attention_model.py:79) */
 int cpc_mean_time(const void* x, void* out, int B, int S, int C, int dtype, void* stream);
 

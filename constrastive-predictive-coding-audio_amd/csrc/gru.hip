@@ -12,19 +12,21 @@
 
 namespace {
 
-constexpr int GRU_MAXJT = 4;      // hidden tiles (16 units) per wave -> H <= 256
+constexpr int GRU_MAXJT = 4;      // hidden tiles (16 units) per wave -> H <= 256 with 4 waves, H <= 512 with 8
+constexpr int GRU_WIDE_H = 512;   // largest H of the 8-wave streaming kernels (their static LDS is sized for it)
 
 template <typename T>
 __device__ __forceinline__ uint4 ldg16(const T* p) { return *(const uint4*)p; }
 
-// grid: ceil(B/16); block 256.
-template <typename T>
-__global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, const T* __restrict__ Wfrag,
-                                                      const float* __restrict__ bhh, T* __restrict__ Hall,
-                                                      T* __restrict__ tape, float* __restrict__ c_out, int B, int V,
-                                                      int H, const float* __restrict__ h0) {
-    constexpr int CH = Elem<T>::CH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// The weight-streaming recurrences with NW waves per workgroup: wave w owns the hidden tiles w + NW*q, q < GRU_MAXJT.
+// NW = 4 (gru_fwd_kernel / gru_bwd_kernel: H <= 256, LDS sized by H at launch); NW = 8 (gru_fwd_wide_kernel /
+// gru_bwd_wide_kernel: 256 < H <= 512, static LDS sized for H = 512: the f32 backward's [16][3H] tile alone is 98 KB).
+// grid: ceil(B/16); block 64 * NW.
+template <typename T, int NW>
+__device__ __forceinline__ void gru_fwd_steps(unsigned char* smem, const T* __restrict__ Gi, const T* __restrict__ Wfrag,
+                                              const float* __restrict__ bhh, T* __restrict__ Hall, T* __restrict__ tape,
+                                              float* __restrict__ c_out, int B, int V, int H, const float* __restrict__ h0) {
+    constexpr int CH = Elem<T>::CH, NTHR = 64 * NW;
     const int rowb = H * (int)sizeof(T) + 16;             // h tile row stride in bytes (16 B pad)
     unsigned char* hbuf[2] = {smem, smem + 16 * rowb};
     float* bsh = (float*)(smem + 2 * 16 * rowb);           // b_hh [3H]
@@ -37,12 +39,12 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
     const int ntile = H / 16;
     const int KC = H / (4 * CH);
 
-    for (int i = tid; i < 3 * H; i += 256) bsh[i] = bhh ? bhh[i] : 0.f;
-    for (int i = tid; i < 16 * rowb / 4; i += 256) ((unsigned int*)hbuf[0])[i] = 0u;    // h_0 = 0
+    for (int i = tid; i < 3 * H; i += NTHR) bsh[i] = bhh ? bhh[i] : 0.f;
+    for (int i = tid; i < 16 * rowb / 4; i += NTHR) ((unsigned int*)hbuf[0])[i] = 0u;    // h_0 = 0
     __syncthreads();          // (the loop below rewrites the tile with a carried state, by other threads)
     // Hall[:, 0, :] = 0
     // (h0: the state a reset_hidden=False model carries over from its previous call, audio_model.py:69, :75; NULL = zeros)
-    for (int i = tid; i < 16 * H; i += 256) {
+    for (int i = tid; i < 16 * H; i += NTHR) {
         const int rb = i / H, j = i % H;
         const float v = (h0 && b0 + rb < B) ? h0[(long long)(b0 + rb) * H + j] : 0.f;
         ((T*)(hbuf[0] + rb * rowb))[j] = from_f32<T>(v);
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
     for (int q = 0; q < GRU_MAXJT; ++q)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int jt = wave + 4 * q;
+            const int jt = wave + NW * q;
             hprev[q][e] = (h0 && b_ok && jt < ntile) ? h0[(long long)b * H + jt * 16 + fg * 4 + e] : 0.f;
         }
 
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
         f32x4 gi[GRU_MAXJT][3];
 #pragma unroll
         for (int q = 0; q < GRU_MAXJT; ++q) {
-            const int jt = wave + 4 * q;
+            const int jt = wave + NW * q;
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
                 gi[q][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
         f32x4 acc[GRU_MAXJT][3];
 #pragma unroll
         for (int q = 0; q < GRU_MAXJT; ++q) {
-            const int jt = wave + 4 * q;
+            const int jt = wave + NW * q;
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
                 acc[q][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
             const uint4 hf = *(const uint4*)(hcur + frow * rowb + (kc * 4 + fg) * 16);
 #pragma unroll
             for (int q = 0; q < GRU_MAXJT; ++q) {
-                const int jt = wave + 4 * q;
+                const int jt = wave + NW * q;
                 if (jt < ntile) {
 #pragma unroll
                     for (int g = 0; g < 3; ++g) {
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
         // gate math for (b, j = jt*16 + fg*4 + e)
 #pragma unroll
         for (int q = 0; q < GRU_MAXJT; ++q) {
-            const int jt = wave + 4 * q;
+            const int jt = wave + NW * q;
             if (jt < ntile) {
                 const int j = jt * 16 + fg * 4;
                 f32x4 r4, u4, n4, q4, h4, hp4;
@@ -135,12 +137,29 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, 
     }
 }
 
-// grid: ceil(B/16); block 256.  WTfrag: fragment-ordered W_hh^T ([H][3H] logical: rows = hidden unit, k = gate column).
 template <typename T>
-__global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
-                                                      const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
-    constexpr int CH = Elem<T>::CH;
+__global__ __launch_bounds__(256) void gru_fwd_kernel(const T* __restrict__ Gi, const T* __restrict__ Wfrag,
+                                                      const float* __restrict__ bhh, T* __restrict__ Hall,
+                                                      T* __restrict__ tape, float* __restrict__ c_out, int B, int V,
+                                                      int H, const float* __restrict__ h0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    gru_fwd_steps<T, 4>(smem, Gi, Wfrag, bhh, Hall, tape, c_out, B, V, H, h0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void gru_fwd_wide_kernel(const T* __restrict__ Gi, const T* __restrict__ Wfrag,
+                                                           const float* __restrict__ bhh, T* __restrict__ Hall,
+                                                           T* __restrict__ tape, float* __restrict__ c_out, int B, int V,
+                                                           int H, const float* __restrict__ h0) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16 * (GRU_WIDE_H * sizeof(T) + 16) + 3 * GRU_WIDE_H * sizeof(float)];
+    gru_fwd_steps<T, 8>(smem, Gi, Wfrag, bhh, Hall, tape, c_out, B, V, H, h0);
+}
+
+// WTfrag: fragment-ordered W_hh^T ([H][3H] logical: rows = hidden unit, k = gate column).
+template <typename T, int NW>
+__device__ __forceinline__ void gru_bwd_steps(unsigned char* smem, const float* __restrict__ dc, const T* __restrict__ tape,
+                                              const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+    constexpr int CH = Elem<T>::CH;
     const int rowb = 3 * H * (int)sizeof(T) + 16;
     unsigned char* gcur = smem;                            // dgh tile [16][3H] (+16 B pad per row)
 
@@ -155,7 +174,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
     float dh[GRU_MAXJT][4];
 #pragma unroll
     for (int q = 0; q < GRU_MAXJT; ++q) {
-        const int jt = wave + 4 * q;
+        const int jt = wave + NW * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[q][e] = 0.f;
         if (jt < ntile && b_ok) {
@@ -169,7 +188,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
         float keep[GRU_MAXJT][4];
 #pragma unroll
         for (int q = 0; q < GRU_MAXJT; ++q) {
-            const int jt = wave + 4 * q;
+            const int jt = wave + NW * q;
             if (jt < ntile) {
                 const int j = jt * 16 + fg * 4;
                 f32x4 hp = (f32x4){0.f, 0.f, 0.f, 0.f}, r4 = hp, u4 = hp, n4 = hp, q4 = hp;
@@ -210,7 +229,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
             const uint4 gf = *(const uint4*)(gcur + frow * rowb + (kc * 4 + fg) * 16);
 #pragma unroll
             for (int q = 0; q < GRU_MAXJT; ++q) {
-                const int jt = wave + 4 * q;
+                const int jt = wave + NW * q;
                 if (jt < ntile) {
                     const uint4 wf = ldg16(WTfrag + ((long long)(jt * KC + kc) * 64 + lane) * CH);
                     mfma_chunk<T>(acc[q], wf, gf);
@@ -223,6 +242,20 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ 
             for (int e = 0; e < 4; ++e) dh[q][e] = keep[q][e] + acc[q][e];
         __syncthreads();      // all reads of the dgh tile are done before the next step overwrites it
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
+                                                      const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    gru_bwd_steps<T, 4>(smem, dc, tape, WTfrag, dG, B, V, H);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void gru_bwd_wide_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
+                                                           const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[16 * (3 * GRU_WIDE_H * sizeof(T) + 16)];
+    gru_bwd_steps<T, 8>(smem, dc, tape, WTfrag, dG, B, V, H);
 }
 
 // ----------------------------------------------------------------------------------------------- weight-resident bf16
@@ -623,7 +656,7 @@ int g_gru_force_streaming = 0;
 static bool gru_ok(int B, int V, int H, int dtype) {
     const int ch = dtype == CPC_DTYPE_BF16 ? 8 : 4;
     if (B <= 0 || V <= 0 || H <= 0) return false;
-    if (H % 16 || H % (4 * ch) || H / 16 > 4 * GRU_MAXJT) return false;
+    if (H % 16 || H % (4 * ch) || H > GRU_WIDE_H) return false;
     return dtype == CPC_DTYPE_BF16 || dtype == CPC_DTYPE_F32;
 }
 
@@ -639,6 +672,16 @@ int launch_gru_fwd(const void* Gi, const void* Wfrag, const float* bhh, void* Ha
     const int esz = dtype == CPC_DTYPE_BF16 ? 2 : 4;
     const size_t shm = 2 * 16 * (size_t)(H * esz + 16) + 3 * H * sizeof(float);
     dim3 grid((B + 15) / 16);
+    if (H > 256) {          // 8 waves (tiles w + 8q), static LDS
+        if (dtype == CPC_DTYPE_BF16)
+            hipLaunchKernelGGL((gru_fwd_wide_kernel<bf16_t>), grid, dim3(512), 0, stream, (const bf16_t*)Gi, (const bf16_t*)Wfrag, bhh,
+                               (bf16_t*)Hall, (bf16_t*)tape, c_out, B, V, H, h0);
+        else
+            hipLaunchKernelGGL((gru_fwd_wide_kernel<float>), grid, dim3(512), 0, stream, (const float*)Gi, (const float*)Wfrag, bhh,
+                               (float*)Hall, (float*)tape, c_out, B, V, H, h0);
+        CPC_CHECK_LAUNCH();
+        return CPC_OK;
+    }
     if (dtype == CPC_DTYPE_BF16 && !g_gru_force_streaming && (H == 32 || H == 64 || H == 128 || H == 256)) {
 #define GRU_F(KC) \
     hipLaunchKernelGGL((gru_fwd_res_kernel<KC>), grid, dim3(64 * GRU_NW), 0, stream, (const bf16_t*)Gi, (const bf16_t*)Wfrag, bhh, \
@@ -661,6 +704,16 @@ int launch_gru_fwd(const void* Gi, const void* Wfrag, const float* bhh, void* Ha
 int launch_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
                    hipStream_t stream) {
     if (!gru_ok(B, V, H, dtype)) return CPC_EINVAL;
+    if (H > 256) {          // 8 waves (tiles w + 8q), static LDS
+        if (dtype == CPC_DTYPE_BF16)
+            hipLaunchKernelGGL((gru_bwd_wide_kernel<bf16_t>), dim3((B + 15) / 16), dim3(512), 0, stream, dc, (const bf16_t*)tape,
+                               (const bf16_t*)WTfrag, (bf16_t*)dG, B, V, H);
+        else
+            hipLaunchKernelGGL((gru_bwd_wide_kernel<float>), dim3((B + 15) / 16), dim3(512), 0, stream, dc, (const float*)tape,
+                               (const float*)WTfrag, (float*)dG, B, V, H);
+        CPC_CHECK_LAUNCH();
+        return CPC_OK;
+    }
     const int esz = dtype == CPC_DTYPE_BF16 ? 2 : 4;
     const size_t shm = 16 * (size_t)(3 * H * esz + 16);
     if (shm > 64 * 1024) return CPC_EINVAL;
@@ -708,13 +761,13 @@ int launch_prep_frag(const float* src, void* dst, int R, int Kd, long long ld, i
 // unit down the sequence: G, the adjoint of the summed scores (equal to the adjoint of the tangent variables, the tangent
 // program being linear with the primal Jacobians), and N, the adjoint the primal variables gain through the coefficients of the
 // tangent program (the second derivatives of sigmoid / tanh and the products r*q, z*h, (1-z)*n).  f32 only (the penalty runs in
-// the exact-f32 mode); one workgroup per batch item, one thread per hidden unit, weights streamed from L2 every step: a
+// the exact-f32 mode); one workgroup per batch item, one thread per hidden unit (H <= 512), weights streamed from L2 every step: a
 // parity path of ~B workgroups, not a tuned one (a penalty step costs about three plain steps anyway).
 // tape f32 [B][V][10][H]: r, z, n, q = W_hn h + b_hn, h_{t-1}, tangents of the pre-activations of r and z, of q, of the
 // pre-activation of n, and of h_{t-1}.
 #define GRU_GP_SLOTS 10
 
-__global__ __launch_bounds__(256) void gru_gp_fwd_kernel(const float* __restrict__ Gi, const float* __restrict__ GiT,
+__global__ __launch_bounds__(512) void gru_gp_fwd_kernel(const float* __restrict__ Gi, const float* __restrict__ GiT,
                                                          const float* __restrict__ WT, const float* __restrict__ bhh,
                                                          float* __restrict__ tape, float* __restrict__ ct_out, int V, int H) {
     extern __shared__ float gp_lds[];
@@ -761,7 +814,7 @@ __global__ __launch_bounds__(256) void gru_gp_fwd_kernel(const float* __restrict
 
 // dA f32 [B][V][8][H] = [d r_pre | d z_pre | d n_pre | d q] of the summed scores (the adjoints of the tangent pre-activations),
 // then the same four for the second-order adjoint N.  W: weight_hh in the reference's layout [3H][H].
-__global__ __launch_bounds__(256) void gru_gp_bwd_kernel(const float* __restrict__ dc, const float* __restrict__ tape,
+__global__ __launch_bounds__(512) void gru_gp_bwd_kernel(const float* __restrict__ dc, const float* __restrict__ tape,
                                                          const float* __restrict__ W, float* __restrict__ dA, int V, int H) {
     extern __shared__ float gp_lds[];
     float* dv = gp_lds;              // [3][H]: d r_pre, d z_pre, d q
@@ -813,7 +866,7 @@ __global__ __launch_bounds__(256) void gru_gp_bwd_kernel(const float* __restrict
 
 int launch_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const float* bhh, float* tape, float* ct_out, int B,
                       int V, int H, hipStream_t stream) {
-    if (B <= 0 || V <= 0 || H <= 0 || H > 256) return CPC_EINVAL;
+    if (B <= 0 || V <= 0 || H <= 0 || H > GRU_WIDE_H) return CPC_EINVAL;
     hipLaunchKernelGGL(gru_gp_fwd_kernel, dim3(B), dim3((H + 63) / 64 * 64), 2 * H * sizeof(float), stream, Gi, GiT, WT, bhh, tape,
                        ct_out, V, H);
     CPC_CHECK_LAUNCH();
@@ -821,7 +874,7 @@ int launch_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const 
 }
 
 int launch_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA, int B, int V, int H, hipStream_t stream) {
-    if (B <= 0 || V <= 0 || H <= 0 || H > 256) return CPC_EINVAL;
+    if (B <= 0 || V <= 0 || H <= 0 || H > GRU_WIDE_H) return CPC_EINVAL;
     hipLaunchKernelGGL(gru_gp_bwd_kernel, dim3(B), dim3((H + 63) / 64 * 64), 6 * H * sizeof(float), stream, dc, tape, W, dA, V, H);
     CPC_CHECK_LAUNCH();
     return CPC_OK;

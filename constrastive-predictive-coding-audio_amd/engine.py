@@ -1040,8 +1040,9 @@ class GRUContext:
         ch = 8 if eng.dt == torch.bfloat16 else 4
         if ar.input_size != eng.E or self.H != eng.H:
             raise ValueError("AudioGRUModel sizes do not match enc_size / ar_size")
-        if self.H % 16 or self.H % (4 * ch) or self.H > 256:
-            raise NotImplementedError("HIP GRU kernel: hidden size must be a multiple of 32 and <= 256")
+        if self.H % (4 * ch) or self.H > 512:
+            raise NotImplementedError(f"HIP GRU kernel: hidden size must be <= 512 and a multiple of 32 in bf16, of 16 in float32 "
+                                      f"(this engine: {'bf16' if ch == 8 else 'float32'}, hidden size {self.H})")
         self.prefix = "autoregressive_model.gruCell."
 
     def allocate(self):

@@ -46,6 +46,8 @@ extern "C" {
  *    cpc_diff_scores_rank1.
  *    Added later under 9 (backward compatible, no entry point changed): the attention core for up to 128 steps cpc_attn128_fwd,
  *    cpc_attn128_bwd, cpc_attn128_tangent, cpc_attn128_gp.
+ *    Added later under 9 (backward compatible, no entry point added or changed): cpc_gru_tape_elems, cpc_gru_fwd, cpc_gru_fwd_h0,
+ *    cpc_gru_bwd, cpc_gru_gp_fwd and cpc_gru_gp_bwd accept hidden sizes up to 512 (were 256).
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -513,6 +515,8 @@ int cpc_cast2d_batch(const void* jobs, int njobs, int dtype, void* stream);
 int cpc_prep_frag(const float* src, void* dst, int R, int Kd, long long ld, int transpose, int dtype, void* stream);
 
 /* AudioGRUModel.forward's python loop over nn.GRUCell (audio_model.py:66-77) as one persistent launch.
+ * H: a multiple of 32 (bf16) or 16 (f32), at most 512 (weight-resident bf16 kernels for H in {32, 64, 128, 256}, weight-streaming
+ * kernels otherwise: 4 waves per workgroup up to H = 256, 8 above).
  *   Gi    T   [B][V][3H]  = x_t W_ih^T + b_ih for all steps (cpc_gemm_nt), gate order r, z, n
  *   Wfrag T   cpc_prep_frag(weight_hh [3H][H]);  bhh f32 [3H]
  *   Hall  T   [B][V+1][H] hidden states (Hall[:,0] = 0)
@@ -534,7 +538,7 @@ int cpc_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG,
                 void* stream);
 
 /* The Wasserstein gradient penalty through AudioGRUModel (contrastive_estimation_training.py:144-158: loss.backward() through
- * torch.autograd.grad(..., create_graph=True), here for the GRUCell loop of audio_model.py:66-77).  f32 only, H <= 256.
+ * torch.autograd.grad(..., create_graph=True), here for the GRUCell loop of audio_model.py:66-77).  f32 only, H <= 512.
  * cpc_gru_gp_fwd: primal and tangent recurrence together.  Gi as for cpc_gru_fwd (f32); GiT [B][V][3H] = (tangent of x_t) W_ih^T
  * (no bias); WT [H][3H] = weight_hh transposed; bhh [3H]; tape f32 [B][V][10][H] (r, z, n, W_hn h + b_hn, h_{t-1}, then the
  * tangents of the pre-activations of r and z, of W_hn h, of the pre-activation of n, and of h_{t-1}); ct_out [B][H] = tangent of

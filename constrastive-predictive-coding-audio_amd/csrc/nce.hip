@@ -405,17 +405,19 @@ __global__ __launch_bounds__(256) void nce_row_eval_kernel(const float* __restri
     if (r >= rows) return;
     const float* row = S + (long long)r * ld;
     float sum = 0.f, best = -INFINITY;
-    int arg = 0x7fffffff;
+    int arg = 0x7fffffff;                                     // (a lane without columns keeps it: it loses every comparison below)
     for (int c = lane; c < cols; c += 64) {
         const float v = score_tf(row[c], softplus);
         sum += v;
-        if (v > best || (v != v && best == best)) { best = v; arg = c; }          // a NaN wins, as in torch.argmax
+        if (c == lane || v > best || (v != v && best == best)) { best = v; arg = c; }      // a NaN wins, as in torch.argmax
     }
+    // first arg max, as torch.argmax: a NaN beats every number, and between two NaNs or two equal numbers the smaller column wins
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oa = __shfl_xor(arg, o, 64);
         sum += __shfl_xor(sum, o, 64);
-        const bool take = (ob > best) || (ob != ob && best == best) || (ob == best && oa < arg);
+        const bool onan = ob != ob, bnan = best != best;
+        const bool take = onan ? (!bnan || oa < arg) : (!bnan && (ob > best || (ob == best && oa < arg)));
         if (take) { best = ob; arg = oa; }
     }
     if (lane == 0) {
@@ -518,8 +520,8 @@ __global__ __launch_bounds__(256) void nce_lse_merge_kernel(const float* __restr
 // d loss / d linear score from the f32 scores the fused GEMM stored, and its transpose: Sb [items K][ld] (row (b, k) = a prediction, column
 // c = a target), lse [ncols]:
 //   dS[r][c] = score'(s) * ( (exp(sp - lse[c]) - [c == r + diag_off]) / n_rows + 2 reg / (n_items^2 K^2) * m[b][c] ),   m = mean_k sp[(b,k)][c]
-// (n_rows / n_items: of the WHOLE problem — a rank of a data-parallel run holds a strip of it).  Workgroup = 16 items x 64 columns, 128 threads:
-// thread = (item, 8 columns), 16-byte loads / stores along the rows; the transposed copy goes through an LDS image [64][16 K] and leaves
+// (n_rows / n_items: of the WHOLE problem — a rank of a data-parallel run holds a strip of it).  Workgroup = 16 items x 64 columns, 256 threads:
+// thread = (item, 4 columns), 16-byte loads / 8-byte stores along the rows; the transposed copy goes through an LDS image [64][16 K] and leaves
 // as 16 K contiguous elements per column.  gradp[block] = sum of m^2 over the block's (item, column) pairs (the regulariser's value).
 constexpr int NFG_IT = 16, NFG_CW = 64;
 // KT > 0: K as a compile-time constant — the K rows of a thread are loaded once, all loads in flight (with a run-time K the rows are read
@@ -602,8 +604,13 @@ __global__ __launch_bounds__(256) void nce_fused_grad_kernel(const float* __rest
         for (int q = tid; q < NFG_CW * cpr; q += 256) {
             const int cl = q / cpr, ch = q % cpr;
             const int c = blockIdx.x * NFG_CW + cl;
-            if (c < ncols && ch * 8 < rows_here)
-                *(uint4*)(dST + (long long)c * ldT + (long long)blockIdx.y * NFG_IT * K + ch * 8) = *(const uint4*)(tsm + cl * rs + ch * 16);
+            if (c >= ncols || ch * 8 >= rows_here) continue;
+            bf16_t* out = dST + (long long)c * ldT + (long long)blockIdx.y * NFG_IT * K + ch * 8;
+            if (ch * 8 + 8 <= rows_here) {
+                *(uint4*)out = *(const uint4*)(tsm + cl * rs + ch * 16);
+            } else {                                          // partial last item block: the chunk's elements up to rows_here only
+                for (int e = 0; e < rows_here - ch * 8; ++e) out[e] = ((const bf16_t*)(tsm + cl * rs + ch * 16))[e];
+            }
         }
     }
     red[tid] = msq;

@@ -157,7 +157,9 @@ __global__ __launch_bounds__(256) void cast2d_batch_kernel(const CastJob* __rest
 }
 
 // MaxPool1d(pool, ceil_mode=True) over positions of a channels-last activation (ConvolutionalArBlock, audio_model.py:98-99).
-// out[b][p][c] = max_{i < pool, p*pool+i < Lin_valid} in[b][p*pool+i][c];  pad rows (p >= Lout_valid) get zeros.
+// out[b][p][c] = max_{i < pool, p*pool+i < Lin_valid} in[b][p*pool+i][c];  pad rows (p >= Lout_valid) get zeros.  A NaN in a window
+// is its maximum, as in torch (a window element replaces the running maximum when it is greater or NaN): the NaN guard of the
+// training loop must see it.
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ in, T* __restrict__ out, int B, int C, int pool,
                                                           int Lin_valid, int Lin_alloc, int Lout_valid, int Lout_alloc) {
@@ -174,15 +176,15 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
             for (int i = 1; i < pool && pp * pool + i < Lin_valid; ++i) {
                 const f32x4 v = load4(src + (long long)i * C);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+                for (int e = 0; e < 4; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];
             }
         }
         store4(out + ((long long)b * Lout_alloc + pp) * C + c4 * 4, m);
     }
 }
 
-// Backward of the pooling: the gradient of a window goes to its FIRST maximal element (torch semantics); everything
-// else, and the pad rows, get zeros.
+// Backward of the pooling: the gradient of a window goes to the element the forward rule above ends on (torch semantics): the
+// FIRST maximal element, or the LAST NaN of a window holding NaN; everything else, and the pad rows, get zeros.
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ in, const T* __restrict__ dout, T* __restrict__ din,
                                                           int B, int C, int pool, int Lin_valid, int Lin_alloc, int Lout_alloc) {
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
                 const f32x4 v = load4(src + (long long)i * C);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (v[e] > best[e]) { best[e] = v[e]; arg[e] = i; }
+                    if (v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; arg[e] = i; }
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) g[e] = arg[e] == me ? d[e] : 0.f;

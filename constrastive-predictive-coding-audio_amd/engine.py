@@ -889,6 +889,9 @@ class CPCEngine:
         B, n = self.B, self.n
         La, Lv = self.geo.alloc, self.geo.valid
         bl, self._bl_active = getattr(self, "_bl_active", None), None      # target lane (_bwd_lane): this pass covers rows [0, n_l + 1) only
+        # Target lane invariant: every main-stream reader of rows the side stream's lane wrote (rows >= n_l of dact[l], the second slab
+        # set of bl.c1) first waits on that layer's lane event bl.ev[l + 1] (bl.ev[1] for bl.c1).  Side-stream readers are ordered behind
+        # the lane by their stream alone.
         cs_slabs = self.cs_slabs if bl is None else bl.cs
         # encoder, top layer down to layer 2.  Main stream: weight-gradient GEMM, data-gradient GEMM.  Side stream, after the
         # weight-gradient GEMM: the bias column sum (needs dact[l]) and the slab reduction, see _alloc_encoder.
@@ -912,6 +915,8 @@ class CPCEngine:
                           work=flops,
                           shape=("wgrad", B * La[l], kw * cin, cout, self.nsplit[l]))
             if wg_mode == "0":
+                if bl is not None and l < n - 1:
+                    torch.cuda.current_stream().wait_event(bl.ev[l + 1])     # wgrad reads rows >= n_l of dact[l] (see below)
                 wgrad_call()
             with self.side(self._ev_w[l]):
                 for fn in getattr(self, "_deferred_side", ()):       # work backward() put off the main stream (see there)
@@ -954,6 +959,7 @@ class CPCEngine:
         # layer 1
         c0, k0, s0 = self.channels[0], self.kernels[0], self.strides[0]
         if bl is not None:
+            torch.cuda.current_stream().wait_event(bl.ev[1])                 # the side stream's slab tiles of bl.c1 (part 1 of layer 1)
             _hip.call("cpc_conv1_fused_reduce_tiles", _hip.ptr(bl.c1), _hip.ptr(self.c1_tmp), _hip.ptr(g["encoder.layers.0.weight"]),
                       _hip.ptr(g.get("encoder.layers.0.bias")), sum(bl.tiles[1]), c0, self.strides[1], k0)
             return

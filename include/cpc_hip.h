@@ -597,7 +597,7 @@ int cpc_nce_loss_all(const float* S, const float* ST, void* dS, void* dST, float
  *                      {sum of the block's lse, max of its pm}.
  *   cpc_nce_fused_grad d loss / d linear score (bf16, dS [items K][ld]; and its transpose, dST [ncols][ldT], or NULL) from S and lse, as cpc_nce_loss_all forms it:
  *                      (exp(sp - lse[c]) - [c == r + diag_off]) / n_rows_total + 2 reg / (n_items_total^2 K^2) mean_k sp[(b,k)][c], times the score
- *                      function's derivative; rows r = (item, k), items K of them, K even and <= 24, ncols a multiple of 8; gradp
+ *                      function's derivative; rows r = (item, k), items K of them, K even and <= 24, ncols a multiple of 4; gradp
  *                      [cpc_nce_fused_grad_blocks(items, ncols)] = partial sums of (mean_k sp)^2 (the regulariser :141).
  *   cpc_nce_fused_finalize   the eight values cpc_nce_loss_all writes to `out`.  mode 0: from the partials (colp, valid, gradp); mode 1:
  *                      the partials reduced to sums[4] = {sum valid, sum lse, sum m^2, max s} only — a rank that holds a strip of the
@@ -619,7 +619,7 @@ int cpc_nce_fused_finalize(const float* colp, int ncolp, const float* valid, int
  * score matrices the train step uses (S of cpc_nce_loss when all_timesteps == 0, S of cpc_nce_loss_all otherwise; softplus as
  * there): out[0..K) = prediction_losses per step (:237-241, including the reference's reading of the (k, b') log-sum-exps as a
  * (B, K) matrix in flat order in the default branch), out[K..2K) = prediction_accuracy per step (:245-247: arg max over the
- * targets of every prediction equal to its own target; first maximum on ties), out[2K] = mean score (:249).  accumulate != 0
+ * targets of every prediction equal to its own target; first maximum on ties, first NaN if the row holds one, as torch.argmax), out[2K] = mean score (:249).  accumulate != 0
  * adds to out instead of overwriting it (validate sums over batches and divides once).  workspace:
  * cpc_nce_eval_workspace_floats(B, K) f32. */
 long long cpc_nce_eval_workspace_floats(int B, int K);

@@ -177,22 +177,6 @@ def test_stem_arguments_are_checked_before_any_launch():
 # here; the list may only shrink (a name that a test mentions must leave it).
 ABI_NAMES_WITHOUT_A_TEST = {
     "cpc_abi_version": "checked by the library loader (_hip.lib) and by test_c_abi_v9_exports_every_declared_symbol in this file",
-    "cpc_conv1_fwd_rows": "encoder row-range launch: only through test_model_gpu.py::test_target_lanes_equal_the_single_lane_step",
-    "cpc_conv_dgrad_rows": "encoder row-range launch: only through test_target_lanes_equal_the_single_lane_step",
-    "cpc_conv_dgrad_conv1_rows": "encoder row-range launch: only through test_target_lanes_equal_the_single_lane_step",
-    "cpc_conv1_fused_reduce_tiles": "encoder row-range reduction: only through test_target_lanes_equal_the_single_lane_step",
-    "cpc_maxpool_fwd": "ConvAr context pooling: only through whole-model runs",
-    "cpc_maxpool_bwd": "ConvAr context pooling backward: only through whole-model runs",
-    "cpc_relu_row_bwd": "ConvAr context ReLU backward: only through whole-model runs",
-    "cpc_gru_fwd_h0": "GRU forward from a given initial state: only through whole-model runs",
-    "cpc_gru_set_streaming": "GRU launch-mode switch: only through whole-model runs",
-    "cpc_nce_eval": "evaluation-mode NCE scores: only through the trainer's validation path",
-    "cpc_nce_eval_workspace_floats": "workspace size of cpc_nce_eval: only through the trainer's validation path",
-    "cpc_cast2d": "weight casts of the context network: only through whole-model runs",
-    "cpc_cast2d_batch": "batched weight casts: only through whole-model runs",
-    "cpc_dropout": "attention dropout: only through test_gradient_penalty_attention_context_with_dropout_against_oracle",
-    "cpc_split3_bf16": "bf16x3 CQT operand split: only through test_cqt_full_size_against_oracle",
-    "cpc_scalogram_pointwise": "scalogram pointwise chain: only through the CQT / preprocessing tests against reference fixtures",
 }
 
 

@@ -375,7 +375,7 @@ class _EncoderForward(torch.autograd.Function):
         dtop.zero_()
         dtop[:, :T, :].copy_(d_out.transpose(1, 2))
         eng._ahead = None
-        fused = getattr(eng, "fuse_c1", False)
+        fused = eng.fuse_c1
         if ctx.need_dx and fused:
             eng.fuse_c1 = False          # the input gradient needs layer 1's output gradient in memory: the unfused layer-2 / layer-1 route
         try:
@@ -383,7 +383,7 @@ class _EncoderForward(torch.autograd.Function):
         finally:
             if ctx.need_dx and fused:
                 eng.fuse_c1 = True
-        for fn in getattr(eng, "_deferred_side", ()):
+        for fn in eng._deferred_side:
             fn()
         eng._deferred_side = ()
         if eng.use_aux:

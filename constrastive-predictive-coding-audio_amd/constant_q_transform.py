@@ -11,7 +11,6 @@ UNPINNED.  Everything downstream of the coefficients is pinned: pass ``filters=(
 librosa, or load a reference state_dict, and the outputs follow the reference exactly.
 """
 import math
-import os
 
 import numpy as np
 import ctypes as C
@@ -135,7 +134,7 @@ class CQT(nn.Module):
                 rows, start, size = [banks[i][0]], banks[i][1], banks[i][2]
                 count = rows[0].shape[0]
                 j = i + 1
-                while j < len(banks) and count + banks[j][0].shape[0] <= 128 and os.environ.get("CPC_CQT_MERGE", "1") != "0":
+                while j < len(banks) and count + banks[j][0].shape[0] <= 128:
                     wj, _, sj = banks[j]
                     pad = torch.zeros(wj.shape[0], size, device=device, dtype=torch.float32)
                     o = (size - sj) // 2
@@ -148,13 +147,12 @@ class CQT(nn.Module):
             for inter, start, size in merged:
                 # Only the taps some filter of the bank actually has: a constant-Q filter is its window's length, centred in the
                 # power-of-two frame (the longest of the default bank: 12 060 of 16 384 taps) -- the zero margins are dropped from the
-                # contraction (bounds rounded outwards to multiples of 128 taps: the K-stage, also of a half when K is split; CPC_CQT_TRIM=0: the full frames).
+                # contraction (bounds rounded outwards to multiples of 128 taps: the K-stage, also of a half when K is split).
                 lo, hi = 0, size
-                if os.environ.get("CPC_CQT_TRIM", "1") != "0":
-                    nz = (inter != 0).any(dim=0).nonzero()
-                    if nz.numel():
-                        lo = int(nz.min()) // 128 * 128
-                        hi = min(size, (int(nz.max()) + 128) // 128 * 128)
+                nz = (inter != 0).any(dim=0).nonzero()
+                if nz.numel():
+                    lo = int(nz.min()) // 128 * 128
+                    hi = min(size, (int(nz.max()) + 128) // 128 * 128)
                 inter = inter[:, lo:hi]
                 npad = (inter.shape[0] + 7) // 8 * 8
                 full = torch.zeros(npad, hi - lo, device=device, dtype=torch.float32)

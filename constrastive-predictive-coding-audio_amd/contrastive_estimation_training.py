@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 import random
 
 import torch
@@ -25,6 +24,7 @@ import torch.utils.data
 
 from .audio_model import *          # noqa: F401,F403  (the reference re-exports the model names from here)
 from .audio_dataset import FileBatchSampler
+from . import switches
 
 
 def _need_gpu(t, what):
@@ -45,8 +45,6 @@ class InputAhead:
         from .engine import side_stream
         self.fn, self.device = fn, torch.device(device)
         self.aux = side_stream(self.device)
-        if os.environ.get("CPC_PREPROCESS_STREAM", "side") == "own":          # A/B: a stream of its own at the default priority
-            self.aux = _own_stream(self.device)
         self.pending = []
 
     def submit(self, batch):
@@ -68,16 +66,6 @@ class InputAhead:
         if isinstance(x, torch.Tensor):
             x.record_stream(main)
         return batch, x
-
-
-_OWN_STREAMS = {}
-
-
-def _own_stream(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _OWN_STREAMS:
-        _OWN_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _OWN_STREAMS[key]
 
 
 def _with_next(it):
@@ -518,7 +506,7 @@ class ContrastiveEstimationTrainer:
             with ctx as prof_ctx:
                 ahead = None
                 if (fused and not graphed and self.preprocessing is not None and self.preprocess_ahead and device.type == "cuda"
-                        and os.environ.get("CPC_PREPROCESS_AHEAD", "1") != "0"):
+                        and switches.preprocess_ahead()):
                     ahead = InputAhead(self._model_input, device)
                 batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world)
                 # (the sampler is read one batch ahead only where that batch is preprocessed ahead)

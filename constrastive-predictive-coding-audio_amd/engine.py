@@ -17,13 +17,12 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
-import os
 from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import torch
 
-from . import _hip
+from . import _hip, switches
 
 
 _SIDE_STREAMS = {}
@@ -124,8 +123,15 @@ class CPCEngine:
         self.ctx = make_context(self, ar) if (self.V + self.K) > 0 else None
         self._alloc()
 
+    # Step-control state with its defaults (every engine class, and a _Float32EngineView through its engine, sees these)
+    _gp_phase = 0               # gradient-penalty step: which of its passes is running (0: an ordinary step)
+    _deferred_side = ()         # calls backward() put off the main stream, for the encoder backward's first side-stream block
+    _bl_active = None           # the backward target lane (_bwd_lane) of the pass in flight, or None
+    fuse_c1 = False             # layer 2's data gradient fused with layer 1's weight / bias gradient (_alloc_encoder)
+    gp_capable = False          # built for gradient-penalty steps
+
     # ------------------------------------------------------------------------------------------ side stream
-    use_aux = os.environ.get("CPC_SIDE_STREAM", "1") != "0"     # False: everything on the launching stream (GraphedStep captures that way; CPC_SIDE_STREAM=0 for A/B runs)
+    use_aux = True     # False (set on the instance): everything on the launching stream (GraphedStep captures that way)
 
     @contextlib.contextmanager
     def side(self, ev):
@@ -187,9 +193,9 @@ class CPCEngine:
         # 950 us, layer-1 forward +20 us.  For the deeper layers the same trade is even (the forward GEMMs' epilogues pay 2-6 % for
         # writing the bits — one workgroup per CU, nothing to hide an epilogue instruction behind — and a separate kernel costs what
         # the data gradients gain — also when that kernel runs on the side stream while the GRU leaves 240 CUs idle: 4.52 -> 4.57 ms per
-        # step), so they keep reading their masks from the activations.  CPC_MASK_BITS=0: plain masks (A/B).
+        # step), so they keep reading their masks from the activations.
         self.act_bits: List[Optional[torch.Tensor]] = [None] * n
-        if (dt == torch.bfloat16 and os.environ.get("CPC_MASK_BITS", "1") != "0" and n >= 2 and self.channels[0] == 512
+        if (dt == torch.bfloat16 and n >= 2 and self.channels[0] == 512
                 and _hip.nt_tile(self.code, B * La[1], self.strides[1] * 512, self.geo.taps[1] * self.channels[1]) == 256
                 and self.guard[0] % 128 == 0):
             full = torch.zeros((2 * self.guard[0] + B * La[0] * 512) // 8, device=dev, dtype=torch.uint8)
@@ -200,7 +206,7 @@ class CPCEngine:
         # column-sum pass over the 0.06-0.24 GB gradient (beside the main-stream GEMMs those passes cost the step 58 us,
         # CPC_PROBE runs).  bf16 and 256 x 256 tiles only; the top layer's gradient comes from other kernels and keeps its pass.
         self.cs_slabs: List[Optional[torch.Tensor]] = [None] * n       # cs_slabs[l]: sums of dact[l], written by layer l+1's data gradient
-        if dt == torch.bfloat16 and os.environ.get("CPC_FUSED_COLSUM", "1") != "0":
+        if dt == torch.bfloat16:
             for l in range(2, n):
                 cin, cout, s = self.channels[l - 1], self.channels[l], self.strides[l]
                 if _hip.nt_tile(self.code, B * La[l], s * cin, self.geo.taps[l] * cout) == 256 and (s * cin) % 8 == 0:
@@ -227,7 +233,6 @@ class CPCEngine:
         need.append(self.colsum_blocks * max(self.channels))
         # bf16, wide first layer: the data gradient of layer 2 is fused with the weight / bias gradient of layer 1
         # (cpc_conv_dgrad_conv1): the 1 GB gradient of layer 1's output is neither written nor read back
-        self.fuse_c1 = False
         if n >= 2 and dt == torch.bfloat16 and self.channels[0] % 256 == 0 and self.kernels[0] <= 15:
             s1, c0, c1 = self.strides[1], self.channels[0], self.channels[1]
             if _hip.nt_tile(self.code, B * La[1], s1 * c0, self.geo.taps[1] * c1) == 256 and (self.geo.taps[1] * c1) % 64 == 0:
@@ -351,7 +356,7 @@ class CPCEngine:
         side stream; ``final`` False) and from step() for the head of the buffer (``final`` True, main stream, backward
         complete).  In a hook call the lowest updated encoder layer's data-gradient operand is still being read by that
         layer's data-gradient GEMM on the main stream: its next copy is built in a second buffer, swapped in by the final call."""
-        if not self.supports_prepare_ahead or not getattr(self.ctx, "ahead_ok", False) or os.environ.get("CPC_PREPARE_AHEAD", "1") == "0":
+        if not self.supports_prepare_ahead or not getattr(self.ctx, "ahead_ok", False) or not switches.prepare_ahead():
             return
         st = getattr(self, "_ahead", None)
         # (one Adam launch over everything, no gradient-ready pieces: the copies are rebuilt here, on the main stream behind Adam.  Doing that on
@@ -390,13 +395,13 @@ class CPCEngine:
     # With unpadded causal convolutions top rows [0, V) need rows [0, n_l) of layer l, n_{l-1} = s_l (n_l - 1) + k_l — a prefix of every
     # layer.  The GRU occupies 16 of the 256 CUs for 0.27 ms (100 dependent steps): the remaining rows of every layer (11 % of the encoder's
     # forward work at V = 100, K = 12) are computed on the side stream while it runs, and the main stream's forward launches are
-    # that much shorter.  Same kernels on row ranges, identical results (CPC_TARGET_LANE=0: one launch per layer).
+    # that much shorter.  Same kernels on row ranges, identical results (_tl_rows = None: one launch per layer).
     def _target_lane_rows(self):
         """n_l per layer (rows of layer l that the context network's frames depend on), or None when the split does not apply."""
         if getattr(self, "_tl_rows", 0) != 0:
             return self._tl_rows
         self._tl_rows = None
-        if (os.environ.get("CPC_TARGET_LANE", "1") == "0" or not self.use_aux or not isinstance(self.ctx, GRUContext) or self.K <= 0
+        if (not self.use_aux or not isinstance(self.ctx, GRUContext) or self.K <= 0
                 or self.V <= 0 or self.n < 2 or self.T != self.V + self.K):
             return None
         La = self.geo.alloc
@@ -418,8 +423,7 @@ class CPCEngine:
         256-wide tile from 200 tiles on): layer 2's target rows at the headline size are 196 such tiles — 0.11 ms in one round against
         0.135 ms as 784 128-wide tiles on 512 slots."""
         tiles = _ceil_div(M, 256) * _ceil_div(N, 256)
-        lo = int(os.environ.get("CPC_ROW_BIG_TILE_MIN", "160"))
-        return _hip.GEMM_BIG_TILE if (self.dt == torch.bfloat16 and lo <= tiles < 200 and N % 256 == 0) else 0
+        return _hip.GEMM_BIG_TILE if (self.dt == torch.bfloat16 and 160 <= tiles < 200 and N % 256 == 0) else 0
 
     def _encoder_rows(self, x, lo, hi):
         """Layers 1 .. n on rows [lo[l], hi[l]) of every item (hi[l] = L_alloc[l]: to the end, pad rows included)."""
@@ -573,10 +577,10 @@ class CPCEngine:
     # ---- score_over_all_timesteps=True with the column pass fused into the score GEMM (bf16; include/cpc_hip.h, cpc_score_lse) ----
     def fused_scores_ok(self, rows=None, cols=None):
         """The fused path needs bf16 storage, 256-row / 256-column tiles, E a multiple of 64 and an even K <= 24
-        (CPC_FUSED_SCORE=0: the unfused kernels, A/B)."""
+        (switches.fused_score off: the unfused kernels)."""
         R = self.B * self.K
         rows, cols = (R if rows is None else rows), (R if cols is None else cols)
-        return (self.dt == torch.bfloat16 and os.environ.get("CPC_FUSED_SCORE", "1") != "0" and rows % 256 == 0 and cols % 256 == 0
+        return (self.dt == torch.bfloat16 and switches.fused_score() and rows % 256 == 0 and cols % 256 == 0
                 and self.E % 64 == 0 and self.E >= 128 and self.K % 2 == 0 and self.K <= 24)
 
     def _nce_all_fused(self, softplus: bool, regularization: float):
@@ -804,7 +808,7 @@ class CPCEngine:
                          flags=_hip.GEMM_OUT_F32)
         if add_dc is not None:
             self.dc.add_(add_dc)
-        lanes_ok = self.use_aux and getattr(self, "fuse_c1", False) and os.environ.get("CPC_WGRAD_STREAM", "1") != "0" and getattr(self, "_gp_phase", 0) == 0
+        lanes_ok = self.use_aux and self.fuse_c1 and switches.wgrad_stream() and self._gp_phase == 0
         self._bl_active = self._bwd_lane() if lanes_ok else None
         if self._bl_active is not None:
             self._backward_target_rows(x, self._bl_active)
@@ -812,7 +816,7 @@ class CPCEngine:
         if add_dz is not None:
             dtop.view(B, Ltop, E)[:, t0:t0 + V, :].add_(add_dz.transpose(1, 2), alpha=getattr(self.ctx, "z_scale", 1.0))
         self._backward_encoder(x, grad_ready_hook)
-        for fn in getattr(self, "_deferred_side", ()):           # an encoder backward without that side block (scalogram engine)
+        for fn in self._deferred_side:           # an encoder backward without that side block (scalogram engine)
             fn()
         self._deferred_side = ()
         if self.use_aux:
@@ -825,7 +829,7 @@ class CPCEngine:
         frames, whose top-layer gradient is final once the loss kernels are — run on the side stream beside the GRU's backward recurrence
         (_backward_target_rows); the main stream's launches after the recurrence cover rows [0, n_l + 1).  The weight gradients stay
         one launch per layer: split at row n_l the same way (two slab sets, one reduction) they cost the step 0.37 ms — the chip is full
-        once the recurrence has ended, and the second slab set is pure extra traffic (round 4, CPC_TARGET_LANE_BWD A/B: 4.52 off, 4.49 on,
+        once the recurrence has ended, and the second slab set is pure extra traffic (round 4, A/B of this lane: 4.52 off, 4.49 on,
         4.89 with the weight gradients split).  Tried on top of this and removed again: the recurrence itself in two step
         ranges with the encoder rows of the later frames beside the first (forward) / the earlier steps beside the encoder's backward pass
         over the late rows (backward) — bit-identical, and 0.0 - 0.1 ms SLOWER: what the hidden recurrence saves, the split launches lose."""
@@ -835,7 +839,7 @@ class CPCEngine:
         self._bl = None
         nr = self._target_lane_rows()
         n, B, La = self.n, self.B, self.geo.alloc
-        if (nr is None or os.environ.get("CPC_TARGET_LANE_BWD", "1") == "0" or self.dt != torch.bfloat16 or not self.fuse_c1
+        if (nr is None or self.dt != torch.bfloat16 or not self.fuse_c1
                 or type(self)._backward_encoder is not CPCEngine._backward_encoder
                 or any(self.kernels[l] != 2 * self.strides[l] for l in range(1, n))
                 or any(B * (La[l] - nr[l] - 1) < 256 for l in range(1, n))):
@@ -888,7 +892,7 @@ class CPCEngine:
         g, code = self.model._grad, self.code
         B, n = self.B, self.n
         La, Lv = self.geo.alloc, self.geo.valid
-        bl, self._bl_active = getattr(self, "_bl_active", None), None      # target lane (_bwd_lane): this pass covers rows [0, n_l + 1) only
+        bl, self._bl_active = self._bl_active, None      # target lane (_bwd_lane): this pass covers rows [0, n_l + 1) only
         # Target lane invariant: every main-stream reader of rows the side stream's lane wrote (rows >= n_l of dact[l], the second slab
         # set of bl.c1) first waits on that layer's lane event bl.ev[l + 1] (bl.ev[1] for bl.c1).  Side-stream readers are ordered behind
         # the lane by their stream alone.
@@ -899,14 +903,14 @@ class CPCEngine:
             cin, cout, kw, s = self.channels[l - 1], self.channels[l], self.kernels[l], self.strides[l]
             bname = f"encoder.layers.{l}.bias"
             flops = 2.0 * B * La[l] * cout * kw * cin
-            wg_mode = os.environ.get("CPC_WGRAD_STREAM", "1")
+            side_wgrad = switches.wgrad_stream()
 
             # The weight-gradient GEMM of layer l and the data-gradient GEMM of layer l both read dact[l] and are independent: the
             # weight gradient is issued on the side stream, beside the data-gradient chain (the tiles of the two kernels interleave on
             # the CUs, the partial last rounds of tiles of one launch are filled by the other, and both read dact[l] while it is in the
             # caches): 4.61 -> 4.55 ms per step at the end of round 2 (4.72 -> 4.69 before the side stream was cleared of the
             # column-sum passes).  Every kernel then runs longer BY ITSELF: bench.py reports the dominant kernel's roofline both as
-            # it runs in the step and alone (CPC_WGRAD_STREAM=0: everything on the main stream, the round-1 arrangement).
+            # it runs in the step and alone (switches.wgrad_stream off: everything on the main stream, the round-1 arrangement).
             def wgrad_call():
                 _hip.call("cpc_conv_wgrad", _hip.ptr(self.act[l - 1]), _hip.ptr(self.dact[l]), _hip.ptr(self.wslab[l]), B, cin, cout, kw, s,
                           La[l], self.nsplit[l], C.c_longlong(self.guard[l - 1]), code,
@@ -914,15 +918,15 @@ class CPCEngine:
                                                                                                  self._chunk(B * La[l], self.nsplit[l]))),
                           work=flops,
                           shape=("wgrad", B * La[l], kw * cin, cout, self.nsplit[l]))
-            if wg_mode == "0":
+            if not side_wgrad:
                 if bl is not None and l < n - 1:
                     torch.cuda.current_stream().wait_event(bl.ev[l + 1])     # wgrad reads rows >= n_l of dact[l] (see below)
                 wgrad_call()
             with self.side(self._ev_w[l]):
-                for fn in getattr(self, "_deferred_side", ()):       # work backward() put off the main stream (see there)
+                for fn in self._deferred_side:       # work backward() put off the main stream (see there)
                     fn()
                 self._deferred_side = ()
-                if wg_mode != "0":
+                if side_wgrad:
                     wgrad_call()
                 # (ONE event per layer on the main stream: a recorded event between two GEMMs costs ~6 us of idle queue)
                 if bname in g:
@@ -1111,7 +1115,7 @@ class GRUContext:
         e, H = self.eng, self.H
         g, code, B, V, E, K = e.model._grad, e.code, e.B, e.V, e.E, e.K
         Ltop, t0, top, dtop = e.geo.alloc[-1], e.T - K - V, e.act[-1], e.dact[-1]
-        phase = getattr(e, "_gp_phase", 0)
+        phase = e._gp_phase
         if getattr(self, "carried", False):
             raise RuntimeError("this GRU call started from a state carried over from the previous call (reset_hidden=False): it cannot be "
                                "differentiated -- the reference's autograd cannot either (the previous call's graph is gone after its "
@@ -1448,7 +1452,7 @@ class AttentionContext:
         self.w_end, self.w_end_t = new(H * C), new(C * H)
         # LayerNorm backward: a wave walks its rows one at a time (load -> two wave reductions -> store), so the row loop is latency-
         # bound; 512 workgroups = 2 waves per SIMD overlap the rows (attention_architecture_1 at B = 256: 5.60 ms per step with 256 workgroups, 5.45 with 512 or 1024, 5.57 with 2048)
-        self.ln_blocks = max(1, min(int(os.environ.get("CPC_LN_BLOCKS", "512")), M // 4))
+        self.ln_blocks = max(1, min(512, M // 4))
         self.split = {k: e._pick_split(r, c, M) for k, (r, c) in shapes.items()}
 
     def slab_floats(self):
@@ -1687,7 +1691,7 @@ class AttentionContext:
 
     def backward(self, dc):
         e = self.eng
-        phase = getattr(e, "_gp_phase", 0)
+        phase = e._gp_phase
         if phase == 1:               # gradient penalty, pass 1: dc is the adjoint of the summed scores (the last pass starts from it)
             self._gp_buffers()
             self.gp.dc1.copy_(dc)
@@ -1839,7 +1843,7 @@ class Float32Context:
 def make_context(eng, ar):
     from .audio_model import AudioGRUModel, ConvolutionalArModel
     from .attention_model import AttentionModel
-    if getattr(eng, "gp_capable", False) and eng.dt != torch.float32 and isinstance(ar, (AudioGRUModel, AttentionModel)):
+    if eng.gp_capable and eng.dt != torch.float32 and isinstance(ar, (AudioGRUModel, AttentionModel)):
         return Float32Context(eng, GRUContext if isinstance(ar, AudioGRUModel) else AttentionContext, ar)
     if isinstance(ar, AudioGRUModel):
         return GRUContext(eng, ar)
@@ -1848,7 +1852,7 @@ def make_context(eng, ar):
         # later one, stride 1); every other configuration runs on the grid kernels
         lean = not (ar.batch_norm or ar.residual) and all(s == 1 for s in ar.strides) and ar.poolings[0] == 1 and \
             all(p > 1 for p in ar.poolings[1:])
-        if getattr(eng, "gp_capable", False):
+        if eng.gp_capable:
             lean = False          # the gradient penalty's tangent pass lives in the grid implementation
         if not lean:
             from .scalogram_engine import ConvArGridContext
@@ -2172,7 +2176,7 @@ class GlobalNegatives:
         dist.all_gather([self.targ_all[r * n:(r + 1) * n] for r in range(self.world)], self.local_targ)
         P = _hip.ptr
         if all_timesteps:
-            if e.fused_scores_ok(rows=B * K, cols=B * K) and os.environ.get("CPC_SCORE_STRIPS", "1") != "0":
+            if e.fused_scores_ok(rows=B * K, cols=B * K):
                 self._all_timesteps_strips(softplus, regularization)
             else:
                 self._all_timesteps(softplus, regularization)

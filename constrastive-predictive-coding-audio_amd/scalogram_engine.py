@@ -10,13 +10,12 @@ read, so everything downstream is shared with engine.CPCEngine.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
 
-from . import _hip
+from . import _hip, switches
 from .engine import CPCEngine, Float32Context, _ceil_div, make_context, score_kind, side_stream
 
 
@@ -81,7 +80,7 @@ def _col_group(cout, kw=1, stride=(1, 1), pad=0):
     """How many consecutive output rows a tall-kernel GEMM computes per GEMM row: with fewer than 128 output channels the
     128-wide MFMA tile would be mostly empty, so G = 128 / C_out rows are produced side by side (their windows overlap in
     all but G-1 input rows; the weight operand holds G shifted copies of the kernel, +(G-1)/k extra FLOPs)."""
-    width = int(os.environ.get("CPC_COL_WIDTH", "256"))      # 256 x 256 tiles of the large GEMM kernels (128: 20.5 -> 22.2 ms per configs[2] step)
+    width = 256      # 256 x 256 tiles of the large GEMM kernels (measured with 128: 20.5 -> 22.2 ms per configs[2] step)
     if kw != 1 or stride != (1, 1) or pad != 0 or cout >= width or width % cout:
         return 1
     return width // cout
@@ -97,7 +96,7 @@ def _prepare_convs(eng, holder, convs):
     GEMM row) share ONE cpc_conv_w_prep_batch launch — eleven launches of 20 us each for ar_conv_architecture_3 otherwise; the job table is
     planned once per parameter buffer (``holder`` keeps it)."""
     batch = [c for c in convs if isinstance(c, _Conv) and c.mode == 'col' and c.G == 1]
-    if len(batch) < 2 or os.environ.get("CPC_PREP_BATCH", "1") == "0":
+    if len(batch) < 2:
         batch = []
     for c in convs:
         if c not in batch:
@@ -148,7 +147,6 @@ class _Conv:
                 raise AssertionError("an overlapped-row convolution writes its input's row geometry (use _CastRelu for other outputs)")
             self.y0 = Grid(B, gin.W, self.Ho, self.cout, dev, dt, top=0, tail=gin.Ha - self.Ho, guard_rows=self.kh + 16)
             self.K = self.kh * self.cin
-            self.M = gin.rows
             G = _col_group(self.cout)
             self.G = G if (G > 1 and gin.Ha % G == 0 and dt == torch.bfloat16) else 1
             if self.G > 1:
@@ -160,35 +158,32 @@ class _Conv:
             # Only the rows that exist are computed.  A valid convolution with a tall kernel has Ho = Ha - kh + 1 output rows per column
             # (127 of 190, 34 of 63, 2 of 16 in scalogram_resnet_architecture_7), and only the rows [top, top + H) of the input carry a
             # gradient: the GEMMs address "rows per column" (a_rpi / c_rpi) instead of running over every allocated row of the grid
-            # (CPC_COL_VALID=0: all rows, the round-2 form -- 33 ... 47 % more GEMM work on the tall kernels).
-            self.valid_rows = os.environ.get("CPC_COL_VALID", "1") != "0"
+            # (the round-2 form, over all rows, was 33 ... 47 % more GEMM work on the tall kernels).
             self.ncol = B * gin.W
             Gq = self.G
             self.Hg = _ceil_div(self.Ho, Gq)                                   # output (super-)rows per column
             self.r0 = gin.top // Gq                                            # first input (super-)row that carries a gradient
             self.nr = _ceil_div(gin.top + gin.H, Gq) - self.r0                 # ... and how many
+            self.Mw = self.ncol * self.Hg                                      # rows of the weight-gradient reduction
             if self.G > 1:
                 G = self.G
                 self.w_fwd = torch.zeros(G, self.cout, self.Rw, self.cin, device=dev, dtype=dt)       # [(dh,co)][(r,c)]
                 self.w_dgrad = torch.zeros(G, self.cin, self.Rd, self.cout, device=dev, dtype=dt)     # [(dr,c)][(q,co)]
                 self.bias_g = torch.zeros(G * self.cout, device=dev, dtype=torch.float32)
-                self.Mw = self.ncol * self.Hg if self.valid_rows else self.M // G          # rows of the weight-gradient reduction
                 self.nsplit = eng._pick_split(self.Rw * self.cin, G * self.cout, self.Mw)
                 self.slab = self.nsplit * self.Rw * self.cin * G * self.cout
             else:
                 self.w_fwd = torch.empty(self.cout * self.K, device=dev, dtype=dt)
                 self.w_dgrad = torch.empty(self.cin * self.kh * self.cout, device=dev, dtype=dt)
-                self.Mw = self.ncol * self.Hg if self.valid_rows else self.M
                 self.nsplit = eng._pick_split(self.K, self.cout, self.Mw)
                 self.slab = self.nsplit * self.K * self.cout
-            rb = int(os.environ.get(f"CPC_DGRAD_BAND_K{self.kh}", os.environ.get("CPC_DGRAD_BAND", "1")))      # (per kernel height for A/B runs)
-            self.bands = self._bands(rb) if (self.valid_rows and need_dgrad) else None
+            self.bands = self._bands() if need_dgrad else None
         else:
             o_top, o_tail, o_guard = out_pad if out_pad is not None else (0, 0, 96)
-            # Data gradient of a 3x3 stride-2 convolution WITHOUT the im2col-gradient matrix (_dgrad_parity below; CPC_DGRAD_PARITY=0: off): needs
+            # Data gradient of a 3x3 stride-2 convolution WITHOUT the im2col-gradient matrix (_dgrad_parity below): needs
             # one zero row below every output column (the row "H_out" that the last input rows' windows reach)
             self.parity = (need_dgrad and (self.kh, self.kw, self.sh, self.sw, self.pad) == (3, 3, 2, 2, 0) and not in_f32 and
-                           os.environ.get("CPC_DGRAD_PARITY", "1") != "0" and (2 * self.cout) % (64 if dt == torch.bfloat16 else 32) == 0 and
+                           (2 * self.cout) % (64 if dt == torch.bfloat16 else 32) == 0 and
                            self.cin % 8 == 0 and gin.Ha >= 2 * (self.Ho + 1) and gin.W >= 2 * self.Wo + 1)
             if self.parity and out_pad is None:
                 o_tail = 1
@@ -202,7 +197,7 @@ class _Conv:
             kq = 64 if dt == torch.bfloat16 else 32
             self.Kp = _ceil_div(self.K, kq) * kq if self.K > kq // 2 else _ceil_div(self.K, 8) * 8
             self.M = B * self.Wo * self.Ho
-            # Forward and weight gradient without an im2col matrix (bf16; CPC_CONV_GATHER=0: off, =1: also the float32 forward): a GEMM row is the
+            # Forward and weight gradient without an im2col matrix (bf16; switches.conv_gather: off, or also the float32 forward): a GEMM row is the
             # window read straight from the grid as kw pieces — piece dw = the kh rows x C_in channels of kernel column dw, contiguous in the
             # channels-last grid, the next kernel column one grid column (Ha C_in elements) further (cpc_gemm_nt_args.k_taps / k_tap_stride_a;
             # each piece padded to the stage size with zero weights, which over-reads into the rows below: zeros or activations, never beyond
@@ -211,7 +206,8 @@ class _Conv:
             # (the im2col pass kept for the weight gradient, on the side stream) had measured 13.78 against 13.62.
             bkq = 64 if dt == torch.bfloat16 else 32
             self.seg = _ceil_div(self.kh * self.cin, bkq) * bkq
-            self.gather = (self.pad == 0 and not in_f32 and self.cin % 8 == 0 and (os.environ.get("CPC_CONV_GATHER", "") == "1" or (dt == torch.bfloat16 and os.environ.get("CPC_CONV_GATHER", "1") != "0")) and
+            gather_on = switches.conv_gather()
+            self.gather = (self.pad == 0 and not in_f32 and self.cin % 8 == 0 and (gather_on if gather_on is not None else dt == torch.bfloat16) and
                            gin.guard_rows * self.cin >= self.seg)
             if self.gather:
                 self.w_imp = torch.zeros(self.cout, self.kw, self.seg, device=dev, dtype=dt)
@@ -249,8 +245,7 @@ class _Conv:
         # G row pairs per GEMM row where 2 C_in columns would leave most of a 128-wide tile empty (C_in = 32: G = 2, the window is then the
         # three dY rows R-1 .. R+1 per piece): half the tiles, each full — 0.52 -> 0.3x ms for the even columns of block 1 of architecture 7
         G = 1
-        width = int(os.environ.get("CPC_DGRAD_PARITY_GROUP", "128"))          # 0: no grouping; 256: up to the 256-wide tile
-        while width and 2 * cin * G * 2 <= width and Hs % (2 * G) == 0:
+        while 2 * cin * G * 2 <= 128 and Hs % (2 * G) == 0:      # (up to the 128-wide tile)
             G *= 2
         Hg = Hs // G
         tile = 256 if 2 * cin * G >= 256 else 128
@@ -304,33 +299,27 @@ class _Conv:
         if gin.W > 2 * Wo + 1:                          # input columns no window reaches: zero (the residual branch adds into this grid)
             din.t.view(B, gin.W, col_i)[:, 2 * Wo + 1:, :].zero_()
 
-    def _bands(self, RB):
-        """Data gradient of a tall kernel in bands of RB (super-)rows: the GEMM rows are ordered (band, column, row within the band), so
-        that a 256-row tile lies in one band (or two), and every band runs only the part of its window of output-gradient rows that
-        lies inside the column -- input row a receives W[j] dY[a - j] for 0 <= a - j < Ho only, the rest of the window is the zero
-        rows above and below (cpc_gemm_nt_args.k_ranges; (30,1) kernel on 63 rows: 53 % of the MACs of the full windows remain).
-        Returns (first super-row, number of bands, RB, ranges tensor, FLOPs) or None (RB = 0, or the geometry does not fit)."""
-        gin, G, kh = self.gin, self.G, self.kh
-        if RB <= 0:
-            return None
-        rows_alloc = gin.Ha // G
-        nrb = _ceil_div(self.nr, RB) * RB
+    def _bands(self):
+        """Data gradient of a tall kernel in bands of one (super-)row: the GEMM rows are ordered (band, column), so that a 256-row tile
+        lies in one band (or two), and every band runs only the part of its window of output-gradient rows that lies inside the column
+        -- input row a receives W[j] dY[a - j] for 0 <= a - j < Ho only, the rest of the window is the zero rows above and below
+        (cpc_gemm_nt_args.k_ranges; (30,1) kernel on 63 rows: 53 % of the MACs of the full windows remain).  The bands are the nr
+        (super-)rows from r0 on.  Returns (ranges tensor, FLOPs) or None (the geometry does not fit)."""
+        G, kh = self.G, self.kh
         bk = 64 if self.dt == torch.bfloat16 else 32
         Kd = (self.Rd if G > 1 else kh) * self.cout
-        if nrb > rows_alloc or Kd % bk:
+        if Kd % bk:
             return None
-        r0b = min(self.r0, rows_alloc - nrb)
         nst, ranges, stages = Kd // bk, [], 0
-        for i in range(nrb // RB):
-            first, last = r0b + i * RB, r0b + (i + 1) * RB - 1
-            lo, hi = max(0, (kh - 1) - G * last), min(kh + G - 1, self.Ho + kh - 1 - G * first)      # window rows [lo, hi) of the band
+        for row in range(self.r0, self.r0 + self.nr):
+            lo, hi = max(0, (kh - 1) - G * row), min(kh + G - 1, self.Ho + kh - 1 - G * row)      # window rows [lo, hi) of the band
             lo_s, hi_s = (lo * self.cout // bk, min(nst, _ceil_div(hi * self.cout, bk))) if hi > lo else (0, 1)
             ranges += [lo_s, hi_s]
             stages += hi_s - lo_s
-        if stages * 10 > 9 * nst * (nrb // RB) * self.nr // nrb:           # less than 10 % to gain: the plain column order reuses L2 better
+        if stages * 10 > 9 * nst * self.nr:           # less than 10 % to gain: the plain column order reuses L2 better
             return None
         t = torch.tensor(ranges, dtype=torch.int32, device=self.eng.device)
-        return r0b, nrb // RB, RB, t, 2.0 * self.ncol * RB * stages * bk * G * self.cin
+        return t, 2.0 * self.ncol * stages * bk * G * self.cin
 
     # ------------------------------------------------------------------
     def prepare(self):
@@ -378,21 +367,14 @@ class _Conv:
             Kg, Ng = self.Rw * self.cin, G * self.cout
             Hg = _ceil_div(self.Ho, G)
             bias_g = (_hip.ptr(self.bias_g) if self.bname else None) if not tangent else None
-            if self.valid_rows:
-                _hip.gemm_nt(gin.ptr(), _hip.ptr(self.w_fwd), y0.ptr(), self.ncol * Hg, Ng, Kg, G * self.cin, Kg, Ng, code, bias=bias_g, mask=mask,
-                             a_rpi=Hg, a_item=gin.Ha * self.cin, c_rpi=Hg, c_item=y0.Ha * self.cout, c_valid=Hg, flags=flags)
-            else:
-                _hip.gemm_nt(gin.ptr(), _hip.ptr(self.w_fwd), y0.ptr(), self.M // G, Ng, Kg, G * self.cin, Kg, Ng, code, bias=bias_g, mask=mask,
-                             c_rpi=gin.Ha // G, c_item=y0.Ha * self.cout, c_valid=Hg, flags=flags)
+            _hip.gemm_nt(gin.ptr(), _hip.ptr(self.w_fwd), y0.ptr(), self.ncol * Hg, Ng, Kg, G * self.cin, Kg, Ng, code, bias=bias_g, mask=mask,
+                         a_rpi=Hg, a_item=gin.Ha * self.cin, c_rpi=Hg, c_item=y0.Ha * self.cout, c_valid=Hg, flags=flags)
             if Hg * G > self.Ho:          # rows of the last super-row beyond the valid output
                 y0.t.view(-1, y0.Ha, self.cout)[:, self.Ho:Hg * G, :] = 0
-        elif self.mode == 'col' and self.valid_rows:
+        elif self.mode == 'col':
             _hip.gemm_nt(gin.ptr(), _hip.ptr(self.w_fwd), y0.ptr(), self.ncol * self.Ho, self.cout, self.K, self.cin, self.K, self.cout, code,
                          bias=bias, mask=mask, a_rpi=self.Ho, a_item=gin.Ha * self.cin, c_rpi=self.Ho, c_item=y0.Ha * self.cout,
                          c_valid=self.Ho, flags=flags)
-        elif self.mode == 'col':
-            _hip.gemm_nt(gin.ptr(), _hip.ptr(self.w_fwd), y0.ptr(), self.M, self.cout, self.K, self.cin, self.K, self.cout, code,
-                         bias=bias, mask=mask, c_rpi=gin.Ha, c_item=y0.Ha * self.cout, c_valid=self.Ho, flags=flags)
         elif self.gather:
             Kg = self.kw * self.seg
             taps = dict(k_taps=self.kw, k_tap_stride=self.seg, k_tap_stride_a=gin.Ha * self.cin) if self.kw > 1 else {}
@@ -427,8 +409,8 @@ class _Conv:
         # The weight-gradient GEMM reads the convolution's input and its output gradient, both final at this point, and nothing the
         # main stream does next depends on it: it goes to the side stream with its slab reduction, beside the data-gradient GEMM and
         # the HBM-bound BatchNorm / pooling passes of the layer below (the main queue was busy 18.4 of 18.5 ms per configs[2] step
-        # with the side queue idle for 16.8 of them).  CPC_WGRAD_STREAM=0 / a gradient-penalty step: GEMM on the main stream.
-        side_gemm = e.use_aux and getattr(e, "_gp_phase", 0) == 0 and os.environ.get("CPC_WGRAD_STREAM", "1") != "0"
+        # with the side queue idle for 16.8 of them).  switches.wgrad_stream off / a gradient-penalty step: GEMM on the main stream.
+        side_gemm = e.use_aux and e._gp_phase == 0 and switches.wgrad_stream()
 
         def staged(gemm, reduce):
             if side_gemm:
@@ -444,7 +426,7 @@ class _Conv:
             G = self.G
             Kg, Ng, Mg = self.Rw * self.cin, G * self.cout, self.Mw
             chunk = e._chunk(Mg, self.nsplit)
-            rows = dict(a_rpi=self.Hg, a_item=gin.Ha * self.cin, b_rpi=self.Hg, b_item=dy0.Ha * self.cout) if self.valid_rows else {}
+            rows = dict(a_rpi=self.Hg, a_item=gin.Ha * self.cin, b_rpi=self.Hg, b_item=dy0.Ha * self.cout)
 
             def reduce():
                 # slab[(r,c)][(dh,co)] = sum_R X[G R + r][c] dY[G R + dh][co]  ->  dW[co][c][j] = sum_dh slab[(j+dh, c)][(dh, co)]
@@ -457,7 +439,7 @@ class _Conv:
                                         m_chunk=chunk, slab_stride=Kg * Ng, flags=_hip.GEMM_OUT_F32, **rows), reduce)
         elif self.mode == 'col':
             chunk = e._chunk(self.Mw, self.nsplit)
-            rows = dict(a_rpi=self.Ho, a_item=gin.Ha * self.cin, b_rpi=self.Ho, b_item=dy0.Ha * self.cout) if self.valid_rows else {}
+            rows = dict(a_rpi=self.Ho, a_item=gin.Ha * self.cin, b_rpi=self.Ho, b_item=dy0.Ha * self.cout)
             staged(lambda: _hip.gemm_tn(gin.ptr(), dy0.ptr(), _hip.ptr(wslab), self.Mw, self.K, self.cout, self.cin, self.cout, self.cout, code,
                                         nsplit=self.nsplit, m_chunk=chunk, slab_stride=self.K * self.cout, flags=_hip.GEMM_OUT_F32, **rows),
                    lambda: _hip.call("cpc_reduce_conv_w", _hip.ptr(wslab), _hip.ptr(gw), self.cin, self.cout, self.kh, self.nsplit,
@@ -503,11 +485,11 @@ class _Conv:
 
     def _dgrad_bands(self, dy0: Grid, dst: Grid, Kd, mask_input):
         G, gin = self.G, self.gin
-        r0b, nb, RB, ranges, flops = self.bands
-        _hip.gemm_nt(dy0.ptr((r0b * G - (self.kh - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0b * G * self.cin), nb * self.ncol * RB,
-                     G * self.cin, Kd, G * self.cout, Kd, G * self.cin, self.code, mask=gin.ptr(r0b * G * self.cin) if mask_input else None,
-                     a_rpi=RB, a_item=dy0.Ha * self.cout, a_rpi2=self.ncol, a_item2=RB * G * self.cout,
-                     c_rpi=RB, c_item=dst.Ha * self.cin, c_valid=RB, c_rpi2=self.ncol, c_item2=RB * G * self.cin,
+        r0, (ranges, flops) = self.r0, self.bands
+        _hip.gemm_nt(dy0.ptr((r0 * G - (self.kh - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0 * G * self.cin), self.nr * self.ncol,
+                     G * self.cin, Kd, G * self.cout, Kd, G * self.cin, self.code, mask=gin.ptr(r0 * G * self.cin) if mask_input else None,
+                     a_rpi=1, a_item=dy0.Ha * self.cout, a_rpi2=self.ncol, a_item2=G * self.cout,
+                     c_rpi=1, c_item=dst.Ha * self.cin, c_valid=1, c_rpi2=self.ncol, c_item2=G * self.cin,
                      k_ranges=_hip.ptr(ranges), work=flops)
 
     def backward(self, din: Optional[Grid], accumulate=False, mask_input=False):
@@ -516,7 +498,7 @@ class _Conv:
         e, gin, dy0 = self.eng, self.gin, self.dy0
         g, code = e.model._grad, self.code
         gb = g[self.bname] if (self.bname and self.bname in g) else None
-        if gb is not None and self.bn_after is not None and self.bn_after.trained and os.environ.get("CPC_BN_BIAS_COLSUM", "0") != "1":
+        if gb is not None and self.bn_after is not None and self.bn_after.trained and not switches.bn_bias_colsum():
             gb.zero_()
             gb = None
         self._wgrad(gin, getattr(self, "col", None), dy0, g[self.wname], gb)
@@ -524,7 +506,6 @@ class _Conv:
             return
         if self.mode == 'col' and self.G > 1:
             G = self.G
-            Mg = self.M // G
             dst = din
             if accumulate:
                 if getattr(self, "_din_tmp", None) is None:
@@ -533,14 +514,11 @@ class _Conv:
             Kd = self.Rd * self.cout
             if self.bands is not None:
                 self._dgrad_bands(dy0, dst, Kd, mask_input)
-            elif self.valid_rows:
+            else:
                 r0, nr = self.r0, self.nr
                 _hip.gemm_nt(dy0.ptr((r0 * G - (self.kh - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0 * G * self.cin), self.ncol * nr,
                              G * self.cin, Kd, G * self.cout, Kd, G * self.cin, code, mask=gin.ptr(r0 * G * self.cin) if mask_input else None,
                              a_rpi=nr, a_item=dy0.Ha * self.cout, c_rpi=nr, c_item=dst.Ha * self.cin, c_valid=nr)
-            else:
-                _hip.gemm_nt(dy0.ptr(-(self.kh - 1) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(), Mg, G * self.cin, Kd, G * self.cout,
-                             Kd, G * self.cin, code, mask=gin.ptr() if mask_input else None)
             if accumulate:
                 _accumulate(din, dst)
         elif self.mode == 'col':
@@ -552,14 +530,11 @@ class _Conv:
                 dst = self._din_tmp
             if self.bands is not None:
                 self._dgrad_bands(dy0, dst, D * self.cout, mask_input)
-            elif self.valid_rows:
+            else:
                 r0, nr = self.r0, self.nr
                 _hip.gemm_nt(dy0.ptr((r0 - (D - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0 * self.cin), self.ncol * nr, self.cin,
                              D * self.cout, self.cout, D * self.cout, self.cin, code, mask=gin.ptr(r0 * self.cin) if mask_input else None,
                              a_rpi=nr, a_item=dy0.Ha * self.cout, c_rpi=nr, c_item=dst.Ha * self.cin, c_valid=nr)
-            else:
-                _hip.gemm_nt(dy0.ptr(-(D - 1) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(), self.M, self.cin, D * self.cout, self.cout,
-                             D * self.cout, self.cin, code, mask=gin.ptr() if mask_input else None)
             if accumulate:
                 _accumulate(din, dst)
         elif self.parity and not accumulate:
@@ -682,8 +657,7 @@ class _BatchNorm:
         # backward passes instead of the activation itself: 4 of their 14 bytes per element (bf16 grids; not in gradient-penalty
         # engines, whose passes call these kernels on other operands)
         self.abits = None
-        if (eng.dt == torch.bfloat16 and not self.x_f32 and self.C % 8 == 0 and not getattr(eng, "gp_capable", False) and
-                os.environ.get("CPC_BN_BITS", "1") != "0"):
+        if eng.dt == torch.bfloat16 and not self.x_f32 and self.C % 8 == 0 and not eng.gp_capable:
             self.abits = torch.zeros(a.rows * a.C // 8, device=eng.device, dtype=torch.uint8)
 
     def apply_residual(self, res: Grid, out: Grid, oh, ow, relu_out, r_f32, obits=None):
@@ -755,7 +729,7 @@ class _BatchNorm:
             _hip.call("cpc_bn_bwd_apply", da.ptr(), self.a.ptr(), _desc(self.a, self.a.desc), self.y0.ptr(), self.dy0.ptr(),
                       _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb),
                       float(self.y0.count), 1, 1 if self.trained else 0, self.x_f32, code)
-        gp = getattr(e, "_gp_phase", 0)
+        gp = e._gp_phase
         if gp == 1:          # first backward pass of a gradient-penalty step (seeds: the summed scores): keep sum q xhat
             if getattr(self, "s2", None) is None:
                 self.s2 = torch.empty_like(gw)
@@ -1014,7 +988,7 @@ class _Block:
         # block 0 in a training engine (no input gradient): convolution + BatchNorm + ReLU through the recomputing kernels of csrc/stem.hip
         self.stem = None
         if (in_f32 and first and has_bn and self.pool1 == 1 and not cfg.get('separable') and gin.top == 0 and
-                os.environ.get("CPC_STEM", "1") != "0" and
+                switches.stem() and
                 _hip.lib().cpc_stem_supported(gin.C, cfg['hidden_channels'], k1[0], k1[1], s1, gin.H, p1) == 1):
             self.a_a = Grid(gin.B, Wa1, Ha1, cfg['hidden_channels'], dev, dt, **a_geom)
             self.stem = _Stem(eng, f"{pre}main_modules.{i1}.weight", f"{pre}main_modules.{i1}.bias" if bias else None, mm[i1],
@@ -1076,7 +1050,7 @@ class _Block:
                 src, src_f32 = self.rp, in_f32
             self.stem_res = None
             if ('res_conv' in blk.index and src_f32 and first and blk.residual_modules[blk.index['res_conv']].padding == (0, 0) and
-                    src.C <= 2 and os.environ.get("CPC_STEM", "1") != "0" and cfg['out_channels'] % 8 == 0 and
+                    src.C <= 2 and switches.stem() and cfg['out_channels'] % 8 == 0 and
                     256 % (cfg['out_channels'] // 8) == 0 and cfg['out_channels'] <= 128):
                 ri = blk.index['res_conv']
                 self.stem_res = f"{pre}residual_modules.{ri}.weight"
@@ -1160,9 +1134,9 @@ class _Block:
                       _desc(self.a_a, self.a_a.desc), self.pool1, 0, code)
         self.conv_b.forward()
         # second BatchNorm + ReLU, residual add and the ReLU between blocks in one pass where nothing else reads the normalised branch
-        # (CPC_BN_RESIDUAL=0: two passes; the gradient penalty's tangent pass reads it)
+        # (switches.bn_residual off: two passes; the gradient penalty's tangent pass reads it)
         fuse = (self.bn_b is not None and self.blk.residual and self.pool2 == 1 and self.bn_b.abits is not None and
-                not getattr(e, "gp_capable", False) and self.main.C % 8 == 0 and os.environ.get("CPC_BN_RESIDUAL", "1") != "0")
+                not e.gp_capable and self.main.C % 8 == 0 and switches.bn_residual())
         self._fused_bwd = False
         if self.bn_b is not None:
             self.bn_b.forward(apply=not fuse)
@@ -1177,14 +1151,14 @@ class _Block:
                 self.res_conv.forward()
             if self.stem_res is not None:
                 # (fused backward for the first block: needs the ReLU behind the add, i.e. a block that is not the last one)
-                self._fused_bwd = fuse and self.stem_res.relu and os.environ.get("CPC_BN_RESIDUAL_BWD", "1") != "0"
+                self._fused_bwd = fuse and self.stem_res.relu
                 if self._fused_bwd and getattr(self, "obits", None) is None:
                     self.obits = torch.zeros(self.out.rows * self.out.C // 8, device=e.device, dtype=torch.uint8)
                 self.stem_res.forward(self.bn_b if fuse else None, self.obits if self._fused_bwd else None)
             elif fuse:
                 # (the backward pass folds the residual add into the BatchNorm's passes where the residual operand is a bf16 grid: it then
                 # needs the sign bits of the block output in place of the output itself)
-                self._fused_bwd = (not self.r_f32) and os.environ.get("CPC_BN_RESIDUAL_BWD", "1") != "0"
+                self._fused_bwd = not self.r_f32
                 if self._fused_bwd and not self.last and getattr(self, "obits", None) is None:
                     self.obits = torch.zeros(self.out.rows * self.out.C // 8, device=e.device, dtype=torch.uint8)
                 self.bn_b.apply_residual(self.res, self.out, self.oh, self.ow, 0 if self.last else 1, self.r_f32,
@@ -1312,7 +1286,7 @@ class ScalogramCPCEngine(CPCEngine):
         Wasserstein gradient penalty needs (loss_and_grads(..., gradient_penalty=factor))."""
         enc, ar = model.encoder, model.autoregressive_model
         self.gp_capable = bool(gradient_penalty)
-        self._twins, self._gp_phase = {}, 0
+        self._twins = {}
         self.model = model
         self.device = torch.device(device)
         self.dt = dtype
@@ -1375,11 +1349,11 @@ class ScalogramCPCEngine(CPCEngine):
     # Operand copies for the NEXT step: rebuilt on the side stream right after the step's last Adam launch (FusedAdam.after_update), beside
     # the next batch's CQT GEMMs, instead of on the main stream in front of the first convolution (0.4 ms of small launches per configs[2]
     # step).  The next prepare_weights() only waits for their event; any other change of the parameters (load_state_dict, a torch
-    # optimizer, the NaN guard's restore) changes _param_state() and the copies are rebuilt in place as before.  CPC_PREPARE_AHEAD=0: off.
+    # optimizer, the NaN guard's restore) changes _param_state() and the copies are rebuilt in place as before.  switches.prepare_ahead() turns it off.
     supports_prepare_ahead = True
 
     def prepare_ahead(self, lo, hi, final):
-        if final and self.ctx is not None and getattr(self.ctx, "ahead_ok", False) and self.use_aux and os.environ.get("CPC_PREPARE_AHEAD", "1") != "0":
+        if final and self.ctx is not None and getattr(self.ctx, "ahead_ok", False) and self.use_aux and switches.prepare_ahead():
             self._prepare_all_ahead()
 
     def _check_input(self, x):
@@ -1413,15 +1387,12 @@ class ScalogramCPCEngine(CPCEngine):
         # side stream), run once, behind the encoder's last block: from there to the first large data gradient (context network, loss,
         # the upper blocks' backward passes) the main queue holds short, latency-bound launches.  Measured on configs[2] (30 steps after
         # 15, one box): off 12.08 - 12.17 ms, in front of the step 12.25, after block 0 / 1 / 2 / 3: 12.15 / 12.04 / 12.00 / 11.84, behind
-        # the loss kernels 11.86; on a stream of its own at the default priority 11.88 - 12.25.  CPC_SIDE_JOB_BLOCK: after which block.
+        # the loss kernels 11.86; on a stream of its own at the default priority 11.88 - 12.25.
         job, self.side_job = getattr(self, "side_job", None), None
-        at = min(int(os.environ.get("CPC_SIDE_JOB_BLOCK", str(len(self.blocks) - 1))), len(self.blocks) - 1)
-        if job is not None and at < 0:
-            job()
-        for i, b in enumerate(self.blocks):
+        for b in self.blocks:
             b.forward()
-            if job is not None and i == at:
-                job()
+        if job is not None:
+            job()
         if self.top_grid is not None:
             self.top_grid.t.view(self.B, self.T, self.E).copy_(self._row0(self.blocks[-1].out))
 
@@ -1722,8 +1693,8 @@ class _ArBlock:
                       self.pool, 0, code)
         self.conv.forward()
         # BatchNorm1d + ReLU and the residual add in one pass where nothing else reads the normalised branch (see _Block.forward)
-        fuse = (self.bn is not None and self.residual and self.bn.abits is not None and not getattr(self.eng, "gp_capable", False) and
-                self.main.C % 8 == 0 and os.environ.get("CPC_BN_RESIDUAL", "1") != "0")
+        fuse = (self.bn is not None and self.residual and self.bn.abits is not None and not self.eng.gp_capable and
+                self.main.C % 8 == 0 and switches.bn_residual())
         if self.bn is not None:
             self.bn.forward(apply=not fuse)
         if self.residual:
@@ -1732,7 +1703,7 @@ class _ArBlock:
                           self.pool * self.stride, 0, code)
             if self.res_conv is not None:
                 self.res_conv.forward()
-            self._fused_bwd = fuse and os.environ.get("CPC_BN_RESIDUAL_BWD", "1") != "0"
+            self._fused_bwd = fuse
             if fuse:
                 self.bn.apply_residual(self.res, self.out, self.oh, 0, 0, 0)
             else:

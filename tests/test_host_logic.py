@@ -517,3 +517,29 @@ def test_bench_dump_outputs_are_bounded_and_repeatable(tmp_path):
         a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
         assert a.dtype == np.float32 and np.array_equal(a, b), f
     assert np.isin(np.load(tmp_path / "a" / "grads.npy"), g).all()
+
+
+KEPT_SWITCHES = {"CPC_WGRAD_STREAM", "CPC_PREPARE_AHEAD", "CPC_PREPROCESS_AHEAD", "CPC_FUSED_SCORE", "CPC_STEM", "CPC_BN_RESIDUAL",
+                 "CPC_CONV_GATHER", "CPC_BN_BIAS_COLSUM"}
+
+
+def test_environment_is_read_in_one_module_and_only_for_the_kept_switches():
+    """The package reads the process environment in switches.py alone, that module names exactly the eight switches something outside
+    the package sets, and no other CPC_* environment name survives anywhere in the package's Python files, comments included (the
+    names of GEMM flags and C constants, and the historical 'CPC_PROBE runs' of engine.py's _alloc_encoder comment, are not switches)."""
+    pkg = os.path.dirname(os.path.abspath(_hip.__file__))
+    files = {os.path.join(d, f) for d in (pkg, os.path.dirname(os.path.abspath(cpc_audio_amd.__file__))) for f in os.listdir(d) if f.endswith(".py")}
+    assert os.path.join(pkg, "switches.py") in files and len(files) > 10
+    not_a_switch = re.compile(r"CPC_(GEMM_[A-Z0-9_]+|F32|BF16|DTYPE_[A-Z0-9_]+|EINVAL)$")
+    for path in sorted(files):
+        text = open(path).read()
+        name = os.path.relpath(path, ROOT)
+        if path == os.path.join(pkg, "switches.py"):
+            assert set(re.findall(r"CPC_[A-Z0-9_]+", text)) == KEPT_SWITCHES
+            continue
+        assert not re.search(r"environ|getenv", text), f"{name} reads the environment: that belongs in switches.py"
+        if path == os.path.join(pkg, "engine.py"):
+            assert text.count("CPC_PROBE") <= 1
+            text = text.replace("CPC_PROBE runs", "")
+        names = {n for n in re.findall(r"CPC_[A-Z0-9_]+", text) if not not_a_switch.match(n)}
+        assert names <= KEPT_SWITCHES, f"{name} names {sorted(names - KEPT_SWITCHES)}"

@@ -1019,7 +1019,7 @@ def test_tall_kernel_convolutions_at_real_shapes_against_torch(dtype):
     tall = [b.conv_b for b in eng.blocks[:3]]
     assert [c.kh for c in tall] == [64, 30, 15] and all(c.mode == "col" for c in tall)
     if dtype == "bf16":
-        assert [c.G for c in tall] == [8, 2, 1] and all(c.valid_rows for c in tall) and tall[0].bands is not None and tall[1].bands is not None
+        assert [c.G for c in tall] == [8, 2, 1] and tall[0].bands is not None and tall[1].bands is not None
     tol = 2e-5 if dtype == "fp32" else 1.5e-2
     rnd = (lambda t: t) if dtype == "fp32" else (lambda t: t.bfloat16().float())
 

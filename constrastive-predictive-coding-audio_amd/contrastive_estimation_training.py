@@ -25,6 +25,7 @@ import torch.utils.data
 from .audio_model import *          # noqa: F401,F403  (the reference re-exports the model names from here)
 from .audio_dataset import FileBatchSampler
 from . import switches
+from .sampled_negatives import check_negatives, sampled_negative_mask          # noqa: F401  (public: the host restatement)
 
 
 def _need_gpu(t, what):
@@ -229,6 +230,39 @@ class _InfoNCE(torch.autograd.Function):
         return d.to(dtype), None, None
 
 
+class _SampledInfoNCE(torch.autograd.Function):
+    """_InfoNCE's default branch over n_neg seeded negatives per target (cpc_nce_loss_sampled; DESIGN.md, "Sampled negatives"): the
+    generic route's loss when ContrastiveEstimationTrainer.num_negatives is set.  Same returns as _InfoNCE."""
+
+    @staticmethod
+    def forward(ctx, scores4, regularization, n_neg, seed, draw):
+        import ctypes as C
+        from . import _hip
+        _need_gpu(scores4, "the InfoNCE loss over sampled negatives")
+        B, K = scores4.shape[0], scores4.shape[1]
+        n_neg = check_negatives(B, n_neg)
+        S, ld = _score_layout(scores4.detach(), False)
+        dev, f32 = S.device, torch.float32
+        out = torch.zeros(8, device=dev, dtype=f32)
+        dS, dST = torch.zeros_like(S), torch.zeros_like(S)
+        ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(B, K)), device=dev, dtype=f32)
+        _hip.call("cpc_nce_loss_sampled", _hip.ptr(S), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
+                  C.c_float(regularization), n_neg, C.c_ulonglong(int(seed) & (2 ** 64 - 1)), C.c_ulonglong(int(draw) & (2 ** 64 - 1)),
+                  _hip.F32)
+        ctx.save_for_backward(dS)
+        ctx.meta = (B, K, scores4.dtype)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_out):
+        (dS,) = ctx.saved_tensors
+        B, K, dtype = ctx.meta
+        d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
+        torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
+        return d.to(dtype), None, None, None, None
+
+
 class ContrastiveEstimationTrainer:
     def __init__(self, model, dataset, logger=None, device=None,
                  regularization=1., validation_set=None, test_task_set=None, prediction_noise=0.01,
@@ -270,6 +304,12 @@ class ContrastiveEstimationTrainer:
         # Not in the reference's signature: under torch.distributed take the InfoNCE loss over the batches of ALL ranks — what
         # the reference's nn.DataParallel wrap computes — instead of per-GPU negatives (engine.GlobalNegatives).
         self.global_negatives = False
+        # Not in the reference's signature: contrast every target against num_negatives seeded negatives of the batch instead of all
+        # batch_size - 1 (None: the reference's in-batch loss).  Step i draws the sets of (negative_seed, draw = i): a run continued
+        # with continue_training_at_step resumes the same stream, and sampled_negative_mask(...) restates any step's sets on the host.
+        # Default loss branch only; validate() stays in-batch, as the reference measures accuracy.
+        self.num_negatives = None
+        self.negative_seed = 0
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
         self.preprocess_ahead = True
         self.verbose = True
@@ -307,6 +347,25 @@ class ContrastiveEstimationTrainer:
         """difference_score_function + Adam also runs the whole step on the engine (cpc_diff_scores and its backward, FusedAdam, the
         device NaN guard); under global negatives it keeps the generic route."""
         return self.score_function is difference_score_function and self.optimizer is torch.optim.Adam and not self.global_negatives
+
+    def _check_negatives(self, batch_size):
+        """Up-front checks of num_negatives (before any GPU work): ValueError unless 1 <= N <= batch_size - 1, NotImplementedError
+        for what the sampled loss does not cover."""
+        if self.num_negatives is None:
+            return
+        check_negatives(batch_size, self.num_negatives)
+        if self.score_over_all_timesteps:
+            raise NotImplementedError("num_negatives: the sampler is defined for score_over_all_timesteps=False only (it indexes the "
+                                      "batch items of one prediction step, not the (item, step) pairs of the all-timesteps branch)")
+        if self.wasserstein_gradient_penalty:
+            raise NotImplementedError("num_negatives: wasserstein_gradient_penalty runs the dense loss kernels in its tangent passes; "
+                                      "sampled negatives are not carried through them")
+        if self.use_graph:
+            raise NotImplementedError("num_negatives: use_graph replays one captured step, but the draw counter changes every step and "
+                                      "lives on the host (like dropout's seed)")
+        if self.global_negatives:
+            raise NotImplementedError("num_negatives: global_negatives contrasts against the gathered batches of all ranks; the sampler "
+                                      "draws from the rank's own batch only")
 
     def _score_kind(self):
         if self.score_function is difference_score_function:
@@ -374,6 +433,7 @@ class ContrastiveEstimationTrainer:
         """Same contract as the reference's train (:74-176): returns ``prof`` (None unless profile=True) when max_steps is
         reached, None on a NaN loss or when the epochs are exhausted.  ``batch_size`` is the per-process batch; under
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
+        self._check_negatives(batch_size)
         device = self._device()
         rank, world = self._world()
         self.model.train()
@@ -568,7 +628,7 @@ class ContrastiveEstimationTrainer:
                                                      all_timesteps=bool(self.score_over_all_timesteps),
                                                      grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
                                                      global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
-                                                     score=kind)
+                                                     score=kind, **self._negatives_kw())
                         if sync is not None:
                             sync.finish()
                         # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
@@ -600,13 +660,23 @@ class ContrastiveEstimationTrainer:
             return nan_return(nan_step)
         return None
 
+    def _negatives_kw(self):
+        """{} for the in-batch loss; else the step's negatives = (num_negatives, negative_seed, draw = training_step) — the same
+        on every rank of a data-parallel run, each applying it to its own shard."""
+        if self.num_negatives is None:
+            return {}
+        return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
+
     def _generic_step(self, batch, batch_size, optimizer, world):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
         the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133)."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
-        loss, out = _InfoNCE.apply(scores, bool(self.score_over_all_timesteps), float(self.regularization))
+        if self.num_negatives is None:
+            loss, out = _InfoNCE.apply(scores, bool(self.score_over_all_timesteps), float(self.regularization))
+        else:
+            loss, out = _SampledInfoNCE.apply(scores, float(self.regularization), *self._negatives_kw()["negatives"])
         nan = out[5:6].clone()
         if world > 1:          # every rank has its own loss: all ranks leave at the same step
             import torch.distributed as dist
@@ -628,7 +698,8 @@ class ContrastiveEstimationTrainer:
         """Reference validate (:178-269): per-step loss, per-step arg-max accuracy, mean score and the mutual-information lower
         bound log(n) - loss over the validation set (eval mode, FileBatchSampler(seed=0, file_batch_size=8)).  The per-batch
         quantities come from cpc_nce_eval on the train step's own score matrices and are summed on the device; the host reads
-        2 K + 1 numbers once, after the last batch."""
+        2 K + 1 numbers once, after the last batch.  Always in-batch, as the reference measures accuracy: num_negatives does not
+        enter here."""
         import ctypes as C
         from . import _hip
         if self.validation_set is None:

@@ -667,6 +667,177 @@ __global__ __launch_bounds__(256) void nce_fused_finalize_kernel(const float* __
     if (bad != 0.f) out[6] = 1.f;
 }
 
+// ---- sampled negatives: the equal-step loss over N seeded negatives per target (include/cpc_hip.h, cpc_nce_loss_sampled) ----
+// Every target column (k, b') keeps its own row b' and the N rows b != b' with the smallest (key, b), key a counter-based hash of
+// (seed, draw, k, b', b) with the arithmetic of drop_hash (attn.hip).  Nothing of size K B B is stored: the column pass finds each
+// column's N-th smallest composite (key << 32 | b) and leaves it as a threshold, the gradient pass recomputes an element's key and
+// compares.  ONE WAVE PER COLUMN, a lane holding rows lane, lane + 64, ...: the N-th smallest is found bit by bit from the top
+// (count of keys <= candidate through ballots, 32 steps; then 10 steps over the row index among the rows that tie with the
+// threshold key), i.e. 42 x ceil(B / 64) wave-wide compares per column and neither LDS nor a barrier — rank counting costs B^2 / 64
+// = 1024 wave-wide 64-bit compares per column at B = 256, an LDS bitonic sort 36 barrier-separated stages.
+constexpr int NSM_MAXB = 1024;      // 16 rows per lane; the row index takes the low 10 bits of the tie search
+constexpr int NSM_COLS = 4;         // columns (waves) per workgroup of the column pass
+constexpr unsigned long long NSM_DRAW = 0x632BE59BD9B4E019ull, NSM_STEP = 0x9E3779B97F4A7C15ull, NSM_IDX = 0xD1B54A32D192ED03ull;
+
+// what a column's keys share: seed + NSM_DRAW draw + NSM_STEP (k + 1) + (b' B) NSM_IDX   (mod 2^64)
+__device__ __forceinline__ unsigned long long nsm_col_base(unsigned long long seed, unsigned long long draw, int k, int bp, int B) {
+    return seed + NSM_DRAW * draw + NSM_STEP * (unsigned long long)(k + 1) + (unsigned long long)bp * (unsigned long long)B * NSM_IDX;
+}
+__device__ __forceinline__ unsigned nsm_key(unsigned long long col_base, int b) {
+    unsigned long long z = col_base + (unsigned long long)b * NSM_IDX;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (unsigned)(z >> 32);
+}
+__device__ __forceinline__ bool nsm_member(unsigned long long col_base, int b, int bp, unsigned long long thr) {
+    return b == bp || (((unsigned long long)nsm_key(col_base, b) << 32) | (unsigned)b) <= thr;
+}
+
+// The selection routine of both entry points.  Called by all 64 lanes of a wave for column (k, b'): fills key[h] for row
+// lane + 64 h and returns the N-th smallest composite among the rows b < B, b != b' (at least n_neg of them exist: n_neg <= B - 1).
+template <int H>
+__device__ __forceinline__ unsigned long long nsm_select(unsigned long long col_base, int lane, int bp, int B, int n_neg,
+                                                         unsigned (&key)[H]) {
+    unsigned ok = 0;            // bit h: row lane + 64 h takes part in the selection
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int row = lane + 64 * h;
+        key[h] = nsm_key(col_base, row);
+        if (row < B && row != bp) ok |= 1u << h;
+    }
+    unsigned tk = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = tk | ((1u << bit) - 1u);
+        int cnt = 0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] <= cand));
+        if (cnt < n_neg) tk |= 1u << bit;
+    }
+    int below = 0;
+#pragma unroll
+    for (int h = 0; h < H; ++h) below += __popcll(__ballot(((ok >> h) & 1u) && key[h] < tk));
+    const int need = n_neg - below;             // >= 1 rows with key == tk belong, the ones with the smallest index
+    unsigned tb = 0;
+    for (int bit = 9; bit >= 0; --bit) {
+        const unsigned cand = tb | ((1u << bit) - 1u);
+        int cnt = 0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] == tk && (unsigned)(lane + 64 * h) <= cand));
+        if (cnt < need) tb |= 1u << bit;
+    }
+    return ((unsigned long long)tk << 32) | tb;
+}
+
+// Column pass of one wave: threshold of column col = k B + b', and the log-sum-exp over its candidates.  The wave-wide max and sum
+// are xor butterflies (every lane ends with the same bits), the lane's own sum runs over h in order: nothing depends on timing.
+template <int H>
+__device__ __forceinline__ void nsm_col_body(const float* __restrict__ S, unsigned long long* __restrict__ thr, float* __restrict__ lse,
+                                             int B, int ld, int softplus, int n_neg, unsigned long long seed, unsigned long long draw,
+                                             int col) {
+    const int lane = threadIdx.x & 63;
+    const int k = col / B, bp = col % B;
+    const float* cp = S + (long long)k * B * ld + bp;
+    float v[H];
+    unsigned key[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) v[h] = (lane + 64 * h < B) ? cp[(long long)(lane + 64 * h) * ld] : 0.f;      // in flight during the selection
+    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
+    const unsigned long long t = nsm_select<H>(base, lane, bp, B, n_neg, key);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int row = lane + 64 * h;
+        const bool in = row < B && (row == bp || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t);
+        v[h] = in ? score_tf(v[h], softplus) : -INFINITY;
+        mx = fmaxf(mx, v[h]);
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int h = 0; h < H; ++h) sum += expf(v[h] - mx);          // a NaN score: dropped by fmaxf, carried by the sum, as nce_col_body does
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) {
+        thr[col] = t;
+        lse[col] = mx + logf(sum);
+    }
+}
+
+// Column pass + pair means in ONE launch, as nce_col_mean_kernel: the first ncb workgroups take NSM_COLS columns each, the rest the
+// pairs (nce_mean_body: the regulariser, the max score and the valid scores run over ALL scores and do not know about the sampling).
+template <int KT, int H>
+__global__ __launch_bounds__(256) void nce_sampled_col_mean_kernel(const float* __restrict__ S, unsigned long long* __restrict__ thr,
+                                                                   float* __restrict__ lse, float* __restrict__ mean,
+                                                                   float* __restrict__ pairp, int B, int K, int ld, int softplus, int n_neg,
+                                                                   unsigned long long seed, unsigned long long draw, int ncb) {
+    if ((int)blockIdx.x < ncb) {
+        const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
+        if (col < K * B) nsm_col_body<H>(S, thr, lse, B, ld, softplus, n_neg, seed, draw, col);          // (wave-uniform)
+    } else {
+        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb);
+    }
+}
+
+// nce_grad_kernel with the candidate test: exp(sp - lse) only where row b is a candidate of column (k, b'); workgroup (0, 0, 0) also
+// reduces the loss scalars (the column sums are the K B log-sum-exps themselves, in nce_finalize_body's fixed order).
+template <typename T>
+__global__ __launch_bounds__(256) void nce_sampled_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
+                                                               const unsigned long long* __restrict__ thr, const float* __restrict__ mean,
+                                                               T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld, int softplus,
+                                                               float reg, unsigned long long seed, unsigned long long draw,
+                                                               const float* __restrict__ pairp, int npair, float* __restrict__ out) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
+    const int bp0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
+    const float inv_bk = 1.f / ((float)B * (float)K);
+    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
+    const int k = blockIdx.z;
+    const int bp = bp0 + tx;
+    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
+    const unsigned long long t = bp < B ? thr[k * B + bp] : 0ull;
+    const float l = bp < B ? lse[k * B + bp] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = b0 + ty + 8 * r;
+        float g = 0.f;
+        if (b < B && bp < B) {
+            const float x = S[((long long)k * B + b) * ld + bp];
+            const float sp = score_tf(x, softplus);
+            float dsp = reg_c * mean[(long long)b * ld + bp];
+            if (nsm_member(base, b, bp, t)) dsp += expf(sp - l) * inv_bk;
+            if (b == bp) dsp -= inv_bk;
+            g = dsp * score_grad(x, softplus);
+        }
+        if (b < B && bp < ld) dS[((long long)k * B + b) * ld + bp] = from_f32<T>(g);
+        tile[ty + 8 * r][tx] = g;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int bq = bp0 + ty + 8 * r, b = b0 + tx;
+        if (b < ld && bq < B) dST[((long long)k * B + bq) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(lse, K * B, pairp, npair, out, B, K, reg);
+}
+
+// mask[k][b][b'] = 1 where row b is a candidate of column (k, b') (its own row included), from the same selection routine.
+template <int H>
+__global__ __launch_bounds__(256) void nce_sample_mask_kernel(unsigned char* __restrict__ mask, int B, int K, int n_neg,
+                                                              unsigned long long seed, unsigned long long draw) {
+    const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
+    if (col >= K * B) return;                   // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    const int k = col / B, bp = col % B;
+    unsigned key[H];
+    const unsigned long long t = nsm_select<H>(nsm_col_base(seed, draw, k, bp, B), lane, bp, B, n_neg, key);
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int row = lane + 64 * h;
+        if (row < B)
+            mask[((long long)k * B + row) * B + bp] = (row == bp || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t) ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 int launch_nce_lse_merge(const float* pm, const float* ps, int nparts, int ncols, int softplus, float nrows, float* lse, float* colp,
@@ -738,6 +909,56 @@ int launch_nce(const float* S, void* dS, void* dST, float* out, float* workspace
                            ld, softplus, reg, colp, ncol, gradp, nmb, out);
     else
         return CPC_EINVAL;
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+// ---- sampled negatives ----
+// workspace: thresholds [K][B] (64 bits each, first: the workspace must be 8-byte aligned) + lse [K][B] + pair partials
+// [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7]
+long long nce_sampled_workspace_floats(int B, int K) {
+    if (B <= 0 || K <= 0) return 0;
+    const long long nmb = ((long long)B * B + 255) / 256;
+    return 3LL * K * B + 3 * nmb + (long long)B * (B + 8);
+}
+
+int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
+                       int n_neg, unsigned long long seed, unsigned long long draw, int dtype, hipStream_t stream) {
+    if (B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
+    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+    unsigned long long* thr = (unsigned long long*)workspace;
+    float* lse = workspace + 2LL * K * B;
+    float* pairp = lse + (long long)K * B;
+    const int nmb = (int)(((long long)B * B + 255) / 256);
+    float* mean = pairp + 3LL * nmb;
+    const int ncb = (K * B + NSM_COLS - 1) / NSM_COLS;
+    const int nb = (ld + 31) / 32;
+    const dim3 g1(ncb + nmb);
+#define NSM_COL(KT, H) \
+    hipLaunchKernelGGL((nce_sampled_col_mean_kernel<KT, H>), g1, dim3(256), 0, stream, S, thr, lse, mean, pairp, B, K, ld, softplus, n_neg, \
+                       seed, draw, ncb)
+    if (B <= 256) {
+        if (K == 12) NSM_COL(12, 4); else if (K == 16) NSM_COL(16, 4); else NSM_COL(0, 4);
+    } else {
+        if (K == 12) NSM_COL(12, 16); else if (K == 16) NSM_COL(16, 16); else NSM_COL(0, 16);
+    }
+#undef NSM_COL
+    if (dtype == CPC_DTYPE_BF16)
+        hipLaunchKernelGGL((nce_sampled_grad_kernel<bf16_t>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (bf16_t*)dS,
+                           (bf16_t*)dST, B, K, ld, softplus, reg, seed, draw, pairp, nmb, out);
+    else
+        hipLaunchKernelGGL((nce_sampled_grad_kernel<float>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (float*)dS,
+                           (float*)dST, B, K, ld, softplus, reg, seed, draw, pairp, nmb, out);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw,
+                           hipStream_t stream) {
+    if (!mask || B <= 1 || B > NSM_MAXB || K <= 0 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
+    const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
+    if (B <= 256) hipLaunchKernelGGL(nce_sample_mask_kernel<4>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
+    else hipLaunchKernelGGL(nce_sample_mask_kernel<16>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }

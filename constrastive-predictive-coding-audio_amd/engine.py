@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _hip, switches
+from .sampled_negatives import check_negatives
 
 
 _SIDE_STREAMS = {}
@@ -38,6 +39,28 @@ def score_kind(softplus: bool, score: Optional[str] = None) -> str:
     if score not in SCORE_KINDS:
         raise ValueError(f"score must be one of {SCORE_KINDS}, got {score!r}")
     return score
+
+
+def check_negatives_supported(negatives, all_timesteps=False, global_negatives=None, gradient_penalty=None):
+    """Sampled negatives (``negatives = (n_neg, seed, draw)``) exist for the default loss branch on one process's own batch; what
+    they do not cover is refused here, before any launch."""
+    if negatives is None:
+        return
+    if all_timesteps:
+        raise NotImplementedError("sampled negatives are defined for score_over_all_timesteps=False only: the all-timesteps branch "
+                                  "contrasts every (item, step) pair, and no sampler over that set exists")
+    if global_negatives is not None:
+        raise NotImplementedError("sampled negatives draw from the process's own batch; with a global_negatives object the candidates "
+                                  "would span the gathered batches of all ranks, which the sampler does not index")
+    if gradient_penalty is not None:
+        raise NotImplementedError("the gradient penalty's tangent passes run the dense loss kernels; sampled negatives are not "
+                                  "carried through them")
+
+
+def normalize_negatives(negatives, B):
+    """(n_neg, seed, draw) as Python ints the C ABI takes (seed and draw modulo 2^64); ValueError unless 1 <= n_neg <= B - 1."""
+    n_neg, seed, draw = negatives
+    return check_negatives(B, n_neg), int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
 
 
 def side_stream(device):
@@ -546,21 +569,38 @@ class CPCEngine:
                      b_rpi=K, b_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
         return 2.0 * R * R * E
 
-    def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None):
+    def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, negatives=None):
         """Equal-step scores, InfoNCE loss + regulariser, and d loss / d (predicted_z, targets).
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
         (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs).
-        ``score``: see score_kind; "difference" runs _diff_forward_backward."""
+        ``score``: see score_kind; "difference" runs _diff_forward_backward.
+        ``negatives``: None, or (n_neg, seed, draw) — every target is contrasted against n_neg seeded negatives instead of the
+        whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask)."""
         if score_kind(softplus, score) == "difference":
-            return self._diff_forward_backward(False, regularization)
+            return self._diff_forward_backward(False, regularization, negatives)
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         top, dtop = self.act[-1], self.dact[-1]
+        if negatives is not None:
+            negatives = normalize_negatives(negatives, B)
         self.score_gemm()
-        _hip.call("cpc_nce_loss", _hip.ptr(self.S), _hip.ptr(self.dS), _hip.ptr(self.dST), _hip.ptr(self.nce_out),
-                  _hip.ptr(self.nce_ws), B, K, ld, 1 if softplus else 0, C.c_float(regularization), code)
+        if negatives is None:
+            _hip.call("cpc_nce_loss", _hip.ptr(self.S), _hip.ptr(self.dS), _hip.ptr(self.dST), _hip.ptr(self.nce_out),
+                      _hip.ptr(self.nce_ws), B, K, ld, 1 if softplus else 0, C.c_float(regularization), code)
+        else:
+            self._nce_sampled(self.S, self.dS, self.dST, 1 if softplus else 0, regularization, negatives)
         self._score_grads(self.dS, self.dST, self.pred, top, self.dpred, dtop)
+
+    def _nce_sampled(self, S, dS, dST, softplus: int, regularization: float, negatives):
+        """cpc_nce_loss_sampled in place of cpc_nce_loss (same buffers and layouts; its workspace is allocated on first use)."""
+        n_neg, seed, draw = negatives
+        if getattr(self, "nce_sampled_ws", None) is None:
+            self.nce_sampled_ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(self.B, self.K)), device=self.device,
+                                              dtype=torch.float32)
+        P = _hip.ptr
+        _hip.call("cpc_nce_loss_sampled", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_sampled_ws), self.B, self.K, self.ldS,
+                  softplus, C.c_float(regularization), n_neg, C.c_ulonglong(seed), C.c_ulonglong(draw), self.code)
 
     def _score_grads(self, W, WT, pred, top, out_pred, out_top):
         """The two contractions behind d loss / d (predicted_z, targets) of the default branch, for any coefficients W[k][b][b']
@@ -719,12 +759,15 @@ class CPCEngine:
                   code, work=work)
         return work
 
-    def _diff_forward_backward(self, all_timesteps: bool, regularization: float):
+    def _diff_forward_backward(self, all_timesteps: bool, regularization: float, negatives=None):
         """InfoNCE loss + regulariser on difference scores and d loss / d (predicted_z, targets).  The loss kernels take the scores
         as linear scores (softplus = 0, as contrastive_estimation_training._InfoNCE does); with d = |p - t|^2 and s = 1 / d,
         d loss / d d = -g s^2 for g = d loss / d s, so the gradient is the linear score's two contractions with G = 2 g s^2
         minus the rank-1 terms (row / column sums of G) * (p / t): cpc_diff_scores_bwd, _score_grads(_all), cpc_diff_scores_rank1.
         In bf16 storage G is rounded to bf16 (the operand type of the contractions) and its sums are taken of the rounded values."""
+        if negatives is not None:
+            check_negatives_supported(negatives, all_timesteps)
+            negatives = normalize_negatives(negatives, self.B)
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
         top, dtop = self.act[-1], self.dact[-1]
@@ -747,7 +790,10 @@ class CPCEngine:
                 self.ST = torch.zeros_like(self.S)
             S, ST, dS, dST = self.S, self.ST, self.dS, self.dST
             self.diff_scores(S, ST)
-            _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_ws), B, K, ld, 0, C.c_float(regularization), code)
+            if negatives is None:
+                _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_ws), B, K, ld, 0, C.c_float(regularization), code)
+            else:
+                self._nce_sampled(S, dS, dST, 0, regularization, negatives)
             _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), B, B, ld, C.c_longlong(B * ld), K, code)
             self._score_grads(dS, dST, self.pred, top, self.dpred, dtop)
         # mu / nu are indexed like predicted_z's and the targets' (b, k) rows in both branches
@@ -1009,14 +1055,18 @@ class CPCEngine:
 
     # ------------------------------------------------------------------------------------------ whole step
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
-                       global_negatives=None, after_loss=None, score: Optional[str] = None):
+                       global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None):
         """Forward + loss + backward; returns the device tensor [loss, max_score, -mean valid, mean lse, reg, NaN indicator of
         this step, sticky NaN flag, -] (no sync; include/cpc_hip.h, cpc_nce_loss).
         ``global_negatives``: a GlobalNegatives object — the loss is then taken over the batches of ALL ranks.
         ``after_loss(nce_out)`` is called once the loss kernels are queued and before the backward pass is: data-parallel runs
         start the reduction of the NaN flag over the ranks there (GradAllReduce.reduce_flag).
-        ``score``: "softplus" | "linear" | "difference" (score_kind; None: the ``softplus`` flag decides)."""
+        ``score``: "softplus" | "linear" | "difference" (score_kind; None: the ``softplus`` flag decides).
+        ``negatives``: None, or (n_neg, seed, draw): n_neg seeded negatives per target (nce_forward_backward); default branch only."""
         kind = score_kind(softplus, score)
+        if negatives is not None:
+            check_negatives_supported(negatives, all_timesteps, global_negatives)
+            negatives = normalize_negatives(negatives, self.B)
         if kind == "difference" and global_negatives is not None:
             raise NotImplementedError("difference scores under global negatives are not on the HIP path: the trainer takes the generic "
                                       "route there (contrastive_estimation_training.difference_score_function)")
@@ -1026,7 +1076,7 @@ class CPCEngine:
         elif all_timesteps:
             self.nce_all_forward_backward(softplus, regularization, score=kind)
         else:
-            self.nce_forward_backward(softplus, regularization, score=kind)
+            self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives)
         if after_loss is not None:
             after_loss(self.nce_out)
         self.backward(x, grad_ready_hook=grad_ready_hook)
@@ -2357,7 +2407,11 @@ class GraphedStep:
     launch overhead.  Kept as an option for hosts with slower launch paths.  Requirements: single process (no collective inside the graph), no host-side per-step state
     (dropout seeds)."""
 
-    def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None):
+    def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None,
+                 negatives=None):
+        if negatives is not None:
+            raise NotImplementedError("sampled negatives draw a new set per step from a host-side counter (like dropout's seed), which a "
+                                      "captured graph cannot replay")
         if opt.state is None:
             raise ValueError("GraphedStep needs FusedAdam(device_step=True)")
         ctx = eng.ctx

@@ -48,6 +48,8 @@ extern "C" {
  *    cpc_attn128_bwd, cpc_attn128_tangent, cpc_attn128_gp.
  *    Added later under 9 (backward compatible, no entry point added or changed): cpc_gru_tape_elems, cpc_gru_fwd, cpc_gru_fwd_h0,
  *    cpc_gru_bwd, cpc_gru_gp_fwd and cpc_gru_gp_bwd accept hidden sizes up to 512 (were 256).
+ *    Added later under 9 (backward compatible, no entry point changed): the loss over sampled negatives
+ *    cpc_nce_sampled_workspace_floats, cpc_nce_loss_sampled, cpc_nce_sample_mask.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -568,6 +570,23 @@ int cpc_gru_set_streaming(int on);
 long long cpc_nce_workspace_floats(int B, int K);
 int cpc_nce_loss(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
                  float regularization, int dtype, void* stream);
+
+/* The same loss over N SAMPLED negatives per target (not in the reference; DESIGN.md, "Sampled negatives"): column (k, b') runs its
+ * log-sum-exp over C(k,b') = {b'} + Neg(k,b') instead of all B rows, Neg the n_neg rows b != b' with the smallest (key, b),
+ *   s = seed + 0x632BE59BD9B4E019 draw;  z = s + 0x9E3779B97F4A7C15 (k + 1) + (b' B + b) 0xD1B54A32D192ED03;
+ *   z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;  z ^= z >> 31;  key = z >> 32      (all mod 2^64)
+ * — a pure function of its arguments: the same (seed, draw) selects the same rows on every device and launch geometry.
+ *   loss = -mean valid + mean_{k,b'} logsumexp_{b in C} sp + reg mean_{b,b'} (mean_k sp)^2        (regulariser over ALL scores)
+ *   dsp[k][b][b'] = ([b in C(k,b')] exp(sp - lse[k][b']) - [b == b']) / (B K) + 2 reg / (B^2 K) mean_k sp[k][b][b']
+ * S, dS, dST, out[8], ld, softplus, dtype and the pad-column zeros exactly as cpc_nce_loss (out[1] stays the max over all scores);
+ * n_neg == B - 1 is cpc_nce_loss's loss.  workspace: cpc_nce_sampled_workspace_floats(B,K) f32, 8-byte aligned.
+ * Limits: 2 <= B <= 1024, 1 <= n_neg <= B - 1; CPC_EINVAL otherwise, for a null pointer and for a dtype other than f32 / bf16.
+ * cpc_nce_sample_mask writes the candidate sets themselves, by the same device selection routine: mask[k][b][b'] (bytes, no padding)
+ * = 1 where b is in C(k,b') (the diagonal included), else 0. */
+long long cpc_nce_sampled_workspace_floats(int B, int K);
+int cpc_nce_loss_sampled(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
+                         float regularization, int n_neg, unsigned long long seed, unsigned long long draw, int dtype, void* stream);
+int cpc_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw, void* stream);
 
 /* Wasserstein gradient penalty with softplus_score_function (contrastive_estimation_training.py:12-16 under :144-158): the
  * coefficients the penalty's seeds carry.  S (and the tangent scores St1 + St2, St2 may be NULL): nmat f32 matrices [rows][ld].

@@ -185,6 +185,9 @@ _SIGNATURES = {
     "cpc_diff_scores_rank1": ([_P, _P, _P, _I, _I, _I, _L, _L, _I, _P], _I),
     "cpc_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P], _I),
     "cpc_adam_dev": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _F, _P, _P], _I),
+    "cpc_grad_norm_workspace_floats": ([_L], _L),
+    "cpc_grad_norm": ([_P, _L, _F, _F, _P, _P, _P, _P], _I),
+    "cpc_adam_clip": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

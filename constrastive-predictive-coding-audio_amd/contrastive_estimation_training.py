@@ -310,6 +310,14 @@ class ContrastiveEstimationTrainer:
         # Default loss branch only; validate() stays in-batch, as the reference measures accuracy.
         self.num_negatives = None
         self.negative_seed = 0
+        # Not in the reference's signature: clip the gradient to this global L2 norm before the update, as
+        # torch.nn.utils.clip_grad_norm_ in front of optimizer.step() (None: no clipping, the reference's step).  On the fused routes
+        # the norm and the clipped Adam are HIP kernels (engine.FusedAdam(max_grad_norm=...)); under data parallelism it is the norm of
+        # the gradient the update applies, after the reduction over the ranks.  The norm BEFORE clipping of the latest step read back
+        # is kept in last_grad_norm and goes to logger.grad_norm_meter where the logger has one; a norm that is not finite ends the run
+        # like a NaN loss.
+        self.max_grad_norm = None
+        self.last_grad_norm = None
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
         self.preprocess_ahead = True
         self.verbose = True
@@ -366,6 +374,16 @@ class ContrastiveEstimationTrainer:
         if self.global_negatives:
             raise NotImplementedError("num_negatives: global_negatives contrasts against the gathered batches of all ranks; the sampler "
                                       "draws from the rank's own batch only")
+
+    def _check_grad_clip(self):
+        """Up-front checks of max_grad_norm (before any GPU work): ValueError unless None or finite and > 0, NotImplementedError
+        together with use_graph."""
+        from .engine import check_max_grad_norm
+        value = check_max_grad_norm(self.max_grad_norm)
+        if value is not None and self.use_graph:
+            raise NotImplementedError("max_grad_norm: use_graph replays one captured step, and clipped steps are not captured into a "
+                                      "hipGraph")
+        return value
 
     def _score_kind(self):
         if self.score_function is difference_score_function:
@@ -434,6 +452,7 @@ class ContrastiveEstimationTrainer:
         reached, None on a NaN loss or when the epochs are exhausted.  ``batch_size`` is the per-process batch; under
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
         self._check_negatives(batch_size)
+        max_grad_norm = self._check_grad_clip()
         device = self._device()
         rank, world = self._world()
         self.model.train()
@@ -443,7 +462,7 @@ class ContrastiveEstimationTrainer:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
             self.model._flatten_parameters(device)
             graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
-            optimizer = FusedAdam(self.model, lr=lr, device_step=graphed)
+            optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm)
             self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
             graph_steps = {}
             glob_neg = {}
@@ -462,22 +481,31 @@ class ContrastiveEstimationTrainer:
         on_gpu = torch.device(device).type == "cuda"
         ring, ring_pos = [], [0]
 
+        clip = max_grad_norm is not None
+        width = 8 if clip else 6          # with clipping: + the norm before clipping and the coefficient applied (clip_state[0:2])
+
         def stash(step, vals):
             """Queues a step's (loss, max score) for the logger.  On the GPU they travel to a pinned host buffer right behind the
             step's own kernels and an event marks their arrival: reading them later does not wait for LATER steps' work, which a
             synchronous read of a device tensor — queued behind everything launched since — would."""
             if not on_gpu:
-                pending.append((step, vals.detach()[:6].clone(), None))
+                pending.append((step, vals.detach()[:width].clone(), None))
                 return
             need = self.host_sync_interval + self.host_sync_lag + 2
             while len(ring) < need:
-                ring.append(torch.empty(6, dtype=torch.float32, pin_memory=True))
+                ring.append(torch.empty(width, dtype=torch.float32, pin_memory=True))
             buf = ring[ring_pos[0] % len(ring)]
             ring_pos[0] += 1
-            buf.copy_(vals.detach()[:6].float(), non_blocking=True)
+            if clip and fused:          # the engine's result cell and FusedAdam.clip_state: two copies, one event
+                buf[:6].copy_(vals.detach()[:6].float(), non_blocking=True)
+                buf[6:].copy_(optimizer.clip_state[:2], non_blocking=True)
+            else:
+                buf.copy_(vals.detach()[:width].float(), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             pending.append((step, buf, ev))
+
+        bad_grad_norm = [False]
 
         def flush(keep=0):
             """Reads back all pending steps but the ``keep`` most recent ones (in order); returns the step of a NaN loss."""
@@ -487,13 +515,19 @@ class ContrastiveEstimationTrainer:
                     ev.synchronize()
                 row = vals.tolist()
                 loss_v, score_v, nan_v = float(row[0]), float(row[1]), float(row[5])        # cpc_nce_loss: out[0], out[1], out[5]
+                if clip:
+                    self.last_grad_norm = float(row[6])
                 # reference order (:124-133 before :164-169): a NaN loss ends the run before anything is logged for that step
                 if nan_v != 0.0 or math.isnan(loss_v):
+                    # (the indicator is also what cpc_grad_norm raises: a finite loss under it means the gradient was the cause)
+                    bad_grad_norm[0] = clip and not math.isnan(loss_v) and not math.isfinite(self.last_grad_norm)
                     pending.clear()
                     return step
                 if self.logger is not None:
                     self.logger.loss_meter.update(loss_v)
                     self.logger.score_meter.update(score_v)
+                    if clip and hasattr(self.logger, "grad_norm_meter"):
+                        self.logger.grad_norm_meter.update(self.last_grad_norm)
                     self.logger.log(step)
                 elif self.verbose:
                     print("loss at step step " + str(step) + ":", loss_v)
@@ -547,6 +581,8 @@ class ContrastiveEstimationTrainer:
             if here is not None and here[1] is not None and hasattr(optimizer, "t"):
                 optimizer.t = here[1]                               # no update has happened since the start of the NaN step
             self.training_step = step          # the reference leaves train() inside step `step`, before its update (:124-133)
+            if bad_grad_norm[0]:
+                print("gradient norm not finite at step", step, "(max_grad_norm): no update was applied")
             print("nan loss")
             print("returned with nan loss at step", step)
             return None
@@ -612,6 +648,8 @@ class ContrastiveEstimationTrainer:
                             eng.nan_flag().zero_()
                             guarded.add(id(eng))
                         optimizer.skip_flag = eng.nan_flag()
+                        if clip:
+                            optimizer.nan_pair = eng.nan_pair()
                         if sync is not None:      # per-GPU negatives: mean of the shard gradients; global negatives: they add up
                             sync.grad_scale = 1.0 if gneg is not None else 1.0 / world
                         if self.wasserstein_gradient_penalty:
@@ -635,7 +673,7 @@ class ContrastiveEstimationTrainer:
                         optimizer.step(grad_scale=1.0 if gneg is not None else 1.0 / world)
                         vals = out
                     else:
-                        vals = self._generic_step(batch, batch.shape[0], optimizer, world)
+                        vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm)
                     stash(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
                         nan_step = flush()
@@ -667,10 +705,12 @@ class ContrastiveEstimationTrainer:
             return {}
         return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
 
-    def _generic_step(self, batch, batch_size, optimizer, world):
+    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
-        the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133)."""
+        the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133).  With max_grad_norm,
+        torch.nn.utils.clip_grad_norm_ runs between the gradient all-reduce and optimizer.step() and the returned values grow by
+        (norm before clipping, coefficient); a norm that is not finite raises the indicator and skips the update."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
         if self.num_negatives is None:
@@ -682,6 +722,8 @@ class ContrastiveEstimationTrainer:
             import torch.distributed as dist
             dist.all_reduce(nan, op=dist.ReduceOp.MAX)
         vals = torch.cat([out[:5], nan])
+        if max_grad_norm is not None:
+            vals = torch.cat([vals, vals.new_zeros(2)])
         if float(nan.item()) != 0.0:
             return vals
         self.model.zero_grad()
@@ -690,6 +732,12 @@ class ContrastiveEstimationTrainer:
             for p in self.model.parameters():
                 dist.all_reduce(p.grad)
                 p.grad.div_(world)
+        if max_grad_norm is not None:
+            norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_grad_norm).detach().float()
+            vals[6], vals[7] = norm, torch.clamp(max_grad_norm / (norm + 1e-6), max=1.0)
+            if not math.isfinite(float(norm)):
+                vals[5] = 1.0
+                return vals
         optimizer.step()
         return vals
 

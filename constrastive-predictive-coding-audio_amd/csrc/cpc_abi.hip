@@ -761,4 +761,17 @@ int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr
     return launch_adam(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, skip, (hipStream_t)stream);
 }
 
+long long cpc_grad_norm_workspace_floats(long long n) { return grad_norm_workspace_floats(n); }
+
+int cpc_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,
+                  void* stream) {
+    return launch_grad_norm(g, n, grad_scale, max_norm, workspace, state, nan_pair, (hipStream_t)stream);
+}
+
+int cpc_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+                  float grad_scale, const float* coef, const float* skip, void* stream) {
+    if (!p || !g || !m || !v) return CPC_EINVAL;
+    return launch_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, coef, skip, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -171,6 +171,11 @@ int launch_diff_scores_rank1(const float* mu, const void* X, void* out, int rows
 int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype, hipStream_t stream);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, const float* skip, hipStream_t stream);
+long long grad_norm_workspace_floats(long long n);
+int launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,
+                     hipStream_t stream);
+int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
+                     float grad_scale, const float* coef, const float* skip, hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);
 int launch_conv_w_prep_batch(const void* jobs_dev, int njobs, int total_blocks, int lds_bytes, int dtype, hipStream_t stream);
 int launch_conv_w_prep_group(const float* W, const float* bias, void* fwd, void* dgrd, float* bias_g, int Cout, int Cin, int kh, int G,

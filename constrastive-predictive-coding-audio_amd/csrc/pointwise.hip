@@ -266,6 +266,148 @@ int launch_adam_dev(float* p, const float* g, float* m, float* v, long long n, f
     return CPC_OK;
 }
 
+// ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_; include/cpc_hip.h, cpc_grad_norm / cpc_adam_clip) ----
+// Stage 1: a workgroup takes GN_TILE = 256 threads x GN_CHAIN 16-byte loads = 8 192 consecutive floats; thread t reads the float4s
+// t, t + 256, ... of the tile (contiguous over the wave) and keeps four f32 chains acc[e] = fma(x, x, acc[e]) of GN_CHAIN links each,
+// x = g * grad_scale; then (acc0 + acc1) + (acc2 + acc3); thread t < n % 4 of the LAST workgroup adds the square of scalar-tail
+// element t; an xor-shuffle tree over the wave (6 levels), (w0 + w1) + (w2 + w3) over the four waves, one partial per workgroup.
+// Stage 2 (one workgroup): thread t adds the partials t, t + 256, ... in that order, then the same wave and workgroup tree.
+// Every sum has a fixed shape, there is no atomic: the same data give the same bits.  Roundings on the longest path from an
+// element to the total (tests/test_grad_clip_gpu.py computes its bound from these numbers):
+//   2 (the scaled value, squared) + GN_CHAIN + 2 + 1 (tail) + 6 + 2   +   ceil(workgroups / 256) + 6 + 2.
+constexpr int GN_CHAIN = 8;
+constexpr long long GN_TILE4 = 256LL * GN_CHAIN;          // float4s per workgroup
+
+__device__ __forceinline__ float gn_block_sum(float s, float* lds) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, long long n, float grad_scale,
+                                                                float* __restrict__ partial) {
+    __shared__ float lds[4];
+    const long long n4 = n / 4;
+    const long long base = (long long)blockIdx.x * GN_TILE4 + threadIdx.x;
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if ((long long)(blockIdx.x + 1) * GN_TILE4 <= n4) {          // whole tile: GN_CHAIN independent loads in flight
+        f32x4 x[GN_CHAIN];
+#pragma unroll
+        for (int c = 0; c < GN_CHAIN; ++c) x[c] = ((const f32x4*)g)[base + c * 256];
+#pragma unroll
+        for (int c = 0; c < GN_CHAIN; ++c)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float xe = x[c][e] * grad_scale;
+                acc[e] = __builtin_fmaf(xe, xe, acc[e]);
+            }
+    } else {
+        for (int c = 0; c < GN_CHAIN; ++c) {
+            const long long i = base + c * 256;
+            if (i >= n4) break;
+            const f32x4 x = ((const f32x4*)g)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float xe = x[e] * grad_scale;
+                acc[e] = __builtin_fmaf(xe, xe, acc[e]);
+            }
+        }
+    }
+    float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    if (blockIdx.x == gridDim.x - 1 && n4 * 4 + threadIdx.x < n) {          // scalar tail: at most three elements
+        const float xe = g[n4 * 4 + threadIdx.x] * grad_scale;
+        s = __builtin_fmaf(xe, xe, s);
+    }
+    s = gn_block_sum(s, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// state[0] = norm, state[1] = clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)), state[2] = 1 if the norm is NaN or inf
+// (then state[1] = 0 and nan_pair, when given, is raised: the NaN guard's step indicator and sticky flag), state[3] = max_norm
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __restrict__ partial, int nparts, float max_norm,
+                                                              float* __restrict__ state, float* __restrict__ nan_pair) {
+    __shared__ float lds[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += partial[i];
+    s = gn_block_sum(s, lds);
+    if (threadIdx.x != 0) return;
+    const float norm = sqrtf(s);
+    const bool bad = !(fabsf(norm) <= 3.402823466e38f);          // NaN or inf
+    state[0] = norm;
+    state[1] = bad ? 0.f : fminf(1.f, max_norm / (norm + 1e-6f));
+    state[2] = bad ? 1.f : 0.f;
+    state[3] = max_norm;
+    if (bad && nan_pair) { nan_pair[0] = 1.f; nan_pair[1] = 1.f; }
+}
+
+// adam_kernel with the gradient (g * grad_scale) * coef[0], multiplied in that order: with coef[0] == 1.0f the second product is exact
+// and the update is cpc_adam's.  (A kernel of its own: adam_kernel stays as it is, bit for bit.)
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long long n, float step_size, float b1, float b2,
+                                                        float eps, float inv_bc2_sqrt, float grad_scale, const float* __restrict__ coef,
+                                                        const float* __restrict__ skip) {
+    if (skip && skip[0] != 0.f) return;
+    const float cf = coef[0];
+    const long long n4 = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        // same access pattern as adam_kernel: gradient and moments non-temporal, the parameters are read again by the layout kernels
+        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
+              vv = __builtin_nontemporal_load((f32x4*)v + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gs = gg[e] * grad_scale;
+            const float ge = gs * cf;
+            mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
+            vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
+            const float denom = sqrtf(vv[e]) * inv_bc2_sqrt + eps;
+            pp[e] = pp[e] - step_size * (mm[e] / denom);
+        }
+        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
+    }
+    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float gs = g[i] * grad_scale;
+        const float ge = gs * cf;
+        const float mm = m[i] + (ge - m[i]) * (1.f - b1);
+        const float vv = v[i] * b2 + (1.f - b2) * ge * ge;
+        m[i] = mm; v[i] = vv;
+        p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
+    }
+}
+
+long long grad_norm_workspace_floats(long long n) {
+    if (n <= 0) return 0;
+    return std::max(1LL, (n / 4 + GN_TILE4 - 1) / GN_TILE4);          // one partial per workgroup
+}
+
+int launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,
+                     hipStream_t stream) {
+    if (n <= 0 || !g || ((uintptr_t)g % 16) || !workspace || !state || !(max_norm > 0.f) || !(max_norm <= 3.402823466e38f))
+        return CPC_EINVAL;
+    const long long blocks = grad_norm_workspace_floats(n);
+    if (blocks > 0x7fffffffLL) return CPC_EINVAL;
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g, n, grad_scale, workspace);
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, stream, (const float*)workspace, (int)blocks, max_norm, state,
+                       nan_pair);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
+                     float grad_scale, const float* coef, const float* skip, hipStream_t stream) {
+    if (n <= 0 || step < 1 || !coef) return CPC_EINVAL;
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt,
+                       grad_scale, coef, skip);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, const float* skip, hipStream_t stream) {
     if (n <= 0 || step < 1) return CPC_EINVAL;

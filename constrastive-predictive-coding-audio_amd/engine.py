@@ -1086,6 +1086,11 @@ class CPCEngine:
         """One-element view of the sticky NaN flag (nce_out[6]): FusedAdam.skip_flag; zero it when a run starts."""
         return self.nce_out[6:7]
 
+    def nan_pair(self):
+        """Two-element view (nce_out[5:7]): the step's NaN indicator and the sticky flag, FusedAdam.nan_pair — what cpc_grad_norm
+        raises when the gradient norm is not finite."""
+        return self.nce_out[5:7]
+
 
 class GRUContext:
     """AudioGRUModel as the context network (audio_model.py:47-77): one batched input-projection GEMM for all V steps, the
@@ -2323,10 +2328,23 @@ class GradAllReduce:
         self.last_plan, self._plan = self._plan, []
 
 
+def check_max_grad_norm(max_grad_norm):
+    """None, or the value as a float: ValueError unless it is finite and > 0 (what cpc_grad_norm admits)."""
+    if max_grad_norm is None:
+        return None
+    try:
+        value = float(max_grad_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_grad_norm must be None or a positive finite number, got {max_grad_norm!r}") from None
+    if not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"max_grad_norm must be None or a positive finite number, got {max_grad_norm!r}")
+    return value
+
+
 class FusedAdam:
     """torch.optim.Adam (default betas / eps, no weight decay) over the model's flat f32 parameter buffer as one kernel."""
 
-    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False):
+    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None):
         self.model = model
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         flat = model._flat_param
@@ -2344,6 +2362,18 @@ class FusedAdam:
         # device_step: the step count lives on the device (cpc_adam_dev), so the call's arguments never change and the step
         # can be part of a captured hipGraph
         self.state = torch.zeros(4, device=flat.device, dtype=torch.float32) if device_step else None
+        # max_grad_norm: torch.nn.utils.clip_grad_norm_ in front of the update ("Gradient clipping").  The norm needs the
+        # WHOLE gradient, so hook() / update_range() only record their range and step() runs cpc_grad_norm and one cpc_adam_clip
+        # over the buffer.  clip_state (device f32[4]) = {norm before clipping, coefficient applied, 1 if the norm is not finite,
+        # max_grad_norm}; nan_pair: two-element device tensor (CPCEngine.nan_pair()) raised when the norm is not finite.
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.nan_pair = None
+        if self.max_grad_norm is not None:
+            if device_step:
+                raise NotImplementedError("max_grad_norm with device_step=True: clipped steps are not captured into a hipGraph")
+            self.clip_state = torch.zeros(4, device=flat.device, dtype=torch.float32)
+            self._clip_ws = torch.empty(int(_hip.lib().cpc_grad_norm_workspace_floats(flat.numel())), device=flat.device,
+                                        dtype=torch.float32)
 
     def hook(self, lo, hi):
         """Single-process use as ``grad_ready_hook``: updates flat_param[lo:hi] as soon as the backward pass reports that range
@@ -2362,6 +2392,8 @@ class FusedAdam:
             raise ValueError("piecewise updates need the host-side step count (device_step=False)")
         self._done_lo = lo if self._done_lo is None else min(self._done_lo, lo)
         self._piece_scale = float(grad_scale)
+        if self.max_grad_norm is not None:          # the update waits for the norm of the whole gradient: step()
+            return
         self._launch(lo, hi, self.t + 1, grad_scale)
         if self.after_update is not None:
             self.after_update(lo, hi, False)
@@ -2375,9 +2407,29 @@ class FusedAdam:
                   C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), t,
                   C.c_float(grad_scale), _hip.ptr(self.skip_flag))
 
+    def _clipped_update(self, grad_scale):
+        """Norm of grad_scale * (whole flat gradient) — under data parallelism the gradient summed over the ranks, the same on every
+        rank — then Adam on the clipped gradient.  Both launches are queued; nothing is read back here."""
+        flat, grad = self.model._flat_param, self.model._flat_grad
+        n = C.c_longlong(flat.numel())
+        self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
+        _hip.call("cpc_grad_norm", _hip.ptr(grad), n, C.c_float(grad_scale), C.c_float(self.max_grad_norm), _hip.ptr(self._clip_ws),
+                  _hip.ptr(self.clip_state), _hip.ptr(self.nan_pair))
+        _hip.call("cpc_adam_clip", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), n, C.c_float(self.lr),
+                  C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, C.c_float(grad_scale),
+                  _hip.ptr(self.clip_state, 1), _hip.ptr(self.skip_flag))
+
     def step(self, grad_scale: float = 1.0):
         self.t += 1
         flat, grad = self.model._flat_param, self.model._flat_grad
+        if self.max_grad_norm is not None:
+            if self._done_lo is not None and float(grad_scale) != self._piece_scale:
+                raise ValueError(f"the pieces of this step were recorded with grad_scale {self._piece_scale}, step() got {grad_scale}")
+            self._done_lo = None
+            self._clipped_update(grad_scale)
+            if self.after_update is not None:
+                self.after_update(0, flat.numel(), True)
+            return
         if self._done_lo is not None:          # ranges [done_lo, end) were updated by hook() during the backward pass
             hi, self._done_lo = self._done_lo, None
             if float(grad_scale) != self._piece_scale:

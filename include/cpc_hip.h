@@ -681,6 +681,28 @@ int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr
 int cpc_adam_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
                  float grad_scale, const float* skip, void* stream);
 
+
+/* Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(parameters, max_norm) over one flat f32 gradient buffer (not in
+ * the reference's train step; DESIGN.md, "Gradient clipping").  cpc_grad_norm replaces its norm and coefficient:
+ *   state f32[4] (device): state[0] = || grad_scale * g ||_2, state[1] = min(1, max_norm / (state[0] + 1e-6)) — the factor
+ *   clip_grad_norm_ multiplies every gradient by —, state[2] = 1 if the norm is NaN or inf, else 0 (then state[1] = 0),
+ *   state[3] = max_norm.
+ * Squares and sums are float32, in a fixed order without atomics: the same data give the same bits, and an element above about
+ * 1e19 overflows its square and makes the norm inf — non-finite, as torch's float32 norm of it is.
+ * nan_pair (two floats, or NULL): both are set to 1 when the norm is not finite and left alone otherwise; pass out + 5 of
+ * cpc_nce_loss (step indicator and sticky flag) and a non-finite gradient ends the run the way a NaN loss does.
+ * g must be 16-byte aligned; workspace: cpc_grad_norm_workspace_floats(n) floats; max_norm finite and > 0. */
+long long cpc_grad_norm_workspace_floats(long long n);
+int cpc_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,
+                  void* stream);
+/* cpc_adam on the clipped gradient, the optimizer.step() behind torch.nn.utils.clip_grad_norm_: the gradient is
+ * (g * grad_scale) * coef[0], multiplied in that order (coef: device pointer to one float, state + 1 of cpc_grad_norm), so
+ * that coef[0] == 1 gives cpc_adam's bits wherever g * grad_scale is itself exact (grad_scale 1 or a power of two; cpc_adam
+ * contracts that product into its first-moment update, so for other scales the two differ by its rounding).  skip as in
+ * cpc_adam (wire nan_pair of cpc_grad_norm to it: a coefficient of 0 alone does not stop inf * 0 from reaching the parameters). */
+int cpc_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                  int step, float grad_scale, const float* coef, const float* skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

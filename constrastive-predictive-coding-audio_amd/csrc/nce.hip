@@ -69,7 +69,8 @@ __device__ __forceinline__ void nce_col_body(const float* __restrict__ S, float*
         for (int r = 1; r < RL; ++r) m = fmaxf(m, smx[r][tx]);
         float tot = 0.f;
 #pragma unroll
-        for (int r = 0; r < RL; ++r) tot += (smx[r][tx] == -INFINITY) ? 0.f : ssum[r][tx] * expf(smx[r][tx] - m);
+        for (int r = 0; r < RL; ++r)          // (a part whose max IS the column's max counts as it stands: with m = +inf, inf - inf would be NaN)
+            tot += (smx[r][tx] == -INFINITY) ? 0.f : (smx[r][tx] == m) ? ssum[r][tx] : ssum[r][tx] * expf(smx[r][tx] - m);
         if (nbz > 1) {
             if (bp < B) {
                 pm[((long long)bz * K + k) * B + bp] = m;
@@ -104,7 +105,8 @@ __global__ __launch_bounds__(256) void nce_col_merge_kernel(const float* __restr
         float tot = 0.f;
         for (int z = 0; z < nsplit; ++z) {
             const float mz = pm[(long long)z * ncols + c];
-            tot += (mz == -INFINITY) ? 0.f : ps[(long long)z * ncols + c] * expf(mz - m);
+            const float sz = ps[(long long)z * ncols + c];
+            tot += (mz == -INFINITY) ? 0.f : (mz == m) ? sz : sz * expf(mz - m);          // (mz == m: as in nce_col_body)
         }
         l = m + logf(tot);
         lse[c] = l;
@@ -755,7 +757,8 @@ __device__ __forceinline__ void nsm_col_body(const float* __restrict__ S, unsign
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     float sum = 0.f;
 #pragma unroll
-    for (int h = 0; h < H; ++h) sum += expf(v[h] - mx);          // a NaN score: dropped by fmaxf, carried by the sum, as nce_col_body does
+    for (int h = 0; h < H; ++h)                  // a NaN score: dropped by fmaxf, carried by the sum, as nce_col_body does
+        sum += (v[h] == mx) ? 1.f : expf(v[h] - mx);          // (the max itself is 1 also when it is +inf: inf - inf would be NaN)
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) {
         thr[col] = t;
@@ -888,6 +891,7 @@ long long nce_workspace_floats(int B, int K) {
 int launch_nce(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
                int dtype, hipStream_t stream) {
     if (B <= 0 || K <= 0 || ld < B || ld > B + 7) return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) return CPC_EINVAL;       // before the first launch: a refused call writes nothing
     float* lse = workspace;
     const int ncb = (B + NCE_CW - 1) / NCE_CW;
     const int ncol = K * ncb;
@@ -904,11 +908,9 @@ int launch_nce(const float* S, void* dS, void* dST, float* out, float* workspace
     if (dtype == CPC_DTYPE_BF16)
         hipLaunchKernelGGL((nce_grad_kernel<bf16_t>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, mean, (bf16_t*)dS, (bf16_t*)dST,
                            B, K, ld, softplus, reg, colp, ncol, gradp, nmb, out);
-    else if (dtype == CPC_DTYPE_F32)
+    else
         hipLaunchKernelGGL((nce_grad_kernel<float>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, mean, (float*)dS, (float*)dST, B, K,
                            ld, softplus, reg, colp, ncol, gradp, nmb, out);
-    else
-        return CPC_EINVAL;
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }
@@ -976,6 +978,7 @@ int launch_nce_all(const float* S, const float* ST, void* dS, void* dST, float* 
                    int softplus, float reg, int dtype, hipStream_t stream) {
     const int R = B * K;
     if (B <= 0 || K <= 0 || ld < R) return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) return CPC_EINVAL;       // before the first launch: a refused call writes nothing
     float* lse = workspace;
     const int ncb = (R + 31) / 32;
     float* colp = lse + R;
@@ -1004,10 +1007,8 @@ int launch_nce_all(const float* S, const float* ST, void* dS, void* dST, float* 
     } while (0)
     if (dtype == CPC_DTYPE_BF16) {
         if (K == 12) NCE_ALL_GRAD(bf16_t, 12); else if (K == 16) NCE_ALL_GRAD(bf16_t, 16); else NCE_ALL_GRAD(bf16_t, 0);
-    } else if (dtype == CPC_DTYPE_F32) {
-        if (K == 12) NCE_ALL_GRAD(float, 12); else if (K == 16) NCE_ALL_GRAD(float, 16); else NCE_ALL_GRAD(float, 0);
     } else {
-        return CPC_EINVAL;
+        if (K == 12) NCE_ALL_GRAD(float, 12); else if (K == 16) NCE_ALL_GRAD(float, 16); else NCE_ALL_GRAD(float, 0);
     }
 #undef NCE_ALL_GRAD
     hipLaunchKernelGGL(nce_all_finalize_kernel, dim3(1), dim3(256), 0, stream, colp, n_colp, gradp, blocks, out, B, K, reg);

@@ -566,7 +566,10 @@ int cpc_gru_set_streaming(int on);
  *   reg; out[5] = 1 if the loss before the regulariser (out[2] + out[3]) is NaN — the value the reference's NaN guard tests
  *   (:124) — else 0; out[6] = sticky NaN flag: set to 1 together with out[5], never cleared by the library (the caller zeroes it
  *   when a run starts; cpc_adam's `skip` argument).  cpc_nce_loss_all writes the same eight values.
- *   dS[k][b][b'], dST[k][b'][b] (T): d loss / d linear score.  workspace: cpc_nce_workspace_floats(B,K) f32. */
+ *   dS[k][b][b'], dST[k][b'][b] (T): d loss / d linear score.  workspace: cpc_nce_workspace_floats(B,K) f32.
+ * CPC_EINVAL for B <= 0, K <= 0, ld < B, ld > B + 7 (cpc_nce_loss_all: ld < B K), a dtype other than f32 / bf16 and a null pointer.
+ * A refused call of cpc_nce_loss, cpc_nce_loss_all or cpc_nce_loss_sampled launches nothing: every buffer, the workspace included,
+ * keeps its bytes.  One +inf among a column's linear scores gives lse = +inf for that column (loss +inf, out[5] stays 0). */
 long long cpc_nce_workspace_floats(int B, int K);
 int cpc_nce_loss(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
                  float regularization, int dtype, void* stream);

@@ -402,7 +402,7 @@ def _eval_scores(B, K, all_t, ld, g, ties=False, nans=False):
 
 @pytest.mark.parametrize("softplus", [0, 1])
 @pytest.mark.parametrize("all_t", [0, 1])
-@pytest.mark.parametrize("B,K", [(1, 1), (5, 3), (33, 12), (1, 12), (33, 1), (5, 12)])
+@pytest.mark.parametrize("B,K", [(1, 1), (5, 3), (33, 12), (1, 12), (33, 1), (5, 12), (70, 2), (257, 1)])
 @pytest.mark.parametrize("special", ["", "ties", "nans"])
 def test_nce_eval_against_oracle(softplus, all_t, B, K, special):
     """cpc_nce_eval (the validate() quantities) against oracle.validation_terms in float64: both branches (all-timesteps R below and

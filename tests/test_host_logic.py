@@ -173,6 +173,41 @@ def test_stem_arguments_are_checked_before_any_launch():
     assert stats(2, hmax + 1, 3, 3, 2, 1, 4) == -22                 # beyond the LDS limit
 
 
+def test_dense_nce_arguments_are_checked_before_any_launch():
+    """cpc_nce_loss, cpc_nce_loss_all and cpc_gp_score_coeff return CPC_EINVAL (-22) for B = 0, K = 0, a leading dimension outside
+    their limits, a dtype code that is neither f32 nor bf16, a mode they do not have and a null pointer: argument checks that return
+    before a launch (tests/test_nce_dense_gpu.py checks on the device that no buffer changes), so this runs without a GPU."""
+    import ctypes as C
+    lib = _hip.lib()
+    P = C.c_void_p(0x1000)        # never dereferenced
+    s = C.c_void_p(0)
+    B, K, reg = 8, 2, C.c_float(0.5)
+
+    def loss(S=P, dS=P, dST=P, out=P, ws=P, B=B, K=K, ld=B, dtype=_hip.F32):
+        return lib.cpc_nce_loss(S, dS, dST, out, ws, B, K, ld, 1, reg, dtype, s)
+
+    def loss_all(S=P, ST=P, dS=P, dST=P, out=P, ws=P, B=B, K=K, ld=B * K, dtype=_hip.F32):
+        return lib.cpc_nce_loss_all(S, ST, dS, dST, out, ws, B, K, ld, 1, reg, dtype, s)
+
+    for fn, names in ((loss, ("S", "dS", "dST", "out", "ws")), (loss_all, ("S", "ST", "dS", "dST", "out", "ws"))):
+        assert fn(B=0) == -22 and fn(K=0) == -22 and fn(B=-1) == -22
+        for code in (2, -1, 7):
+            assert fn(dtype=code) == -22, code
+        for name in names:
+            assert fn(**{name: None}) == -22, name
+    assert loss(ld=B - 1) == -22 and loss(ld=B + 8) == -22
+    assert loss_all(ld=B * K - 1) == -22
+
+    def coeff(S=P, St1=P, St2=P, W=P, WT=P, nmat=3, rows=5, cols=7, ld=8, ldT=8, mode=0):
+        return lib.cpc_gp_score_coeff(S, St1, St2, W, WT, nmat, rows, cols, ld, ldT, mode, s)
+
+    assert coeff(mode=2) == -22 and coeff(mode=-1) == -22 and coeff(mode=1, St1=None) == -22
+    assert coeff(ld=6) == -22 and coeff(ldT=4) == -22
+    assert coeff(nmat=0) == -22 and coeff(rows=0) == -22 and coeff(cols=0) == -22
+    for name in ("S", "W", "WT"):
+        assert coeff(**{name: None}) == -22, name
+
+
 # Entry points of include/cpc_hip.h that no test names, each with the reason.  Only entry points outside the scalogram path may stand
 # here; the list may only shrink (a name that a test mentions must leave it).
 ABI_NAMES_WITHOUT_A_TEST = {

@@ -188,6 +188,9 @@ _SIGNATURES = {
     "cpc_grad_norm_workspace_floats": ([_L], _L),
     "cpc_grad_norm": ([_P, _L, _F, _F, _P, _P, _P, _P], _I),
     "cpc_adam_clip": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P, _P], _I),
+    "cpc_adamw": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _P, _L, _P, _P, _P], _I),
+    "cpc_adamw_dev": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _F, _F, _P, _I, _L, _L, _F, _L, _P, _P, _P], _I),
+    "cpc_lr_factors": ([_I, _L, _L, _F, _L, _I, _P, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

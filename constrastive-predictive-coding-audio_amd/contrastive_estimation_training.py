@@ -26,6 +26,7 @@ from .audio_model import *          # noqa: F401,F403  (the reference re-exports
 from .audio_dataset import FileBatchSampler
 from . import switches
 from .sampled_negatives import check_negatives, sampled_negative_mask          # noqa: F401  (public: the host restatement)
+from .engine import LRSchedule          # noqa: F401  (public: trainer.lr_schedule takes one)
 
 
 def _need_gpu(t, what):
@@ -318,6 +319,21 @@ class ContrastiveEstimationTrainer:
         # like a NaN loss.
         self.max_grad_norm = None
         self.last_grad_norm = None
+        # Not in the reference's signature (it runs Adam at one constant lr, without decay, from zero moments in every train() call):
+        # weight_decay: torch.optim.AdamW's decoupled decay, p <- p (1 - lr_step * weight_decay) in front of Adam's update, on the
+        #   parameters weight_decay_filter(name, parameter) selects (None: parameter.dim() >= 2 — conv, GRU, linear and attention
+        #   matrices, not biases or BatchNorm's weight and bias);
+        # lr_schedule: an LRSchedule; step s runs at lr * lr_schedule.factor(s) with s = training_step, so that
+        #   continue_training_at_step resumes the schedule (None: the reference's constant lr);
+        # optimizer_state: a state dict in torch.optim.Adam's format, loaded into the optimizer at the start of the next train() and
+        #   then set back to None (trainer.last_optimizer.state_dict() takes one out of a fused run);
+        # last_lr: the learning rate of the latest step launched; every step's rate goes to logger.lr_meter where the logger has one.
+        # On the fused routes decay and schedule are engine.FusedAdam's (cpc_adamw; cpc_adamw_dev under use_graph).
+        self.weight_decay = 0.0
+        self.weight_decay_filter = None
+        self.lr_schedule = None
+        self.optimizer_state = None
+        self.last_lr = None
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
         self.preprocess_ahead = True
         self.verbose = True
@@ -384,6 +400,18 @@ class ContrastiveEstimationTrainer:
             raise NotImplementedError("max_grad_norm: use_graph replays one captured step, and clipped steps are not captured into a "
                                       "hipGraph")
         return value
+
+    def _check_adamw(self):
+        """Up-front checks of weight_decay, weight_decay_filter, lr_schedule and optimizer_state (before any GPU work): ValueError
+        for a decay that is not finite and >= 0, a filter that is not callable, a schedule that is no LRSchedule, a state that is no
+        dict.  Returns (weight_decay, filter or None, schedule or None)."""
+        from .engine import check_weight_decay
+        value = check_weight_decay(self.weight_decay, self.weight_decay_filter)
+        if self.lr_schedule is not None and not isinstance(self.lr_schedule, LRSchedule):
+            raise ValueError(f"lr_schedule must be None or an LRSchedule, got {self.lr_schedule!r}")
+        if self.optimizer_state is not None and not isinstance(self.optimizer_state, dict):
+            raise ValueError("optimizer_state must be None or an optimizer's state dict")
+        return value, self.weight_decay_filter, self.lr_schedule
 
     def _score_kind(self):
         if self.score_function is difference_score_function:
@@ -453,6 +481,7 @@ class ContrastiveEstimationTrainer:
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
         self._check_negatives(batch_size)
         max_grad_norm = self._check_grad_clip()
+        weight_decay, decay_filter, schedule = self._check_adamw()
         device = self._device()
         rank, world = self._world()
         self.model.train()
@@ -462,7 +491,8 @@ class ContrastiveEstimationTrainer:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
             self.model._flatten_parameters(device)
             graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
-            optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm)
+            optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                                  decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step))
             self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
             graph_steps = {}
             glob_neg = {}
@@ -471,6 +501,13 @@ class ContrastiveEstimationTrainer:
         else:
             self.model._flatten_parameters(device)
             optimizer = self.optimizer(self.model.parameters(), lr=lr)
+        decayed = []
+        if weight_decay > 0.0 and not fused:          # the generic route multiplies them itself, in front of optimizer.step()
+            from .engine import default_decay_filter
+            decayed = [p for n_, p in self.model.named_parameters() if (decay_filter or default_decay_filter)(n_, p)]
+        if self.optimizer_state is not None:
+            state, self.optimizer_state = self.optimizer_state, None
+            optimizer.load_state_dict(state)
         sampler = FileBatchSampler(index_count_per_file=self.dataset.get_example_count_per_file(),
                                    batch_size=batch_size * world, file_batch_size=self.file_batch_size, drop_last=True,
                                    verbose=self.verbose)
@@ -489,7 +526,7 @@ class ContrastiveEstimationTrainer:
             step's own kernels and an event marks their arrival: reading them later does not wait for LATER steps' work, which a
             synchronous read of a device tensor — queued behind everything launched since — would."""
             if not on_gpu:
-                pending.append((step, vals.detach()[:width].clone(), None))
+                pending.append((step, vals.detach()[:width].clone(), None, self.last_lr))
                 return
             need = self.host_sync_interval + self.host_sync_lag + 2
             while len(ring) < need:
@@ -503,14 +540,14 @@ class ContrastiveEstimationTrainer:
                 buf.copy_(vals.detach()[:width].float(), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            pending.append((step, buf, ev))
+            pending.append((step, buf, ev, self.last_lr))          # (the host knows the step's learning rate: it rides along)
 
         bad_grad_norm = [False]
 
         def flush(keep=0):
             """Reads back all pending steps but the ``keep`` most recent ones (in order); returns the step of a NaN loss."""
             n = max(len(pending) - keep, 0)
-            for step, vals, ev in pending[:n]:
+            for step, vals, ev, lr_v in pending[:n]:
                 if ev is not None:
                     ev.synchronize()
                 row = vals.tolist()
@@ -528,6 +565,8 @@ class ContrastiveEstimationTrainer:
                     self.logger.score_meter.update(score_v)
                     if clip and hasattr(self.logger, "grad_norm_meter"):
                         self.logger.grad_norm_meter.update(self.last_grad_norm)
+                    if hasattr(self.logger, "lr_meter"):
+                        self.logger.lr_meter.update(lr_v)
                     self.logger.log(step)
                 elif self.verbose:
                     print("loss at step step " + str(step) + ":", loss_v)
@@ -608,6 +647,10 @@ class ContrastiveEstimationTrainer:
                 # (the sampler is read one batch ahead only where that batch is preprocessed ahead)
                 for batch, next_batch in (_with_next(batches) if ahead is not None else ((b_, None) for b_ in batches)):
                     snapshot(self.training_step)
+                    # the step's learning rate, before its first hook can fire (under use_graph the device evaluates the same factor)
+                    self.last_lr = step_lr = lr if schedule is None else lr * schedule.factor(self.training_step)
+                    if fused and schedule is not None:
+                        optimizer.lr = step_lr
                     if fused and graphed:
                         eng = self.model.engine(batch.shape[0], batch.shape[1], device)
                         key = (batch.shape[0], batch.shape[1])
@@ -673,7 +716,8 @@ class ContrastiveEstimationTrainer:
                         optimizer.step(grad_scale=1.0 if gneg is not None else 1.0 / world)
                         vals = out
                     else:
-                        vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm)
+                        vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm,
+                                                  (step_lr if schedule is not None else None, step_lr * weight_decay, decayed))
                     stash(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
                         nan_step = flush()
@@ -705,12 +749,14 @@ class ContrastiveEstimationTrainer:
             return {}
         return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
 
-    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None):
+    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ())):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
         the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133).  With max_grad_norm,
         torch.nn.utils.clip_grad_norm_ runs between the gradient all-reduce and optimizer.step() and the returned values grow by
-        (norm before clipping, coefficient); a norm that is not finite raises the indicator and skips the update."""
+        (norm before clipping, coefficient); a norm that is not finite raises the indicator and skips the update.
+        adamw = (the step's learning rate under a schedule or None, lr * weight_decay of the step, the parameters that decay): every
+        param group gets the rate, and the decay p <- p (1 - lr weight_decay) is applied right before optimizer.step()."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
         if self.num_negatives is None:
@@ -738,6 +784,13 @@ class ContrastiveEstimationTrainer:
             if not math.isfinite(float(norm)):
                 vals[5] = 1.0
                 return vals
+        step_lr, lr_wd, decayed = adamw
+        if step_lr is not None:
+            for group in optimizer.param_groups:
+                group["lr"] = step_lr
+        if lr_wd != 0.0 and decayed:
+            with torch.no_grad():
+                torch._foreach_mul_(list(decayed), 1.0 - lr_wd)
         optimizer.step()
         return vals
 

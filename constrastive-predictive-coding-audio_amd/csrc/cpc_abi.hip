@@ -774,4 +774,23 @@ int cpc_adam_clip(float* p, const float* g, float* m, float* v, long long n, flo
     return launch_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, coef, skip, (hipStream_t)stream);
 }
 
+int cpc_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+              float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
+              const float* skip, void* stream) {
+    return launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, weight_decay, decay_bits, first_block, coef, skip,
+                        (hipStream_t)stream);
+}
+
+int cpc_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                  float* state, float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
+                  long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip, void* stream) {
+    return launch_adamw_dev(p, g, m, v, n, lr, beta1, beta2, eps, state, grad_scale, weight_decay, decay_bits, kind, warmup_steps,
+                            total_steps, min_ratio, step_offset, coef, skip, (hipStream_t)stream);
+}
+
+int cpc_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
+                   void* stream) {
+    return launch_lr_factors(kind, warmup_steps, total_steps, min_ratio, step0, count, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -176,6 +176,15 @@ int launch_grad_norm(const float* g, long long n, float grad_scale, float max_no
                      hipStream_t stream);
 int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
                      float grad_scale, const float* coef, const float* skip, hipStream_t stream);
+int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
+                 float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
+                 const float* skip, hipStream_t stream);
+int launch_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
+                     float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
+                     long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip,
+                     hipStream_t stream);
+int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
+                      hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);
 int launch_conv_w_prep_batch(const void* jobs_dev, int njobs, int total_blocks, int lds_bytes, int dtype, hipStream_t stream);
 int launch_conv_w_prep_group(const float* W, const float* bias, void* fwd, void* dgrd, float* bias_g, int Cout, int Cin, int kh, int G,

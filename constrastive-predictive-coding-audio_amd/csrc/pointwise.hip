@@ -408,6 +408,159 @@ int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, 
     return CPC_OK;
 }
 
+// ---- AdamW and the learning-rate schedule (torch.optim.AdamW + LambdaLR; include/cpc_hip.h, cpc_adamw / cpc_adamw_dev / cpc_lr_factors) ----
+// LRSchedule.factor(s) of engine.py in double: s is the 0-based index of the step, kind 0 constant / 1 linear / 2 cosine.
+__device__ __forceinline__ double lr_factor(int kind, long long warmup, long long total, double min_ratio, long long s) {
+    if (s < warmup) return (double)(s + 1) / (double)warmup;
+    if (kind == 0) return 1.0;
+    const double q = fmin((double)(s - warmup) / (double)(total - warmup), 1.0);
+    if (kind == 1) return min_ratio + (1.0 - min_ratio) * (1.0 - q);
+    return min_ratio + (1.0 - min_ratio) * 0.5 * (1.0 + cos(3.14159265358979323846 * q));
+}
+
+__global__ void lr_factors_kernel(int kind, long long warmup, long long total, float min_ratio, long long step0, int count,
+                                  float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) out[i] = (float)lr_factor(kind, warmup, total, (double)min_ratio, step0 + i);
+}
+
+// adam_tick_kernel with the schedule and the decay: state[0] = step count t (int bits), state[1] = lr f / (1 - b1^t),
+// state[2] = 1 / sqrt(1 - b2^t), state[3] = 1 - lr f wd, with f = factor(step_offset + t - 1).
+__global__ void adamw_tick_kernel(float* __restrict__ state, float lr, float b1, float b2, float weight_decay, int kind,
+                                  long long warmup, long long total, float min_ratio, long long step_offset,
+                                  const float* __restrict__ skip) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (skip && skip[0] != 0.f) return;
+    int t = __float_as_int(state[0]) + 1;
+    state[0] = __int_as_float(t);
+    const double lrs = (double)lr * lr_factor(kind, warmup, total, (double)min_ratio, step_offset + t - 1);
+    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+    state[1] = (float)(lrs / bc1);
+    state[2] = (float)(1.0 / sqrt(bc2));
+    state[3] = (float)(1.0 - lrs * (double)weight_decay);
+}
+
+// One 16-byte piece / one tail element of the update.  COEF = false has adam_kernel's expressions, COEF = true adam_clip_kernel's;
+// the decay is a select in front of them (never an operand of their subtraction), so that an undecayed element keeps their bits.
+template <bool COEF>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long long n, float step_size, float b1, float b2, float eps,
+                                           float inv_bc2_sqrt, float grad_scale, float decay, const unsigned* __restrict__ bits,
+                                           long long first_block, float cf) {
+    const long long n4 = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        // a float4 lies inside one 64-float block: 16 consecutive lanes share the word (one cached 4-byte load)
+        const long long blk = first_block + (i >> 4);
+        const bool dec = bits && ((bits[blk >> 5] >> (unsigned)(blk & 31)) & 1u);
+        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
+              vv = __builtin_nontemporal_load((f32x4*)v + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float pd = dec ? pp[e] * decay : pp[e];
+            if (COEF) {
+                const float gs = gg[e] * grad_scale;
+                const float ge = gs * cf;
+                mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
+                vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
+            } else {
+                const float ge = gg[e] * grad_scale;
+                mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
+                vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
+            }
+            const float denom = sqrtf(vv[e]) * inv_bc2_sqrt + eps;
+            pp[e] = pd - step_size * (mm[e] / denom);
+        }
+        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
+    }
+    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const long long blk = first_block + (i >> 6);
+        const bool dec = bits && ((bits[blk >> 5] >> (unsigned)(blk & 31)) & 1u);
+        const float pd = dec ? p[i] * decay : p[i];
+        float mm, vv;
+        if (COEF) {
+            const float gs = g[i] * grad_scale;
+            const float ge = gs * cf;
+            mm = m[i] + (ge - m[i]) * (1.f - b1);
+            vv = v[i] * b2 + (1.f - b2) * ge * ge;
+        } else {
+            const float ge = g[i] * grad_scale;
+            mm = m[i] + (ge - m[i]) * (1.f - b1);
+            vv = v[i] * b2 + (1.f - b2) * ge * ge;
+        }
+        m[i] = mm; v[i] = vv;
+        p[i] = pd - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
+    }
+}
+
+// The one streaming kernel of cpc_adamw and cpc_adamw_dev: with ``state`` the three step scalars come from the device
+// (adamw_tick_kernel), otherwise from the arguments.  bits == nullptr: nothing decays.
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, long long n, float step_size, float b1, float b2, float eps,
+                                                    float inv_bc2_sqrt, float grad_scale, float decay,
+                                                    const unsigned* __restrict__ bits, long long first_block,
+                                                    const float* __restrict__ state, const float* __restrict__ coef,
+                                                    const float* __restrict__ skip) {
+    if (skip && skip[0] != 0.f) return;
+    if (state) { step_size = state[1]; inv_bc2_sqrt = state[2]; decay = state[3]; }
+    if (coef)
+        adamw_body<true>(p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale, decay, bits, first_block, coef[0]);
+    else
+        adamw_body<false>(p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale, decay, bits, first_block, 1.f);
+}
+
+static bool lr_schedule_ok(int kind, long long warmup, long long total, float min_ratio) {
+    if (kind < 0 || kind > 2 || warmup < 0 || !(min_ratio >= 0.f && min_ratio <= 1.f)) return false;
+    return kind == 0 || total > warmup;
+}
+
+static bool adamw_args_ok(const float* p, const float* g, const float* m, const float* v, long long n, float weight_decay,
+                          const unsigned* decay_bits, long long first_block) {
+    if (!p || !g || !m || !v || n <= 0 || first_block < 0) return false;
+    if (!(weight_decay >= 0.f) || !(weight_decay <= 3.402823466e38f)) return false;          // negative, NaN or inf
+    return !(weight_decay > 0.f && !decay_bits);
+}
+
+int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
+                 float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
+                 const float* skip, hipStream_t stream) {
+    if (!adamw_args_ok(p, g, m, v, n, weight_decay, decay_bits, first_block) || step < 1) return CPC_EINVAL;
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
+    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale,
+                       decay, weight_decay > 0.f ? decay_bits : (const unsigned*)nullptr, first_block, (const float*)nullptr, coef, skip);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
+                     float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
+                     long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip,
+                     hipStream_t stream) {
+    if (!adamw_args_ok(p, g, m, v, n, weight_decay, decay_bits, 0) || !state || coef || step_offset < 0 ||
+        !lr_schedule_ok(kind, warmup_steps, total_steps, min_ratio))
+        return CPC_EINVAL;
+    hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, stream, state, lr, b1, b2, weight_decay, kind, warmup_steps, total_steps,
+                       min_ratio, step_offset, skip);
+    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
+    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, 0.f, b1, b2, eps, 0.f, grad_scale, 1.f,
+                       weight_decay > 0.f ? decay_bits : (const unsigned*)nullptr, 0LL, (const float*)state, (const float*)nullptr, skip);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
+                      hipStream_t stream) {
+    if (!lr_schedule_ok(kind, warmup_steps, total_steps, min_ratio) || step0 < 0 || count <= 0 || !out) return CPC_EINVAL;
+    hipLaunchKernelGGL(lr_factors_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, kind, warmup_steps, total_steps, min_ratio,
+                       step0, count, out);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, const float* skip, hipStream_t stream) {
     if (n <= 0 || step < 1) return CPC_EINVAL;

@@ -2341,12 +2341,100 @@ def check_max_grad_norm(max_grad_norm):
     return value
 
 
-class FusedAdam:
-    """torch.optim.Adam (default betas / eps, no weight decay) over the model's flat f32 parameter buffer as one kernel."""
+def check_weight_decay(weight_decay, decay_filter=None):
+    """The decay as a float: ValueError unless it is finite and >= 0 (what cpc_adamw admits) and the filter None or callable."""
+    try:
+        value = float(weight_decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"weight_decay must be a finite number >= 0, got {weight_decay!r}") from None
+    if not (math.isfinite(value) and value >= 0.0):
+        raise ValueError(f"weight_decay must be a finite number >= 0, got {weight_decay!r}")
+    if decay_filter is not None and not callable(decay_filter):
+        raise ValueError(f"weight_decay_filter must be None or callable(name, parameter) -> bool, got {decay_filter!r}")
+    return value
 
-    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None):
+
+def default_decay_filter(name, parameter):
+    """Matrices and convolution kernels decay; biases and BatchNorm's weight and bias do not."""
+    return parameter.dim() >= 2
+
+
+class LRSchedule:
+    """Warm-up, then a constant, linearly or cosine-decaying learning rate: step ``s`` (0-based) runs at ``lr * factor(s)``, what
+    ``torch.optim.lr_scheduler.LambdaLR(optimizer, schedule.factor)`` with ``scheduler.step()`` behind every ``optimizer.step()``
+    gives.  ``kind``: 'constant', 'linear' or 'cosine'; the factor rises as (s + 1) / warmup_steps over the first
+    ``warmup_steps`` steps and falls from 1 to ``min_lr_ratio`` between step ``warmup_steps`` and step ``total_steps``, where it
+    stays.  cpc_lr_factors / cpc_adamw_dev evaluate the same function on the device."""
+
+    KINDS = ("constant", "linear", "cosine")
+
+    def __init__(self, kind, warmup_steps=0, total_steps=None, min_lr_ratio=0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"LRSchedule kind must be one of {self.KINDS}, got {kind!r}")
+
+        def whole(value, what):
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise ValueError(f"LRSchedule {what} must be an integer, got {value!r}")
+            return value
+        self.kind = kind
+        self.warmup_steps = whole(warmup_steps, "warmup_steps")
+        if self.warmup_steps < 0:
+            raise ValueError(f"LRSchedule warmup_steps must be >= 0, got {warmup_steps!r}")
+        if total_steps is None:
+            if kind != "constant":
+                raise ValueError(f"LRSchedule('{kind}') needs total_steps")
+        elif whole(total_steps, "total_steps") <= self.warmup_steps:
+            raise ValueError(f"LRSchedule total_steps ({total_steps!r}) must be greater than warmup_steps ({warmup_steps!r})")
+        self.total_steps = total_steps
+        try:
+            self.min_lr_ratio = float(min_lr_ratio)
+        except (TypeError, ValueError):
+            raise ValueError(f"LRSchedule min_lr_ratio must be a number in [0, 1], got {min_lr_ratio!r}") from None
+        if not 0.0 <= self.min_lr_ratio <= 1.0:
+            raise ValueError(f"LRSchedule min_lr_ratio must be in [0, 1], got {min_lr_ratio!r}")
+
+    def factor(self, s):
+        """The factor of the step with 0-based index ``s`` (trainer.training_step), in Python floats."""
+        W, T, r = self.warmup_steps, self.total_steps, self.min_lr_ratio
+        if s < W:
+            return (s + 1) / W
+        if self.kind == "constant":
+            return 1.0
+        q = min((s - W) / (T - W), 1.0)
+        if self.kind == "linear":
+            return r + (1.0 - r) * (1.0 - q)
+        return r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * q))
+
+    def abi_args(self):
+        """(kind, warmup_steps, total_steps, min_ratio) as cpc_lr_factors / cpc_adamw_dev take them."""
+        total = self.total_steps if self.total_steps is not None else self.warmup_steps + 1
+        return self.KINDS.index(self.kind), C.c_longlong(self.warmup_steps), C.c_longlong(total), C.c_float(self.min_lr_ratio)
+
+    def __repr__(self):
+        return (f"LRSchedule({self.kind!r}, warmup_steps={self.warmup_steps}, total_steps={self.total_steps}, "
+                f"min_lr_ratio={self.min_lr_ratio})")
+
+
+class FusedAdam:
+    """torch.optim.Adam (default betas / eps) over the model's flat f32 parameter buffer as one kernel; with ``weight_decay`` > 0
+    torch.optim.AdamW on the parameters ``decay_filter`` selects, with ``schedule`` at the learning rate lr * schedule.factor(step)."""
+
+    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None,
+                 weight_decay: float = 0.0, decay_filter=None, schedule=None, step_offset: int = 0):
         self.model = model
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        # weight_decay / decay_filter / schedule / step_offset (DESIGN.md, "AdamW and the learning-rate schedule").  Step number i of
+        # this object (0-based, counted from construction or from load_state_dict) has the schedule index step_offset + i and runs at
+        # self.lr = base_lr * schedule.factor(index): set here before the step's first launch, on the device under device_step.
+        # decay_bits: one bit per 64-float block of the flat buffer, set for the blocks of the parameters that decay (their
+        # alignment padding included), 32 blocks per int32 word.  Without decay and schedule none of this is allocated or reached.
+        self.weight_decay = check_weight_decay(weight_decay, decay_filter)
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise ValueError(f"schedule must be None or an LRSchedule, got {schedule!r}")
+        if isinstance(step_offset, bool) or not isinstance(step_offset, int) or step_offset < 0:
+            raise ValueError(f"step_offset must be an integer >= 0, got {step_offset!r}")
+        self.base_lr, self.schedule, self.step_offset, self._t0 = self.lr, schedule, step_offset, 0
+        self.decay_bits = self._decay_bitmap(decay_filter or default_decay_filter) if self.weight_decay > 0.0 else None
         flat = model._flat_param
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
@@ -2394,6 +2482,7 @@ class FusedAdam:
         self._piece_scale = float(grad_scale)
         if self.max_grad_norm is not None:          # the update waits for the norm of the whole gradient: step()
             return
+        self._scheduled_lr(self.t)
         self._launch(lo, hi, self.t + 1, grad_scale)
         if self.after_update is not None:
             self.after_update(lo, hi, False)
@@ -2403,9 +2492,84 @@ class FusedAdam:
         if hi <= lo:
             return
         self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
+        if self.decay_bits is not None:          # a range starts at a parameter: a 64-float block of the bitmap
+            assert lo % 64 == 0, f"a decayed range has to start at a 64-float boundary, got {lo}"
+            _hip.call("cpc_adamw", _hip.ptr(flat, lo), _hip.ptr(grad, lo), _hip.ptr(self.m, lo), _hip.ptr(self.v, lo),
+                      C.c_longlong(hi - lo), C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
+                      t, C.c_float(grad_scale), C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(lo // 64), None,
+                      _hip.ptr(self.skip_flag))
+            return
         _hip.call("cpc_adam", _hip.ptr(flat, lo), _hip.ptr(grad, lo), _hip.ptr(self.m, lo), _hip.ptr(self.v, lo), C.c_longlong(hi - lo),
                   C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), t,
                   C.c_float(grad_scale), _hip.ptr(self.skip_flag))
+
+    def _scheduled_lr(self, steps_done):
+        """With a schedule: self.lr becomes the rate of the step that follows ``steps_done`` finished ones."""
+        if self.schedule is not None:
+            self.lr = self.base_lr * self.schedule.factor(self.step_offset + steps_done - self._t0)
+
+    def _decay_bitmap(self, decay_filter):
+        """int32 words on the buffer's device: bit j % 32 of word j // 32 is set when floats [64 j, 64 j + 64) belong to a parameter
+        the filter selects (model._offset puts every parameter at a 64-float boundary; its padding follows it)."""
+        offset, total = self.model._offset, self.model._flat_param.numel()
+        assert total % 64 == 0
+        blocks = total // 64
+        words = [0] * ((blocks + 31) // 32)
+        for name, p in self.model.named_parameters():
+            assert offset[name] % 64 == 0
+            if decay_filter(name, p):
+                for j in range(offset[name] // 64, (offset[name] + p.numel() + 63) // 64):
+                    words[j // 32] |= 1 << (j % 32)
+        signed = [w - (1 << 32) if w >= (1 << 31) else w for w in words]
+        return torch.tensor(signed, dtype=torch.int32).to(self.model._flat_param.device)
+
+    # ---- state in torch.optim.Adam's format
+    def state_dict(self):
+        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [one group]} with i in model.parameters() order, as
+        torch.optim.Adam / AdamW write and load it (copies of the moments; 'lr' is the rate of the latest step)."""
+        state, offset = {}, self.model._offset
+        for i, (name, p) in enumerate(self.model.named_parameters()):
+            lo, n = offset[name], p.numel()
+            state[i] = {"step": torch.tensor(float(self.t)), "exp_avg": self.m[lo:lo + n].view(p.shape).clone(),
+                        "exp_avg_sq": self.v[lo:lo + n].view(p.shape).clone()}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": True, "params": list(range(len(state)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict):
+        """Takes the moments and the step count of a state dict in torch.optim.Adam's format (an empty 'state' — an optimizer that
+        has not stepped — gives zero moments and step 0).  The hyper-parameters stay the constructor's: 'lr' of a scheduled run is
+        one step's rate, not the base rate.  The schedule goes on from ``step_offset`` at the next step.  ValueError for entries
+        that are missing, have the wrong shape, or carry different step counts."""
+        saved, offset = state_dict["state"], self.model._offset
+        named = list(self.model.named_parameters())
+        if saved and sorted(saved) != list(range(len(named))):
+            raise ValueError(f"the state dict has entries {sorted(saved)} for {len(named)} parameters")
+        steps = set()
+        for i, (name, p) in enumerate(named):
+            if not saved:
+                break
+            entry = saved[i]
+            for key in ("exp_avg", "exp_avg_sq"):
+                if tuple(entry[key].shape) != tuple(p.shape):
+                    raise ValueError(f"{key} of parameter {i} ({name}) has shape {tuple(entry[key].shape)}, expected {tuple(p.shape)}")
+            steps.add(int(entry["step"]))
+        if len(steps) > 1:
+            raise ValueError(f"the parameters carry different step counts {sorted(steps)}; this optimizer keeps one")
+        with torch.no_grad():
+            self.m.zero_()
+            self.v.zero_()
+            for i, (name, p) in enumerate(named):
+                if not saved:
+                    break
+                lo, n = offset[name], p.numel()
+                self.m[lo:lo + n].view(p.shape).copy_(saved[i]["exp_avg"])
+                self.v[lo:lo + n].view(p.shape).copy_(saved[i]["exp_avg_sq"])
+            self.t = self._t0 = steps.pop() if steps else 0
+            self._done_lo = None
+            if self.state is not None:          # cpc_adam_dev keeps the count as the bits of an int
+                self.state[0:1].copy_(torch.tensor([self.t], dtype=torch.int32).view(torch.float32))
 
     def _clipped_update(self, grad_scale):
         """Norm of grad_scale * (whole flat gradient) — under data parallelism the gradient summed over the ranks, the same on every
@@ -2415,11 +2579,18 @@ class FusedAdam:
         self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
         _hip.call("cpc_grad_norm", _hip.ptr(grad), n, C.c_float(grad_scale), C.c_float(self.max_grad_norm), _hip.ptr(self._clip_ws),
                   _hip.ptr(self.clip_state), _hip.ptr(self.nan_pair))
+        if self.decay_bits is not None:
+            _hip.call("cpc_adamw", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), n, C.c_float(self.lr),
+                      C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, C.c_float(grad_scale),
+                      C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(0), _hip.ptr(self.clip_state, 1),
+                      _hip.ptr(self.skip_flag))
+            return
         _hip.call("cpc_adam_clip", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), n, C.c_float(self.lr),
                   C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, C.c_float(grad_scale),
                   _hip.ptr(self.clip_state, 1), _hip.ptr(self.skip_flag))
 
     def step(self, grad_scale: float = 1.0):
+        self._scheduled_lr(self.t)
         self.t += 1
         flat, grad = self.model._flat_param, self.model._flat_grad
         if self.max_grad_norm is not None:
@@ -2438,7 +2609,23 @@ class FusedAdam:
             if self.after_update is not None:
                 self.after_update(0, hi, True)
             return
+        if self.decay_bits is not None and self.state is None:          # the whole buffer as one decayed range
+            self._launch(0, flat.numel(), self.t, grad_scale)
+            if self.after_update is not None:
+                self.after_update(0, flat.numel(), True)
+            return
         self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
+        if self.state is not None and (self.decay_bits is not None or self.schedule is not None):
+            # the device evaluates the schedule at (its step count - 1) + offset: the count starts at _t0 where step_offset does
+            offset = self.step_offset - self._t0
+            if offset < 0:
+                raise ValueError(f"device_step: the loaded step count {self._t0} lies beyond step_offset {self.step_offset}")
+            sched = self.schedule.abi_args() if self.schedule is not None else LRSchedule("constant").abi_args()
+            _hip.call("cpc_adamw_dev", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), C.c_longlong(flat.numel()),
+                      C.c_float(self.base_lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
+                      _hip.ptr(self.state), C.c_float(grad_scale), C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), *sched,
+                      C.c_longlong(offset), None, _hip.ptr(self.skip_flag))
+            return
         if self.state is not None:
             _hip.call("cpc_adam_dev", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), C.c_longlong(flat.numel()),
                       C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),

@@ -706,6 +706,43 @@ int cpc_grad_norm(const float* g, long long n, float grad_scale, float max_norm,
 int cpc_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                   int step, float grad_scale, const float* coef, const float* skip, void* stream);
 
+
+/* AdamW and the learning-rate schedule: torch.optim.AdamW's decoupled weight decay in cpc_adam's update, and the factor of a
+ * torch.optim.lr_scheduler.LambdaLR (not in the reference's train step, which runs Adam at one constant lr without decay;
+ * DESIGN.md, "AdamW and the learning-rate schedule").
+ * cpc_adamw: cpc_adam (coef == NULL) or cpc_adam_clip (coef given: the gradient is (g * grad_scale) * coef[0], in that order)
+ * with the decay in front: a decayed element does p <- p * decay first, decay = (float)(1 - (double)lr * weight_decay), then
+ * the Adam update with the new moments; gradient and moments do not see the decay.  lr is the step's learning rate (the
+ * caller has multiplied the schedule's factor in).
+ *   decay_bits: device pointer, one bit per 64-float block of the WHOLE flat buffer (parameters start at 64-float boundaries):
+ *   bit j % 32 of word j / 32 covers floats [64 j, 64 j + 64); a set bit decays.  p, g, m, v point at the start of block
+ *   first_block (a range that begins at float lo passes first_block = lo / 64, lo a multiple of 64); the words up to block
+ *   first_block + (n - 1) / 64 are read.  decay_bits may be NULL when weight_decay == 0 (it is not read then).
+ * With weight_decay == 0, or on an undecayed block, the results are cpc_adam's bits without coef and cpc_adam_clip's with
+ * coef wherever g * grad_scale is exact (grad_scale 1 or a power of two).  skip as in cpc_adam.
+ * CPC_EINVAL before any launch: n <= 0, step < 1, weight_decay negative or not finite, weight_decay > 0 with decay_bits NULL,
+ * first_block < 0, p, g, m or v NULL. */
+int cpc_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+              float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
+              const float* skip, void* stream);
+/* The same update over the whole buffer (first_block 0) with the step count on the device, as cpc_adam_dev: the argument list
+ * never changes from step to step, so the launch can be captured.  A one-thread kernel advances state[0] (unless skip is
+ * raised) to the count t and writes, in double, with f = the schedule's factor at step index step_offset + t - 1:
+ *   state[1] = lr f / (1 - beta1^t), state[2] = 1 / sqrt(1 - beta2^t), state[3] = 1 - lr f weight_decay;
+ * the streaming kernel is cpc_adamw's and reads the three from state.  kind: 0 constant, 1 linear, 2 cosine (see
+ * cpc_lr_factors; kind 0 with warmup_steps 0 is a constant lr).  coef must be NULL (clipped steps are not captured).
+ * CPC_EINVAL: cpc_adamw's cases, state NULL, coef given, step_offset < 0, an invalid schedule. */
+int cpc_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                  float* state, float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
+                  long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip, void* stream);
+/* out[i] = (float) factor(step0 + i), i < count (out: device pointer) — the function cpc_adamw_dev's tick evaluates, in double:
+ *   s < warmup_steps: (s + 1) / warmup_steps;  kind 0: 1;  q = min((s - warmup_steps) / (total_steps - warmup_steps), 1);
+ *   kind 1: r + (1 - r)(1 - q);  kind 2: r + (1 - r) * 0.5 * (1 + cos(pi q)),  r = min_ratio.
+ * CPC_EINVAL: kind outside 0..2, warmup_steps < 0, total_steps <= warmup_steps unless kind 0, min_ratio outside [0, 1] or NaN,
+ * step0 < 0, count <= 0, out NULL. */
+int cpc_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count,
+                   float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

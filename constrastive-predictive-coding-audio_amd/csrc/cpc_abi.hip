@@ -610,8 +610,8 @@ int cpc_split3_bf16(const float* src, void* dst, long long n, void* stream) {
 
 int cpc_adam_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
                  float grad_scale, const float* skip, void* stream) {
-    if (!p || !g || !m || !v || !state) return CPC_EINVAL;
-    return launch_adam_dev(p, g, m, v, n, lr, b1, b2, eps, state, grad_scale, skip, (hipStream_t)stream);
+    return launch_adam_dev({p, g, m, v, n, lr, b1, b2, eps, grad_scale, skip, nullptr, 0.f, nullptr, 0}, state, false, 0, 0, 0, 0.f, 0,
+                           (hipStream_t)stream);
 }
 
 int cpc_cast2d(const float* src, void* dst, int R, int C, long long sr, long long sc, int dtype, void* stream) {
@@ -757,8 +757,7 @@ int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, i
 
 int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
              float grad_scale, const float* skip, void* stream) {
-    if (!p || !g || !m || !v) return CPC_EINVAL;
-    return launch_adam(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, skip, (hipStream_t)stream);
+    return launch_adam({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, nullptr, 0.f, nullptr, 0}, step, false, (hipStream_t)stream);
 }
 
 long long cpc_grad_norm_workspace_floats(long long n) { return grad_norm_workspace_floats(n); }
@@ -770,22 +769,21 @@ int cpc_grad_norm(const float* g, long long n, float grad_scale, float max_norm,
 
 int cpc_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
                   float grad_scale, const float* coef, const float* skip, void* stream) {
-    if (!p || !g || !m || !v) return CPC_EINVAL;
-    return launch_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, coef, skip, (hipStream_t)stream);
+    return launch_adam({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, coef, 0.f, nullptr, 0}, step, true, (hipStream_t)stream);
 }
 
 int cpc_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
               float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
               const float* skip, void* stream) {
-    return launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, weight_decay, decay_bits, first_block, coef, skip,
-                        (hipStream_t)stream);
+    return launch_adam({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, coef, weight_decay, decay_bits, first_block}, step, false,
+                       (hipStream_t)stream);
 }
 
 int cpc_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                   float* state, float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
                   long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip, void* stream) {
-    return launch_adamw_dev(p, g, m, v, n, lr, beta1, beta2, eps, state, grad_scale, weight_decay, decay_bits, kind, warmup_steps,
-                            total_steps, min_ratio, step_offset, coef, skip, (hipStream_t)stream);
+    return launch_adam_dev({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, coef, weight_decay, decay_bits, 0}, state, true, kind,
+                           warmup_steps, total_steps, min_ratio, step_offset, (hipStream_t)stream);
 }
 
 int cpc_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,

@@ -169,20 +169,20 @@ int launch_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const
 int launch_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
                              hipStream_t stream);
 int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype, hipStream_t stream);
-int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                float grad_scale, const float* skip, hipStream_t stream);
 long long grad_norm_workspace_floats(long long n);
 int launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,
                      hipStream_t stream);
-int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                     float grad_scale, const float* coef, const float* skip, hipStream_t stream);
-int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                 float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
-                 const float* skip, hipStream_t stream);
-int launch_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
-                     float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
-                     long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip,
-                     hipStream_t stream);
+// One optimizer update as the cpc_adam* entry points give it (pointwise.hip): coef NULL, weight_decay 0, decay_bits NULL and first_block 0
+// where an entry point has no such argument.
+struct AdamArgs {
+    float* p; const float* g; float* m; float* v; long long n;
+    float lr, b1, b2, eps, grad_scale;
+    const float* skip; const float* coef;
+    float weight_decay; const unsigned* decay_bits; long long first_block;
+};
+int launch_adam(const AdamArgs& a, int step, bool clip, hipStream_t stream);
+int launch_adam_dev(const AdamArgs& a, float* state, bool adamw, int kind, long long warmup_steps, long long total_steps, float min_ratio,
+                    long long step_offset, hipStream_t stream);
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
                       hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);
@@ -276,8 +276,6 @@ int launch_bn_gp_cross(const void* x, const void* yt, const void* delta, void* o
 int launch_relu_mask(void* g, const void* y, long long n, int dtype, hipStream_t stream);
 int launch_accumulate(void* a, const void* b, long long n, int dtype, hipStream_t stream);
 int launch_split3_bf16(const float* src, void* dst, long long n, hipStream_t stream);
-int launch_adam_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
-                    float grad_scale, const float* skip, hipStream_t stream);
 
 // first block of the scalogram encoder on the float32 input (stem.hip): the convolution is recomputed, never stored
 int launch_stem_supported(int cin, int cout, int kh, int kw, int sh, int hin, int ph);

@@ -7,41 +7,6 @@
 
 namespace {
 
-// torch.optim.Adam (no weight decay, no amsgrad):  m = m + (g - m)(1 - b1);  v = b2 v + (1 - b2) g^2;
-// p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).   g is pre-multiplied by grad_scale (1 / world size for DP means).
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n, float step_size, float b1, float b2,
-                                                   float eps, float inv_bc2_sqrt, float grad_scale, const float* __restrict__ skip) {
-    // NaN guard (contrastive_estimation_training.py:124-133 returns BEFORE backward() / optimizer.step()): the loss kernel raises
-    // *skip when the loss is NaN and this update becomes a no-op — parameters and moments keep their last good values
-    if (skip && skip[0] != 0.f) return;
-    const long long n4 = n / 4;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        // gradient and moments are touched once per step: non-temporal, so that 130 MB of them per step do not push the activations and
-        // gradients the backward GEMMs are working on out of the Infinity Cache (the parameters are read again by the layout kernels)
-        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
-              vv = __builtin_nontemporal_load((f32x4*)v + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ge = gg[e] * grad_scale;
-            mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
-            vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
-            const float denom = sqrtf(vv[e]) * inv_bc2_sqrt + eps;
-            pp[e] = pp[e] - step_size * (mm[e] / denom);
-        }
-        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
-    }
-    // tail
-    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float ge = g[i] * grad_scale;
-        const float mm = m[i] + (ge - m[i]) * (1.f - b1);
-        const float vv = v[i] * b2 + (1.f - b2) * ge * ge;
-        m[i] = mm; v[i] = vv;
-        p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
-    }
-}
-
 // Conv weight W[co][c][tap] (f32, reference layout) ->
 //   fwd  [co][(j, c)]            : gemm_nt Bt operand of the forward conv       (K = kw * Cin)
 //   dgrd [(r, c)][(dd, co)]      : gemm_nt Bt operand of the data gradient      (K = D * Cout), tap = r + (D-1-dd)*stride,
@@ -229,43 +194,6 @@ __global__ __launch_bounds__(256) void relu_row_bwd_kernel(const float* __restri
 
 }  // namespace
 
-// Step counter kept on the device (so that a captured hipGraph can be replayed): state[0] = step count (as float bits of an
-// int), state[1] = lr / (1 - b1^t), state[2] = 1 / sqrt(1 - b2^t).
-__global__ void adam_tick_kernel(float* __restrict__ state, float lr, float b1, float b2, const float* __restrict__ skip) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (skip && skip[0] != 0.f) return;
-    int t = __float_as_int(state[0]) + 1;
-    state[0] = __int_as_float(t);
-    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-    state[1] = (float)((double)lr / bc1);
-    state[2] = (float)(1.0 / sqrt(bc2));
-}
-__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long long n, const float* __restrict__ state, float b1,
-                                                       float b2, float eps, float grad_scale, const float* __restrict__ skip) {
-    if (skip && skip[0] != 0.f) return;
-    const float step_size = state[1], inv_bc2_sqrt = state[2];
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float ge = g[i] * grad_scale;
-        const float mm = m[i] + (ge - m[i]) * (1.f - b1);
-        const float vv = v[i] * b2 + (1.f - b2) * ge * ge;
-        m[i] = mm; v[i] = vv;
-        p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
-    }
-}
-
-int launch_adam_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
-                    float grad_scale, const float* skip, hipStream_t stream) {
-    if (n <= 0 || !state) return CPC_EINVAL;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, stream, state, lr, b1, b2, skip);
-    const int blocks = (int)min((long long)2048, (n + 255) / 256);
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, (const float*)state, b1, b2, eps, grad_scale,
-                       skip);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
-}
-
 // ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_; include/cpc_hip.h, cpc_grad_norm / cpc_adam_clip) ----
 // Stage 1: a workgroup takes GN_TILE = 256 threads x GN_CHAIN 16-byte loads = 8 192 consecutive floats; thread t reads the float4s
 // t, t + 256, ... of the tile (contiguous over the wave) and keeps four f32 chains acc[e] = fma(x, x, acc[e]) of GN_CHAIN links each,
@@ -342,41 +270,6 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __res
     if (bad && nan_pair) { nan_pair[0] = 1.f; nan_pair[1] = 1.f; }
 }
 
-// adam_kernel with the gradient (g * grad_scale) * coef[0], multiplied in that order: with coef[0] == 1.0f the second product is exact
-// and the update is cpc_adam's.  (A kernel of its own: adam_kernel stays as it is, bit for bit.)
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long long n, float step_size, float b1, float b2,
-                                                        float eps, float inv_bc2_sqrt, float grad_scale, const float* __restrict__ coef,
-                                                        const float* __restrict__ skip) {
-    if (skip && skip[0] != 0.f) return;
-    const float cf = coef[0];
-    const long long n4 = n / 4;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        // same access pattern as adam_kernel: gradient and moments non-temporal, the parameters are read again by the layout kernels
-        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
-              vv = __builtin_nontemporal_load((f32x4*)v + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gs = gg[e] * grad_scale;
-            const float ge = gs * cf;
-            mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
-            vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
-            const float denom = sqrtf(vv[e]) * inv_bc2_sqrt + eps;
-            pp[e] = pp[e] - step_size * (mm[e] / denom);
-        }
-        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
-    }
-    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float gs = g[i] * grad_scale;
-        const float ge = gs * cf;
-        const float mm = m[i] + (ge - m[i]) * (1.f - b1);
-        const float vv = v[i] * b2 + (1.f - b2) * ge * ge;
-        m[i] = mm; v[i] = vv;
-        p[i] = p[i] - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
-    }
-}
-
 long long grad_norm_workspace_floats(long long n) {
     if (n <= 0) return 0;
     return std::max(1LL, (n / 4 + GN_TILE4 - 1) / GN_TILE4);          // one partial per workgroup
@@ -395,20 +288,7 @@ int launch_grad_norm(const float* g, long long n, float grad_scale, float max_no
     return CPC_OK;
 }
 
-int launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                     float grad_scale, const float* coef, const float* skip, hipStream_t stream) {
-    if (n <= 0 || step < 1 || !coef) return CPC_EINVAL;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt,
-                       grad_scale, coef, skip);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
-}
-
-// ---- AdamW and the learning-rate schedule (torch.optim.AdamW + LambdaLR; include/cpc_hip.h, cpc_adamw / cpc_adamw_dev / cpc_lr_factors) ----
+// ---- the learning-rate schedule (torch.optim.lr_scheduler.LambdaLR; include/cpc_hip.h, cpc_lr_factors / cpc_adamw_dev) ----
 // LRSchedule.factor(s) of engine.py in double: s is the 0-based index of the step, kind 0 constant / 1 linear / 2 cosine.
 __device__ __forceinline__ double lr_factor(int kind, long long warmup, long long total, double min_ratio, long long s) {
     if (s < warmup) return (double)(s + 1) / (double)warmup;
@@ -424,132 +304,9 @@ __global__ void lr_factors_kernel(int kind, long long warmup, long long total, f
     if (i < count) out[i] = (float)lr_factor(kind, warmup, total, (double)min_ratio, step0 + i);
 }
 
-// adam_tick_kernel with the schedule and the decay: state[0] = step count t (int bits), state[1] = lr f / (1 - b1^t),
-// state[2] = 1 / sqrt(1 - b2^t), state[3] = 1 - lr f wd, with f = factor(step_offset + t - 1).
-__global__ void adamw_tick_kernel(float* __restrict__ state, float lr, float b1, float b2, float weight_decay, int kind,
-                                  long long warmup, long long total, float min_ratio, long long step_offset,
-                                  const float* __restrict__ skip) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (skip && skip[0] != 0.f) return;
-    int t = __float_as_int(state[0]) + 1;
-    state[0] = __int_as_float(t);
-    const double lrs = (double)lr * lr_factor(kind, warmup, total, (double)min_ratio, step_offset + t - 1);
-    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-    state[1] = (float)(lrs / bc1);
-    state[2] = (float)(1.0 / sqrt(bc2));
-    state[3] = (float)(1.0 - lrs * (double)weight_decay);
-}
-
-// One 16-byte piece / one tail element of the update.  COEF = false has adam_kernel's expressions, COEF = true adam_clip_kernel's;
-// the decay is a select in front of them (never an operand of their subtraction), so that an undecayed element keeps their bits.
-template <bool COEF>
-__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, long long n, float step_size, float b1, float b2, float eps,
-                                           float inv_bc2_sqrt, float grad_scale, float decay, const unsigned* __restrict__ bits,
-                                           long long first_block, float cf) {
-    const long long n4 = n / 4;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        // a float4 lies inside one 64-float block: 16 consecutive lanes share the word (one cached 4-byte load)
-        const long long blk = first_block + (i >> 4);
-        const bool dec = bits && ((bits[blk >> 5] >> (unsigned)(blk & 31)) & 1u);
-        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
-              vv = __builtin_nontemporal_load((f32x4*)v + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float pd = dec ? pp[e] * decay : pp[e];
-            if (COEF) {
-                const float gs = gg[e] * grad_scale;
-                const float ge = gs * cf;
-                mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
-                vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
-            } else {
-                const float ge = gg[e] * grad_scale;
-                mm[e] = mm[e] + (ge - mm[e]) * (1.f - b1);
-                vv[e] = vv[e] * b2 + (1.f - b2) * ge * ge;
-            }
-            const float denom = sqrtf(vv[e]) * inv_bc2_sqrt + eps;
-            pp[e] = pd - step_size * (mm[e] / denom);
-        }
-        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
-    }
-    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const long long blk = first_block + (i >> 6);
-        const bool dec = bits && ((bits[blk >> 5] >> (unsigned)(blk & 31)) & 1u);
-        const float pd = dec ? p[i] * decay : p[i];
-        float mm, vv;
-        if (COEF) {
-            const float gs = g[i] * grad_scale;
-            const float ge = gs * cf;
-            mm = m[i] + (ge - m[i]) * (1.f - b1);
-            vv = v[i] * b2 + (1.f - b2) * ge * ge;
-        } else {
-            const float ge = g[i] * grad_scale;
-            mm = m[i] + (ge - m[i]) * (1.f - b1);
-            vv = v[i] * b2 + (1.f - b2) * ge * ge;
-        }
-        m[i] = mm; v[i] = vv;
-        p[i] = pd - step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
-    }
-}
-
-// The one streaming kernel of cpc_adamw and cpc_adamw_dev: with ``state`` the three step scalars come from the device
-// (adamw_tick_kernel), otherwise from the arguments.  bits == nullptr: nothing decays.
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long long n, float step_size, float b1, float b2, float eps,
-                                                    float inv_bc2_sqrt, float grad_scale, float decay,
-                                                    const unsigned* __restrict__ bits, long long first_block,
-                                                    const float* __restrict__ state, const float* __restrict__ coef,
-                                                    const float* __restrict__ skip) {
-    if (skip && skip[0] != 0.f) return;
-    if (state) { step_size = state[1]; inv_bc2_sqrt = state[2]; decay = state[3]; }
-    if (coef)
-        adamw_body<true>(p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale, decay, bits, first_block, coef[0]);
-    else
-        adamw_body<false>(p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale, decay, bits, first_block, 1.f);
-}
-
 static bool lr_schedule_ok(int kind, long long warmup, long long total, float min_ratio) {
     if (kind < 0 || kind > 2 || warmup < 0 || !(min_ratio >= 0.f && min_ratio <= 1.f)) return false;
     return kind == 0 || total > warmup;
-}
-
-static bool adamw_args_ok(const float* p, const float* g, const float* m, const float* v, long long n, float weight_decay,
-                          const unsigned* decay_bits, long long first_block) {
-    if (!p || !g || !m || !v || n <= 0 || first_block < 0) return false;
-    if (!(weight_decay >= 0.f) || !(weight_decay <= 3.402823466e38f)) return false;          // negative, NaN or inf
-    return !(weight_decay > 0.f && !decay_bits);
-}
-
-int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                 float grad_scale, float weight_decay, const unsigned* decay_bits, long long first_block, const float* coef,
-                 const float* skip, hipStream_t stream) {
-    if (!adamw_args_ok(p, g, m, v, n, weight_decay, decay_bits, first_block) || step < 1) return CPC_EINVAL;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt, grad_scale,
-                       decay, weight_decay > 0.f ? decay_bits : (const unsigned*)nullptr, first_block, (const float*)nullptr, coef, skip);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
-}
-
-int launch_adamw_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float* state,
-                     float grad_scale, float weight_decay, const unsigned* decay_bits, int kind, long long warmup_steps,
-                     long long total_steps, float min_ratio, long long step_offset, const float* coef, const float* skip,
-                     hipStream_t stream) {
-    if (!adamw_args_ok(p, g, m, v, n, weight_decay, decay_bits, 0) || !state || coef || step_offset < 0 ||
-        !lr_schedule_ok(kind, warmup_steps, total_steps, min_ratio))
-        return CPC_EINVAL;
-    hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, stream, state, lr, b1, b2, weight_decay, kind, warmup_steps, total_steps,
-                       min_ratio, step_offset, skip);
-    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, 0.f, b1, b2, eps, 0.f, grad_scale, 1.f,
-                       weight_decay > 0.f ? decay_bits : (const unsigned*)nullptr, 0LL, (const float*)state, (const float*)nullptr, skip);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
 }
 
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
@@ -561,17 +318,130 @@ int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, f
     return CPC_OK;
 }
 
-int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step,
-                float grad_scale, const float* skip, hipStream_t stream) {
-    if (n <= 0 || step < 1) return CPC_EINVAL;
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    const int blocks = (int)min((long long)2048, (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, step_size, b1, b2, eps, inv_bc2_sqrt,
-                       grad_scale, skip);
+// ---- Adam / AdamW (include/cpc_hip.h: cpc_adam, cpc_adam_clip, cpc_adamw, cpc_adam_dev, cpc_adamw_dev) ----
+// torch.optim.Adam (no amsgrad):  m = m + (g - m)(1 - b1);  v = b2 v + (1 - b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),
+// with g pre-multiplied by grad_scale (1 / world size for DP means) and, for torch.optim.AdamW, p <- p (1 - lr wd) in front.
+// The scalars of one step: step_size = lr / (1 - b1^t), inv_bc2_sqrt = 1 / sqrt(1 - b2^t), decay = 1 - lr wd, cf = clipping coefficient.
+struct AdamStep { float step_size, inv_bc2_sqrt, decay, b1, b2, eps, grad_scale, cf; };
+
+// The update of one element, the only copy of it: all five entry points give the same bits because they run this text.
+// COEF: the gradient is (g * grad_scale) * cf, in that order (cf == 1 is exact), otherwise g * grad_scale, which the compiler contracts
+// into the first-moment update — a compile-time choice, so that neither form changes the other's roundings.  DECAY: the decay is a
+// select in front of the update (never an operand of its subtraction), so that an undecayed element keeps the plain update's bits.
+template <bool COEF, bool DECAY>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, bool dec, const AdamStep& k) {
+    const float pd = (DECAY && dec) ? p * k.decay : p;
+    float ge = g * k.grad_scale;
+    if (COEF) ge = ge * k.cf;
+    m = m + (ge - m) * (1.f - k.b1);
+    v = v * k.b2 + (1.f - k.b2) * ge * ge;
+    p = pd - k.step_size * (m / (sqrtf(v) * k.inv_bc2_sqrt + k.eps));
+}
+
+// bit blk % 32 of word blk / 32: does the 64-float block blk of the flat buffer decay?
+__device__ __forceinline__ bool decay_bit(const unsigned* __restrict__ bits, long long blk) {
+    return (bits[blk >> 5] >> (unsigned)(blk & 31)) & 1u;
+}
+
+// The one streaming kernel of the five entry points: <false, false> is cpc_adam's and carries no bitmap load and no select, COEF reads
+// the coefficient from coef[0], DECAY the bitmap (p points at block first_block).  With ``state`` the step scalars come from the device
+// (adam_tick_kernel), otherwise from the arguments.  (The scalars are separate kernel arguments, not an AdamStep: with the struct as
+// the argument the compiler pairs the tail's products differently and rounds its second moment another way.)
+template <bool COEF, bool DECAY>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, long long n, float step_size, float b1, float b2, float eps,
+                                                   float inv_bc2_sqrt, float grad_scale, float decay, const float* __restrict__ state,
+                                                   const float* __restrict__ coef, const unsigned* __restrict__ bits,
+                                                   long long first_block, const float* __restrict__ skip) {
+    // NaN guard (contrastive_estimation_training.py:124-133 returns BEFORE backward() / optimizer.step()): the loss kernel raises
+    // *skip when the loss is NaN and this update becomes a no-op — parameters and moments keep their last good values
+    if (skip && skip[0] != 0.f) return;
+    AdamStep k = {step_size, inv_bc2_sqrt, decay, b1, b2, eps, grad_scale, 1.f};
+    if (state) { k.step_size = state[1]; k.inv_bc2_sqrt = state[2]; if (DECAY) k.decay = state[3]; }
+    if (COEF) k.cf = coef[0];
+    const long long n4 = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        // a float4 lies inside one 64-float block: 16 consecutive lanes share the bitmap word (one cached 4-byte load)
+        const bool dec = DECAY ? decay_bit(bits, first_block + (i >> 4)) : false;
+        // gradient and moments are touched once per step: non-temporal, so that 130 MB of them per step do not push the activations and
+        // gradients the backward GEMMs are working on out of the Infinity Cache (the parameters are read again by the layout kernels)
+        f32x4 pp = ((f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i), mm = __builtin_nontemporal_load((f32x4*)m + i),
+              vv = __builtin_nontemporal_load((f32x4*)v + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = pp[e], me = mm[e], ve = vv[e];
+            adam_update<COEF, DECAY>(pe, gg[e], me, ve, dec, k);
+            pp[e] = pe; mm[e] = me; vv[e] = ve;
+        }
+        ((f32x4*)p)[i] = pp; __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
+    }
+    // tail: at most three elements
+    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const bool dec = DECAY ? decay_bit(bits, first_block + (i >> 6)) : false;
+        float pe = p[i], me = m[i], ve = v[i];
+        adam_update<COEF, DECAY>(pe, g[i], me, ve, dec, k);
+        m[i] = me; v[i] = ve; p[i] = pe;
+    }
+}
+
+// Step counter kept on the device (so that a captured hipGraph can be replayed): state[0] = step count t (as float bits of an int),
+// state[1] = lr f / (1 - b1^t), state[2] = 1 / sqrt(1 - b2^t) and, with write_decay, state[3] = 1 - lr f wd, f = factor(step_offset + t - 1).
+// cpc_adam_dev is the constant schedule (f is exactly 1.0) without write_decay: state[3] stays as the caller left it.
+__global__ void adam_tick_kernel(float* __restrict__ state, float lr, float b1, float b2, float weight_decay, int write_decay, int kind,
+                                 long long warmup, long long total, float min_ratio, long long step_offset,
+                                 const float* __restrict__ skip) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (skip && skip[0] != 0.f) return;
+    int t = __float_as_int(state[0]) + 1;
+    state[0] = __int_as_float(t);
+    const double lrs = (double)lr * lr_factor(kind, warmup, total, (double)min_ratio, step_offset + t - 1);
+    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+    state[1] = (float)(lrs / bc1);
+    state[2] = (float)(1.0 / sqrt(bc2));
+    if (write_decay) state[3] = (float)(1.0 - lrs * (double)weight_decay);
+}
+
+template <bool COEF, bool DECAY>
+static void adam_launch(const AdamArgs& a, float step_size, float inv_bc2_sqrt, float decay, const float* state, int blocks,
+                        hipStream_t stream) {
+    hipLaunchKernelGGL((adam_kernel<COEF, DECAY>), dim3(blocks), dim3(256), 0, stream, a.p, a.g, a.m, a.v, a.n, step_size, a.b1, a.b2, a.eps,
+                       inv_bc2_sqrt, a.grad_scale, decay, state, a.coef, a.decay_bits, a.first_block, a.skip);
+}
+
+// The streaming launch of every entry point: COEF = a coefficient is given, DECAY = weight_decay > 0 (the bitmap is not read otherwise).
+static int adam_stream(const AdamArgs& a, float step_size, float inv_bc2_sqrt, float decay, const float* state, hipStream_t stream) {
+    const int blocks = (int)min((long long)2048, (a.n / 4 + 255) / 256 + 1);
+    const bool decays = a.weight_decay > 0.f;
+    (a.coef ? (decays ? adam_launch<true, true> : adam_launch<true, false>)
+            : (decays ? adam_launch<false, true> : adam_launch<false, false>))(a, step_size, inv_bc2_sqrt, decay, state, blocks, stream);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
+}
+
+// What every entry point refuses (include/cpc_hip.h); cpc_adam, cpc_adam_clip and cpc_adam_dev come with weight_decay 0 and first_block 0.
+static bool adam_args_ok(const AdamArgs& a) {
+    if (!a.p || !a.g || !a.m || !a.v || a.n <= 0 || a.first_block < 0) return false;
+    if (!(a.weight_decay >= 0.f) || !(a.weight_decay <= 3.402823466e38f)) return false;          // negative, NaN or inf
+    return !(a.weight_decay > 0.f && !a.decay_bits);
+}
+
+// Host-side step count: cpc_adam, cpc_adam_clip (clip: the coefficient is not optional) and cpc_adamw.
+int launch_adam(const AdamArgs& a, int step, bool clip, hipStream_t stream) {
+    if (!adam_args_ok(a) || step < 1 || (clip && !a.coef)) return CPC_EINVAL;
+    const double bc1 = 1.0 - pow((double)a.b1, step), bc2 = 1.0 - pow((double)a.b2, step);
+    return adam_stream(a, (float)((double)a.lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - (double)a.lr * (double)a.weight_decay),
+                       nullptr, stream);
+}
+
+// Device-side step count: cpc_adam_dev (adamw false: the constant schedule, state[3] untouched) and cpc_adamw_dev.
+int launch_adam_dev(const AdamArgs& a, float* state, bool adamw, int kind, long long warmup_steps, long long total_steps, float min_ratio,
+                    long long step_offset, hipStream_t stream) {
+    if (!adam_args_ok(a) || !state || a.coef || step_offset < 0 || !lr_schedule_ok(kind, warmup_steps, total_steps, min_ratio))
+        return CPC_EINVAL;
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, stream, state, a.lr, a.b1, a.b2, a.weight_decay, adamw ? 1 : 0, kind,
+                       warmup_steps, total_steps, min_ratio, step_offset, a.skip);
+    return adam_stream(a, 0.f, 0.f, 1.f, state, stream);
 }
 
 // Operands of a tall (kh,1) convolution computed G output rows per GEMM row (scalogram_engine._col_group): G shifted copies of the kernel

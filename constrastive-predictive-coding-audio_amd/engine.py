@@ -2483,25 +2483,40 @@ class FusedAdam:
         if self.max_grad_norm is not None:          # the update waits for the norm of the whole gradient: step()
             return
         self._scheduled_lr(self.t)
-        self._launch(lo, hi, self.t + 1, grad_scale)
+        self._update(lo, hi, self.t + 1, grad_scale)
         if self.after_update is not None:
             self.after_update(lo, hi, False)
 
-    def _launch(self, lo, hi, t, grad_scale):
-        flat, grad = self.model._flat_param, self.model._flat_grad
+    def _update(self, lo, hi, t, grad_scale, coef=None):
+        """The one place that issues the update of flat_param[lo:hi) as step ``t``.  Host-side step count: cpc_adamw when a decay
+        bitmap is set, else cpc_adam_clip when ``coef`` (device pointer to the clipping coefficient) is given, else cpc_adam.
+        device_step: cpc_adamw_dev when decay or a schedule is set (the device evaluates the schedule from the base rate), else
+        cpc_adam_dev; both keep the count themselves and ignore ``t``."""
         if hi <= lo:
             return
-        self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
-        if self.decay_bits is not None:          # a range starts at a parameter: a 64-float block of the bitmap
+        model, dev, decayed = self.model, self.state is not None, self.decay_bits is not None
+        model._raw_updates = getattr(model, "_raw_updates", 0) + 1
+        dev_schedule = dev and (decayed or self.schedule is not None)
+        head = [_hip.ptr(x, lo) for x in (model._flat_param, model._flat_grad, self.m, self.v)]
+        head += [C.c_longlong(hi - lo), C.c_float(self.base_lr if dev_schedule else self.lr), C.c_float(self.betas[0]),
+                 C.c_float(self.betas[1]), C.c_float(self.eps), _hip.ptr(self.state) if dev else t, C.c_float(grad_scale)]
+        if dev_schedule:
+            # the device evaluates the schedule at (its step count - 1) + offset: the count starts at _t0 where step_offset does
+            offset = self.step_offset - self._t0
+            if offset < 0:
+                raise ValueError(f"device_step: the loaded step count {self._t0} lies beyond step_offset {self.step_offset}")
+            sched = self.schedule.abi_args() if self.schedule is not None else LRSchedule("constant").abi_args()
+            name, tail = "cpc_adamw_dev", [C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), *sched, C.c_longlong(offset), None]
+        elif dev:
+            name, tail = "cpc_adam_dev", []
+        elif decayed:          # a range starts at a parameter: a 64-float block of the bitmap
             assert lo % 64 == 0, f"a decayed range has to start at a 64-float boundary, got {lo}"
-            _hip.call("cpc_adamw", _hip.ptr(flat, lo), _hip.ptr(grad, lo), _hip.ptr(self.m, lo), _hip.ptr(self.v, lo),
-                      C.c_longlong(hi - lo), C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                      t, C.c_float(grad_scale), C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(lo // 64), None,
-                      _hip.ptr(self.skip_flag))
-            return
-        _hip.call("cpc_adam", _hip.ptr(flat, lo), _hip.ptr(grad, lo), _hip.ptr(self.m, lo), _hip.ptr(self.v, lo), C.c_longlong(hi - lo),
-                  C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), t,
-                  C.c_float(grad_scale), _hip.ptr(self.skip_flag))
+            name, tail = "cpc_adamw", [C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(lo // 64), coef]
+        elif coef is not None:
+            name, tail = "cpc_adam_clip", [coef]
+        else:
+            name, tail = "cpc_adam", []
+        _hip.call(name, *head, *tail, _hip.ptr(self.skip_flag))
 
     def _scheduled_lr(self, steps_done):
         """With a schedule: self.lr becomes the rate of the step that follows ``steps_done`` finished ones."""
@@ -2571,71 +2586,29 @@ class FusedAdam:
             if self.state is not None:          # cpc_adam_dev keeps the count as the bits of an int
                 self.state[0:1].copy_(torch.tensor([self.t], dtype=torch.int32).view(torch.float32))
 
-    def _clipped_update(self, grad_scale):
-        """Norm of grad_scale * (whole flat gradient) — under data parallelism the gradient summed over the ranks, the same on every
-        rank — then Adam on the clipped gradient.  Both launches are queued; nothing is read back here."""
-        flat, grad = self.model._flat_param, self.model._flat_grad
-        n = C.c_longlong(flat.numel())
-        self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
-        _hip.call("cpc_grad_norm", _hip.ptr(grad), n, C.c_float(grad_scale), C.c_float(self.max_grad_norm), _hip.ptr(self._clip_ws),
-                  _hip.ptr(self.clip_state), _hip.ptr(self.nan_pair))
-        if self.decay_bits is not None:
-            _hip.call("cpc_adamw", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), n, C.c_float(self.lr),
-                      C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, C.c_float(grad_scale),
-                      C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(0), _hip.ptr(self.clip_state, 1),
-                      _hip.ptr(self.skip_flag))
-            return
-        _hip.call("cpc_adam_clip", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), n, C.c_float(self.lr),
-                  C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, C.c_float(grad_scale),
-                  _hip.ptr(self.clip_state, 1), _hip.ptr(self.skip_flag))
+    def _grad_norm(self, grad_scale):
+        """Queues the norm of grad_scale * (whole flat gradient) — under data parallelism the gradient summed over the ranks, the same
+        on every rank — and returns the device pointer to the clipping coefficient.  Nothing is read back here."""
+        grad = self.model._flat_grad
+        _hip.call("cpc_grad_norm", _hip.ptr(grad), C.c_longlong(grad.numel()), C.c_float(grad_scale), C.c_float(self.max_grad_norm),
+                  _hip.ptr(self._clip_ws), _hip.ptr(self.clip_state), _hip.ptr(self.nan_pair))
+        return _hip.ptr(self.clip_state, 1)
 
     def step(self, grad_scale: float = 1.0):
         self._scheduled_lr(self.t)
         self.t += 1
-        flat, grad = self.model._flat_param, self.model._flat_grad
-        if self.max_grad_norm is not None:
-            if self._done_lo is not None and float(grad_scale) != self._piece_scale:
-                raise ValueError(f"the pieces of this step were recorded with grad_scale {self._piece_scale}, step() got {grad_scale}")
-            self._done_lo = None
-            self._clipped_update(grad_scale)
-            if self.after_update is not None:
-                self.after_update(0, flat.numel(), True)
-            return
-        if self._done_lo is not None:          # ranges [done_lo, end) were updated by hook() during the backward pass
-            hi, self._done_lo = self._done_lo, None
+        hi, clip = self.model._flat_param.numel(), self.max_grad_norm is not None
+        if self._done_lo is not None:          # hook() / update_range() ran during the backward pass
+            if not clip:                       # and updated [done_lo, end): the head of the buffer is left
+                hi, self._done_lo = self._done_lo, None
             if float(grad_scale) != self._piece_scale:
-                raise ValueError(f"the pieces of this step were updated with grad_scale {self._piece_scale}, step() got {grad_scale}")
-            self._launch(0, hi, self.t, grad_scale)
-            if self.after_update is not None:
-                self.after_update(0, hi, True)
-            return
-        if self.decay_bits is not None and self.state is None:          # the whole buffer as one decayed range
-            self._launch(0, flat.numel(), self.t, grad_scale)
-            if self.after_update is not None:
-                self.after_update(0, flat.numel(), True)
-            return
-        self.model._raw_updates = getattr(self.model, "_raw_updates", 0) + 1
-        if self.state is not None and (self.decay_bits is not None or self.schedule is not None):
-            # the device evaluates the schedule at (its step count - 1) + offset: the count starts at _t0 where step_offset does
-            offset = self.step_offset - self._t0
-            if offset < 0:
-                raise ValueError(f"device_step: the loaded step count {self._t0} lies beyond step_offset {self.step_offset}")
-            sched = self.schedule.abi_args() if self.schedule is not None else LRSchedule("constant").abi_args()
-            _hip.call("cpc_adamw_dev", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), C.c_longlong(flat.numel()),
-                      C.c_float(self.base_lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                      _hip.ptr(self.state), C.c_float(grad_scale), C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), *sched,
-                      C.c_longlong(offset), None, _hip.ptr(self.skip_flag))
-            return
-        if self.state is not None:
-            _hip.call("cpc_adam_dev", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), C.c_longlong(flat.numel()),
-                      C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                      _hip.ptr(self.state), C.c_float(grad_scale), _hip.ptr(self.skip_flag))
-            return
-        _hip.call("cpc_adam", _hip.ptr(flat), _hip.ptr(grad), _hip.ptr(self.m), _hip.ptr(self.v), C.c_longlong(flat.numel()),
-                  C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t,
-                  C.c_float(grad_scale), _hip.ptr(self.skip_flag))
-        if self.after_update is not None:
-            self.after_update(0, flat.numel(), True)
+                raise ValueError(f"the pieces of this step were {'recorded' if clip else 'updated'} with grad_scale "
+                                 f"{self._piece_scale}, step() got {grad_scale}")
+            self._done_lo = None
+        coef = self._grad_norm(grad_scale) if clip else None
+        self._update(0, hi, self.t, grad_scale, coef)
+        if self.after_update is not None and self.state is None:
+            self.after_update(0, hi, True)
 
 
 class GraphedStep:

@@ -675,7 +675,11 @@ int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, i
  * skip (device pointer to one float, or NULL): the reference's NaN guard returns BEFORE backward() / optimizer.step()
  * (contrastive_estimation_training.py:124-133), so a NaN loss leaves the parameters at their last good values.  Here the update
  * is issued without waiting for the host to read the loss: while *skip != 0 — pass out + 6 of cpc_nce_loss / cpc_nce_loss_all,
- * the sticky NaN flag — the call changes nothing (p, m, v and the device-side step count keep their values). */
+ * the sticky NaN flag — the call changes nothing (p, m, v and the device-side step count keep their values).
+ * p, g, m and v must be 16-byte aligned, here and in cpc_adam_dev, cpc_adam_clip, cpc_adamw and cpc_adamw_dev (the five run one
+ * kernel, which moves them as float4; whole torch buffers, and ranges of them that start at a multiple of four floats, are).
+ * CPC_EINVAL before any launch: p, g, m or v NULL, n <= 0, step < 1; cpc_adam_clip: the same and coef NULL; cpc_adam_dev: p, g, m, v
+ * or state NULL, n <= 0. */
 int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
              int step, float grad_scale, const float* skip, void* stream);
 /* The same update with the step count kept on the device: state f32[4] = {step count (int bits), lr/(1-b1^t), 1/sqrt(1-b2^t), -},

@@ -208,6 +208,51 @@ def test_adamw_dev_counts_and_schedules_on_the_device():
     assert (p.cpu() - p0).abs().max().item() > 1e-3          # ... and five updates were applied
 
 
+@pytest.mark.parametrize("scale", [1.0, 0.5])
+@pytest.mark.parametrize("entry", ["cpc_adam_dev", "cpc_adamw_dev"])
+def test_device_step_entry_points_carry_the_host_step_bits(entry, scale):
+    """cpc_adam_dev next to cpc_adam, cpc_adamw_dev (constant schedule, weight_decay 0.1, a random bitmap) next to cpc_adamw: three
+    steps from a zeroed state and non-zero moments, every step of both from the same parameters and moments.  Step 1: state[1],
+    state[2] and, for cpc_adamw_dev, state[3] are bitwise the floats of the host formulas on the f32 values of lr / betas / decay
+    (pow(x, 1) is exact, so one correctly rounded double division / square root and one rounding to float is all there is), and
+    p, m, v are the host-step entry point's bits.  Steps 2 and 3: the same comparison wherever the scalars agree with the host's."""
+    n = 2048 + 7
+    lr, b1, b2, wd = (float(np.float32(x)) for x in (1e-3, B1, B2, 0.1))
+    decays = entry == "cpc_adamw_dev"
+    gen = torch.Generator().manual_seed(17)
+    _, words = _bitmap("random", -(-n // 64), seed=17)
+    start = (torch.randn(n, generator=gen), torch.randn(n, generator=gen) * 0.1, torch.rand(n, generator=gen) * 0.01)
+    dev, host = [_guarded_copy(t) for t in start], [_guarded(n) for _ in start]
+    (state, sw), compared = _guarded(4), 0
+    for t in range(1, 4):
+        g, gw = _guarded_copy(torch.randn(n, generator=gen) * 2.0)
+        for (h, _), (d, _) in zip(host, dev):
+            h.copy_(d)
+        (p, _), (m, _), (v, _) = dev
+        (q, _), (qm, _), (qv, _) = host
+        if decays:
+            _hip.call(entry, *_args(p, g, m, v, lr, _hip.ptr(state), scale), F(wd), _hip.ptr(words), *LRSchedule("constant").abi_args(),
+                      L(0), None, None)
+            _hip.call("cpc_adamw", *_args(q, g, qm, qv, lr, t, scale), F(wd), _hip.ptr(words), L(0), None, None)
+        else:
+            _hip.call(entry, *_args(p, g, m, v, lr, _hip.ptr(state), scale), None)
+            _hip.call("cpc_adam", *_args(q, g, qm, qv, lr, t, scale), None)
+        torch.cuda.synchronize()
+        assert _intact(sw, gw, *(w for _, w in dev + host)), t
+        st = state.cpu().numpy()
+        assert int(st[:1].view(np.int32)[0]) == t and (decays or st[3] == 0.0)
+        want = [lr / (1.0 - b1 ** t), 1.0 / math.sqrt(1.0 - b2 ** t)] + ([1.0 - lr * wd] if decays else [])
+        agree = [np.float32(w).tobytes() == st[1 + i].tobytes() for i, w in enumerate(want)]
+        print(f"{entry} scale {scale} step {t}: state[1:4] = {st[1:4].tolist()}, host {want}, bitwise equal {agree}")
+        assert t > 1 or all(agree), (st[1:4].tolist(), want)
+        if all(agree):
+            compared += 1
+            for (d, _), (h, _), name in zip(dev, host, "pmv"):
+                assert torch.equal(d, h), (name, t)
+    print(f"{entry} scale {scale}: {compared} of 3 steps compared bit for bit")
+    assert (dev[0][0].cpu() - start[0]).abs().max().item() > 1e-3          # ... and the updates were applied
+
+
 # ------------------------------------------------------------------------------------------ engine / trainer against the oracle
 def _load(golden_dir, name):
     z = np.load(os.path.join(golden_dir, name))

@@ -104,13 +104,15 @@ class Recorder(FusedAdam):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.launches, self.aheads, self.sync, self.total = [], [], None, None
-    def _launch(self, lo, hi, t, grad_scale):
-        raise AssertionError(f"a piecewise update [{lo}, {hi}) was launched although clipping is on")
-    def _clipped_update(self, grad_scale):
+    def _grad_norm(self, grad_scale):
         g = self.model._flat_grad
         assert self.sync.pending == [] and self.sync.split is None          # finish() has waited for every piece
         assert torch.equal(g, self.total), "the norm would be taken of a gradient that is not reduced yet"
-        self.launches.append((0, g.numel(), grad_scale, float((g.double() * grad_scale).norm())))
+        self.norm = float((g.double() * grad_scale).norm())
+        return "coef"
+    def _update(self, lo, hi, t, grad_scale, coef=None):
+        assert coef == "coef", f"a piecewise update [{lo}, {hi}) was launched although clipping is on"
+        self.launches.append((lo, hi, grad_scale, self.norm))
 
 m = Model()
 m._flat_param = torch.zeros(N)

@@ -27,7 +27,8 @@ cpc_nce_loss_all, (B, K), R = B K
   (257, 12)  R = 3084: second (to fourth) trip of the <12> gradient kernel; one dtype and score function
 neighbours
   cpc_gp_score_coeff (1, 520, 520): 270 400 elements > 1024 blocks x 256: second grid-stride trip; (3, 5, 7): rows != cols
-  cpc_adam_dev n = 2048 x 256 + 3: second trip of the grid capped at 2048 blocks
+  cpc_adam_dev n = 4 x 2048 x 256 + 7: second trip of the float4 loop of the grid capped at 2048 blocks (n / 4 > 2048 x 256) and a
+             three-element scalar tail; cpc_adam beside it runs the same kernel
   cpc_nce_eval's loops: the (70, 2) and (257, 1) cases of tests/test_audio_kernels_gpu.py::test_nce_eval_against_oracle
 
 Bounds: the ones tests/test_hip_kernels.py carries for these kernels (test_nce_loss, test_adam_matches_torch): loss 2e-5 relative,
@@ -460,7 +461,7 @@ def test_adam_dev_three_steps_against_float64():
     """Three cpc_adam_dev steps from a zeroed state next to three cpc_adam calls with step = 1, 2, 3, both against
     oracle.adam_update in float64 on the values the kernels receive (lr and the betas as f32).  state[0] holds the step count as int
     bits; state[1] = lr / (1 - b1^t) and state[2] = 1 / sqrt(1 - b2^t) are one float rounding of a double result: 2^-23 relative."""
-    n = 2048 * 256 + 3
+    n = 4 * 2048 * 256 + 7
     g = torch.Generator().manual_seed(0)
     lr, b1, b2, eps = (float(np.float32(x)) for x in (1e-3, 0.9, 0.999, 1e-8))
     p0 = torch.randn(n, generator=g)

@@ -9,6 +9,8 @@ Prints one JSON line per measurement:
            spread) and with both set in between.
   plain    the two default runs and cpc_adam alone: this part touches nothing the change added, so the same file measures the
            parent commit.
+  dev      one whole-buffer cpc_adam against one whole-buffer cpc_adam_dev (its one-thread tick kernel and the update), alternating
+           like `kernels`.
 
 Usage: python tools/adamw_bench.py [--batch 256] [--weight-decay 0.01] [--parts kernels,trainer]
 """
@@ -72,6 +74,26 @@ def kernel_times(args, device, with_adamw):
     if with_adamw:
         row.update({"cpc_adamw_us": us_w, "cpc_adamw_GB_per_s": gbs(us_w, 4 * bits.numel())})
     print(json.dumps(row), flush=True)
+
+
+def dev_times(args, device):
+    n, P, L, F = args.n, _hip.ptr, C.c_longlong, C.c_float
+    gen = torch.Generator(device=device).manual_seed(1)
+    g = torch.randn(n, device=device, generator=gen) * 1e-3
+    p, m, v = torch.randn(n, device=device, generator=gen), torch.zeros(n, device=device), torch.zeros(n, device=device)
+    state = torch.zeros(4, device=device)
+
+    def adam():
+        _hip.call("cpc_adam", P(p), P(g), P(m), P(v), L(n), F(1e-4), F(0.9), F(0.999), F(1e-8), 1, F(1.0), None)
+
+    def adam_dev():
+        _hip.call("cpc_adam_dev", P(p), P(g), P(m), P(v), L(n), F(1e-4), F(0.9), F(0.999), F(1e-8), P(state), F(1.0), None)
+
+    us_a, us_d = [], []
+    for _ in range(args.rounds):
+        us_a.append(round(_time(adam, args.launches) * 1e3, 2))
+        us_d.append(round(_time(adam_dev, args.launches) * 1e3, 2))
+    print(json.dumps({"part": "dev", "n": n, "launches": args.launches, "cpc_adam_us": us_a, "cpc_adam_dev_us": us_d}), flush=True)
 
 
 def trainer_ms(args, device, on, tag):
@@ -143,6 +165,8 @@ def main():
         kernel_times(args, device, False)
         trainer_ms(args, device, False, "default A")
         trainer_ms(args, device, False, "default B")
+    if "dev" in parts:
+        dev_times(args, device)
 
 
 if __name__ == "__main__":

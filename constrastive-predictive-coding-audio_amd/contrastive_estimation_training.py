@@ -13,10 +13,12 @@ DeterministicSampler :363-382, grad_mean_var :385-391).  ``train`` has two route
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import random
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 import torch.optim
@@ -25,7 +27,8 @@ import torch.utils.data
 from .audio_model import *          # noqa: F401,F403  (the reference re-exports the model names from here)
 from .audio_dataset import FileBatchSampler
 from . import switches
-from .sampled_negatives import check_negatives, sampled_negative_mask          # noqa: F401  (public: the host restatement)
+from .sampled_negatives import (check_negatives, empty_negative_sets, file_group_ids, group_mode,        # noqa: F401
+                                grouped_negative_mask, sampled_negative_mask)                                        # (public: the host restatements)
 from .engine import LRSchedule          # noqa: F401  (public: trainer.lr_schedule takes one)
 
 
@@ -264,6 +267,62 @@ class _SampledInfoNCE(torch.autograd.Function):
         return d.to(dtype), None, None, None, None
 
 
+class _GroupedInfoNCE(torch.autograd.Function):
+    """_SampledInfoNCE's twin for candidates by group id (cpc_nce_loss_grouped; DESIGN.md, "Grouped negatives"): the generic route's
+    loss when ContrastiveEstimationTrainer.negative_groups is set.  groups: int32 device tensor [B]; mode 0 = same, 1 = other; n_neg 0
+    = every eligible row.  Same returns as _InfoNCE."""
+
+    @staticmethod
+    def forward(ctx, scores4, regularization, groups, mode, n_neg, seed, draw):
+        import ctypes as C
+        from . import _hip
+        _need_gpu(scores4, "the InfoNCE loss over grouped negatives")
+        B, K = scores4.shape[0], scores4.shape[1]
+        S, ld = _score_layout(scores4.detach(), False)
+        dev, f32 = S.device, torch.float32
+        if groups.dtype != torch.int32 or tuple(groups.shape) != (B,) or groups.device != dev:
+            raise ValueError(f"groups must be an int32 tensor of shape [{B}] on {dev}")
+        groups = groups.contiguous()
+        out = torch.zeros(8, device=dev, dtype=f32)
+        dS, dST = torch.zeros_like(S), torch.zeros_like(S)
+        ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(B, K)), device=dev, dtype=f32)
+        _hip.call("cpc_nce_loss_grouped", _hip.ptr(S), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
+                  C.c_float(regularization), _hip.ptr(groups), int(mode), int(n_neg), C.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+                  C.c_ulonglong(int(draw) & (2 ** 64 - 1)), _hip.F32)
+        ctx.save_for_backward(dS)
+        ctx.meta = (B, K, scores4.dtype)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_out):
+        (dS,) = ctx.saved_tensors
+        B, K, dtype = ctx.meta
+        d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
+        torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
+        return d.to(dtype), None, None, None, None, None, None
+
+
+class _RecordingSampler:
+    """Hands out a batch sampler's index lists and appends each to ``fifo`` first: whoever consumes the batches in order (a DataLoader
+    reads its sampler ahead of the batch it yields) finds the indices of the batch in hand at the front."""
+
+    def __init__(self, inner, fifo):
+        self.inner, self.fifo = inner, fifo
+
+    def __iter__(self):
+        for idx in self.inner:
+            idx = [int(i) for i in idx]
+            self.fifo.append(idx)
+            yield idx
+
+    def __len__(self):
+        return len(self.inner)
+
+
+_NEGATIVE_GROUP_MODES = {"same_file": "same", "other_files": "other"}
+
+
 class ContrastiveEstimationTrainer:
     def __init__(self, model, dataset, logger=None, device=None,
                  regularization=1., validation_set=None, test_task_set=None, prediction_noise=0.01,
@@ -311,6 +370,16 @@ class ContrastiveEstimationTrainer:
         # Default loss branch only; validate() stays in-batch, as the reference measures accuracy.
         self.num_negatives = None
         self.negative_seed = 0
+        # Not in the reference's signature: restrict every target's negatives by a group id per example ("Grouped
+        # negatives").  negative_groups: None (every other batch item is a candidate), "same_file" (only items with the target's id)
+        # or "other_files" (only items with another id).  negative_group_ids: None — the id of an example is the index of its file in
+        # dataset.get_example_count_per_file() — or a 1-D integer sequence of len(dataset), speaker ids for instance.  Composes with
+        # num_negatives: a target then keeps min(num_negatives, eligible) seeded rows of its eligible set.  A target without eligible
+        # rows contributes 0 to the loss; last_empty_negative_sets holds how many items of the latest step's batch had none.
+        # Default loss branch only; validate() stays in-batch.
+        self.negative_groups = None
+        self.negative_group_ids = None
+        self.last_empty_negative_sets = None
         # Not in the reference's signature: clip the gradient to this global L2 norm before the update, as
         # torch.nn.utils.clip_grad_norm_ in front of optimizer.step() (None: no clipping, the reference's step).  On the fused routes
         # the norm and the clipped Adam are HIP kernels (engine.FusedAdam(max_grad_norm=...)); under data parallelism it is the norm of
@@ -391,6 +460,51 @@ class ContrastiveEstimationTrainer:
             raise NotImplementedError("num_negatives: global_negatives contrasts against the gathered batches of all ranks; the sampler "
                                       "draws from the rank's own batch only")
 
+    def _check_negative_groups(self):
+        """Up-front checks of negative_groups / negative_group_ids (before any GPU work): ValueError for an unknown value, for ids of
+        the wrong kind or length, and for "same_file" over files that give one example per batch; NotImplementedError for what the
+        grouped loss does not cover.  Returns None, or (mode, int32 numpy ids or None for the file index)."""
+        if self.negative_groups is None:
+            return None
+        if self.negative_groups not in _NEGATIVE_GROUP_MODES:
+            raise ValueError(f"negative_groups must be None or one of {tuple(_NEGATIVE_GROUP_MODES)}, got {self.negative_groups!r}")
+        ids = None
+        if self.negative_group_ids is not None:
+            ids = np.asarray(self.negative_group_ids)
+            if ids.ndim != 1 or ids.dtype.kind not in "iu":
+                raise ValueError("negative_group_ids must be None or a 1-D sequence of integers")
+            if ids.size != len(self.dataset):
+                raise ValueError(f"negative_group_ids must have len(dataset) = {len(self.dataset)} entries, got {ids.size}")
+            if ids.size and (int(ids.min()) < -2 ** 31 or int(ids.max()) > 2 ** 31 - 1):
+                raise ValueError("negative_group_ids must fit 32-bit signed integers")
+            ids = ids.astype(np.int32)
+        elif self.negative_groups == "same_file" and int(self.file_batch_size) < 2:
+            raise ValueError("negative_groups='same_file' with the file index as the group id needs file_batch_size >= 2: with one "
+                             "example per file and batch no target would have a negative")
+        if self.score_over_all_timesteps:
+            raise NotImplementedError("negative_groups: defined for score_over_all_timesteps=False only (the groups index the batch "
+                                      "items of one prediction step, not the (item, step) pairs of the all-timesteps branch)")
+        if self.wasserstein_gradient_penalty:
+            raise NotImplementedError("negative_groups: wasserstein_gradient_penalty runs the dense loss kernels in its tangent passes; "
+                                      "grouped negatives are not carried through them")
+        if self.use_graph:
+            raise NotImplementedError("negative_groups: use_graph replays one captured step, but the group ids of a step's batch come "
+                                      "from the host every step")
+        if self.global_negatives:
+            raise NotImplementedError("negative_groups: global_negatives contrasts against the gathered batches of all ranks; the "
+                                      "groups are those of the rank's own batch only")
+        return _NEGATIVE_GROUP_MODES[self.negative_groups], ids
+
+    def _groups_kw(self, grouping, idx, device):
+        """{} without negative_groups; else the step's negative_groups = (int32 device ids of the batch's examples, mode), and
+        last_empty_negative_sets is set from the same ids."""
+        if grouping is None:
+            return {}
+        mode, ids = grouping
+        gid = np.ascontiguousarray(ids[np.asarray(idx, dtype=np.int64)], dtype=np.int32)
+        self.last_empty_negative_sets = empty_negative_sets(gid, mode)
+        return {"negative_groups": (torch.from_numpy(gid).to(device), mode)}
+
     def _check_grad_clip(self):
         """Up-front checks of max_grad_norm (before any GPU work): ValueError unless None or finite and > 0, NotImplementedError
         together with use_graph."""
@@ -425,10 +539,15 @@ class ContrastiveEstimationTrainer:
             return dist.get_rank(), dist.get_world_size()
         return 0, 1
 
-    def _batches(self, dataset, sampler, device, num_workers, pin_memory, rank, world):
+    def _batches(self, dataset, sampler, device, num_workers, pin_memory, rank, world, with_indices=False):
         """Yields device batches (B, L).  A dataset exposing ``device_data`` (an (N, L) tensor already in HBM) is
-        indexed on the device; anything else goes through a torch DataLoader as in the reference (:87-91)."""
+        indexed on the device; anything else goes through a torch DataLoader as in the reference (:87-91).
+        with_indices: yields (batch, the example indices of that batch — this rank's slice under data parallelism) instead."""
         resident = getattr(dataset, "device_data", None)
+        fifo = collections.deque() if with_indices else None
+
+        def out(b):
+            return (b, fifo.popleft()) if with_indices else b
         if world > 1:
             import torch.distributed as dist
             lists = [list(b) for b in iter(sampler)] if rank == 0 else None
@@ -438,16 +557,17 @@ class ContrastiveEstimationTrainer:
             index_lists = [b[rank * per:(rank + 1) * per] for b in box[0]]
         else:
             index_lists = None
+        source = index_lists if index_lists is not None else sampler
+        if with_indices:
+            source = _RecordingSampler(source, fifo)
         if resident is not None:
-            it = index_lists if index_lists is not None else iter(sampler)
-            for idx in it:
-                yield resident[torch.as_tensor(list(idx), device=resident.device)]
+            for idx in iter(source):
+                yield out(resident[torch.as_tensor(list(idx), device=resident.device)])
             return
-        loader = torch.utils.data.DataLoader(dataset, batch_sampler=index_lists if index_lists is not None else sampler,
-                                             num_workers=num_workers, pin_memory=pin_memory)
+        loader = torch.utils.data.DataLoader(dataset, batch_sampler=source, num_workers=num_workers, pin_memory=pin_memory)
         if torch.device(device).type != "cuda":
             for batch in iter(loader):
-                yield batch.to(device=device, non_blocking=True)
+                yield out(batch.to(device=device, non_blocking=True))
             return
         # Host dataset: double-buffered upload.  Batch i + 1 travels pinned host -> HBM on a copy stream while step i computes
         # (21 MB per step at B = 256: 0.3-0.4 ms of PCIe time that would otherwise sit in front of every step).
@@ -471,7 +591,7 @@ class ContrastiveEstimationTrainer:
             cur = torch.cuda.current_stream(device)
             cur.wait_event(done)
             dev_batch.record_stream(cur)
-            yield dev_batch
+            yield out(dev_batch)
 
     # ------------------------------------------------------------------------------------------ train
     def train(self, batch_size=32, epochs=10, lr=0.0001, continue_training_at_step=0, num_workers=1, max_steps=None,
@@ -480,6 +600,7 @@ class ContrastiveEstimationTrainer:
         reached, None on a NaN loss or when the epochs are exhausted.  ``batch_size`` is the per-process batch; under
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
         self._check_negatives(batch_size)
+        grouping = self._check_negative_groups()
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
         device = self._device()
@@ -511,6 +632,8 @@ class ContrastiveEstimationTrainer:
         sampler = FileBatchSampler(index_count_per_file=self.dataset.get_example_count_per_file(),
                                    batch_size=batch_size * world, file_batch_size=self.file_batch_size, drop_last=True,
                                    verbose=self.verbose)
+        if grouping is not None and grouping[1] is None:
+            grouping = (grouping[0], file_group_ids(self.dataset.get_example_count_per_file()))
         self.training_step = continue_training_at_step
         pending = []          # (step, device scalars) not yet read back
         guarded = set()       # engines whose sticky NaN flag was cleared for this run
@@ -643,9 +766,15 @@ class ContrastiveEstimationTrainer:
                 if (fused and not graphed and self.preprocessing is not None and self.preprocess_ahead and device.type == "cuda"
                         and switches.preprocess_ahead()):
                     ahead = InputAhead(self._model_input, device)
-                batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world)
+                batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world,
+                                        with_indices=grouping is not None)
                 # (the sampler is read one batch ahead only where that batch is preprocessed ahead)
                 for batch, next_batch in (_with_next(batches) if ahead is not None else ((b_, None) for b_ in batches)):
+                    groups_kw = {}
+                    if grouping is not None:          # the indices travel with their batch, the one ahead keeps its own
+                        batch, batch_idx = batch
+                        next_batch = next_batch[0] if next_batch is not None else None
+                        groups_kw = self._groups_kw(grouping, batch_idx, device)
                     snapshot(self.training_step)
                     # the step's learning rate, before its first hook can fire (under use_graph the device evaluates the same factor)
                     self.last_lr = step_lr = lr if schedule is None else lr * schedule.factor(self.training_step)
@@ -709,7 +838,7 @@ class ContrastiveEstimationTrainer:
                                                      all_timesteps=bool(self.score_over_all_timesteps),
                                                      grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
                                                      global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
-                                                     score=kind, **self._negatives_kw())
+                                                     score=kind, **self._negatives_kw(), **groups_kw)
                         if sync is not None:
                             sync.finish()
                         # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
@@ -717,7 +846,8 @@ class ContrastiveEstimationTrainer:
                         vals = out
                     else:
                         vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm,
-                                                  (step_lr if schedule is not None else None, step_lr * weight_decay, decayed))
+                                                  (step_lr if schedule is not None else None, step_lr * weight_decay, decayed),
+                                                  **groups_kw)
                     stash(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
                         nan_step = flush()
@@ -749,7 +879,7 @@ class ContrastiveEstimationTrainer:
             return {}
         return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
 
-    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ())):
+    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ()), negative_groups=None):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
         the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133).  With max_grad_norm,
@@ -759,7 +889,11 @@ class ContrastiveEstimationTrainer:
         param group gets the rate, and the decay p <- p (1 - lr weight_decay) is applied right before optimizer.step()."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
-        if self.num_negatives is None:
+        if negative_groups is not None:
+            n_neg, seed, draw = self._negatives_kw().get("negatives", (0, 0, 0))
+            loss, out = _GroupedInfoNCE.apply(scores, float(self.regularization), negative_groups[0], group_mode(negative_groups[1]),
+                                              n_neg, seed, draw)
+        elif self.num_negatives is None:
             loss, out = _InfoNCE.apply(scores, bool(self.score_over_all_timesteps), float(self.regularization))
         else:
             loss, out = _SampledInfoNCE.apply(scores, float(self.regularization), *self._negatives_kw()["negatives"])

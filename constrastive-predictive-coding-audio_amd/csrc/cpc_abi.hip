@@ -685,6 +685,21 @@ int cpc_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned l
     return launch_nce_sample_mask(mask, B, K, n_neg, seed, draw, (hipStream_t)stream);
 }
 
+long long cpc_nce_grouped_workspace_floats(int B, int K) { return nce_grouped_workspace_floats(B, K); }
+
+int cpc_nce_loss_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
+                         float regularization, const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw,
+                         int dtype, void* stream) {
+    if (!S || !dS || !dST || !out || !workspace || !groups) return CPC_EINVAL;
+    return launch_nce_grouped(S, dS, dST, out, workspace, B, K, ld, softplus, regularization, groups, mode, n_neg, seed, draw, dtype,
+                              (hipStream_t)stream);
+}
+
+int cpc_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
+                       unsigned long long draw, void* stream) {
+    return launch_nce_group_mask(mask, groups, B, K, mode, n_neg, seed, draw, (hipStream_t)stream);
+}
+
 int cpc_gp_score_coeff(const float* S, const float* St1, const float* St2, float* W, float* WT, int nmat, int rows, int cols, int ld,
                        int ldT, int mode, void* stream) {
     if (!S || !W || !WT) return CPC_EINVAL;

@@ -156,6 +156,12 @@ int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* w
                        int n_neg, unsigned long long seed, unsigned long long draw, int dtype, hipStream_t stream);
 int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw,
                            hipStream_t stream);
+long long nce_grouped_workspace_floats(int B, int K);
+int launch_nce_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
+                       const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw, int dtype,
+                       hipStream_t stream);
+int launch_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
+                          unsigned long long draw, hipStream_t stream);
 int launch_gp_score_coeff(const float* S, const float* St1, const float* St2, float* W, float* WT, int nmat, int rows, int cols, int ld,
                           int ldT, int mode, hipStream_t stream);
 long long nce_eval_workspace_floats(int B, int K);

@@ -696,7 +696,34 @@ __device__ __forceinline__ bool nsm_member(unsigned long long col_base, int b, i
     return b == bp || (((unsigned long long)nsm_key(col_base, b) << 32) | (unsigned)b) <= thr;
 }
 
-// The selection routine of both entry points.  Called by all 64 lanes of a wave for column (k, b'): fills key[h] for row
+// The search of every selection: called by all 64 lanes of a wave with key[h] of row lane + 64 h and ok bit h set where that row takes
+// part; returns the n-th smallest composite (key << 32 | row) among the rows that take part (1 <= n <= their number).
+template <int H>
+__device__ __forceinline__ unsigned long long nsm_search(unsigned ok, int lane, int n, const unsigned (&key)[H]) {
+    unsigned tk = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = tk | ((1u << bit) - 1u);
+        int cnt = 0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] <= cand));
+        if (cnt < n) tk |= 1u << bit;
+    }
+    int below = 0;
+#pragma unroll
+    for (int h = 0; h < H; ++h) below += __popcll(__ballot(((ok >> h) & 1u) && key[h] < tk));
+    const int need = n - below;                 // >= 1 rows with key == tk belong, the ones with the smallest index
+    unsigned tb = 0;
+    for (int bit = 9; bit >= 0; --bit) {
+        const unsigned cand = tb | ((1u << bit) - 1u);
+        int cnt = 0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] == tk && (unsigned)(lane + 64 * h) <= cand));
+        if (cnt < need) tb |= 1u << bit;
+    }
+    return ((unsigned long long)tk << 32) | tb;
+}
+
+// The selection routine of the sampled entry points.  Called by all 64 lanes of a wave for column (k, b'): fills key[h] for row
 // lane + 64 h and returns the N-th smallest composite among the rows b < B, b != b' (at least n_neg of them exist: n_neg <= B - 1).
 template <int H>
 __device__ __forceinline__ unsigned long long nsm_select(unsigned long long col_base, int lane, int bp, int B, int n_neg,
@@ -708,27 +735,7 @@ __device__ __forceinline__ unsigned long long nsm_select(unsigned long long col_
         key[h] = nsm_key(col_base, row);
         if (row < B && row != bp) ok |= 1u << h;
     }
-    unsigned tk = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = tk | ((1u << bit) - 1u);
-        int cnt = 0;
-#pragma unroll
-        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] <= cand));
-        if (cnt < n_neg) tk |= 1u << bit;
-    }
-    int below = 0;
-#pragma unroll
-    for (int h = 0; h < H; ++h) below += __popcll(__ballot(((ok >> h) & 1u) && key[h] < tk));
-    const int need = n_neg - below;             // >= 1 rows with key == tk belong, the ones with the smallest index
-    unsigned tb = 0;
-    for (int bit = 9; bit >= 0; --bit) {
-        const unsigned cand = tb | ((1u << bit) - 1u);
-        int cnt = 0;
-#pragma unroll
-        for (int h = 0; h < H; ++h) cnt += __popcll(__ballot(((ok >> h) & 1u) && key[h] == tk && (unsigned)(lane + 64 * h) <= cand));
-        if (cnt < need) tb |= 1u << bit;
-    }
-    return ((unsigned long long)tk << 32) | tb;
+    return nsm_search<H>(ok, lane, n_neg, key);
 }
 
 // Column pass of one wave: threshold of column col = k B + b', and the log-sum-exp over its candidates.  The wave-wide max and sum
@@ -838,6 +845,157 @@ __global__ __launch_bounds__(256) void nce_sample_mask_kernel(unsigned char* __r
         const int row = lane + 64 * h;
         if (row < B)
             mask[((long long)k * B + row) * B + bp] = (row == bp || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t) ? 1 : 0;
+    }
+}
+
+// ---- grouped negatives: the sampled chain with candidates restricted by a per-item group id (include/cpc_hip.h, cpc_nce_loss_grouped) ----
+// Row b is ELIGIBLE for column (k, b') when b != b' and (groups[b] == groups[b']) == (mode == same); the column keeps its own row and
+// the n = min(n_neg, |Elig|) eligible rows with the smallest (key, b) (n_neg == 0: all of them).  Eligibility is one more condition
+// on the ok bits of the selection and is tested AGAIN, before the threshold, wherever membership is asked: a column whose eligible
+// set is empty needs no sentinel threshold.
+constexpr unsigned long long NSG_ALL = ~0ull;       // threshold of a column that keeps every eligible row (no composite reaches it: row < 1024)
+
+__device__ __forceinline__ bool nsg_eligible(int g, int gp, int mode) { return (g == gp) == (mode == 0); }
+
+// Called by all 64 lanes of a wave for column (k, b').  ok bit h <- row lane + 64 h is eligible; returns the column's threshold.
+// |Elig| comes from ballots; with n == |Elig| (always when n_neg == 0, and for an empty set) nothing is hashed or searched and key[]
+// stays unset: the branch is wave-uniform, and callers test `t == NSG_ALL ||` before they look at a key.
+template <int H>
+__device__ __forceinline__ unsigned long long nsg_select(const int* __restrict__ groups, int mode, unsigned long long seed,
+                                                         unsigned long long draw, int k, int lane, int bp, int B, int n_neg,
+                                                         unsigned (&key)[H], unsigned& ok_out) {
+    const int gp = groups[bp];
+    unsigned ok = 0;
+    int elig = 0;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int row = lane + 64 * h;
+        const bool e = row < B && row != bp && nsg_eligible(groups[row < B ? row : 0], gp, mode);
+        if (e) ok |= 1u << h;
+        elig += __popcll(__ballot(e));
+    }
+    ok_out = ok;
+    const int n = (n_neg == 0 || n_neg > elig) ? elig : n_neg;
+    if (n == elig) return NSG_ALL;
+    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
+#pragma unroll
+    for (int h = 0; h < H; ++h) key[h] = nsm_key(base, lane + 64 * h);
+    return nsm_search<H>(ok, lane, n, key);
+}
+
+template <int H>
+__device__ __forceinline__ bool nsg_in(int row, int h, int bp, int B, unsigned ok, unsigned long long t, const unsigned (&key)[H]) {
+    if (row >= B) return false;
+    if (row == bp) return true;
+    if (!((ok >> h) & 1u)) return false;
+    return t == NSG_ALL || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t;
+}
+
+// nsm_col_body with the grouped selection (same butterflies, same order of the lane's own sum).
+template <int H>
+__device__ __forceinline__ void nsg_col_body(const float* __restrict__ S, unsigned long long* __restrict__ thr, float* __restrict__ lse,
+                                             int B, int ld, int softplus, const int* __restrict__ groups, int mode, int n_neg,
+                                             unsigned long long seed, unsigned long long draw, int col) {
+    const int lane = threadIdx.x & 63;
+    const int k = col / B, bp = col % B;
+    const float* cp = S + (long long)k * B * ld + bp;
+    float v[H];
+    unsigned key[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) v[h] = (lane + 64 * h < B) ? cp[(long long)(lane + 64 * h) * ld] : 0.f;
+    unsigned ok;
+    const unsigned long long t = nsg_select<H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        v[h] = nsg_in<H>(lane + 64 * h, h, bp, B, ok, t, key) ? score_tf(v[h], softplus) : -INFINITY;
+        mx = fmaxf(mx, v[h]);
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int h = 0; h < H; ++h) sum += (v[h] == mx) ? 1.f : expf(v[h] - mx);          // (as nsm_col_body)
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) {
+        thr[col] = t;
+        lse[col] = mx + logf(sum);
+    }
+}
+
+template <int KT, int H>
+__global__ __launch_bounds__(256) void nce_grouped_col_mean_kernel(const float* __restrict__ S, unsigned long long* __restrict__ thr,
+                                                                   float* __restrict__ lse, float* __restrict__ mean,
+                                                                   float* __restrict__ pairp, int B, int K, int ld, int softplus,
+                                                                   const int* __restrict__ groups, int mode, int n_neg,
+                                                                   unsigned long long seed, unsigned long long draw, int ncb) {
+    if ((int)blockIdx.x < ncb) {
+        const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
+        if (col < K * B) nsg_col_body<H>(S, thr, lse, B, ld, softplus, groups, mode, n_neg, seed, draw, col);     // (wave-uniform)
+    } else {
+        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb);
+    }
+}
+
+// nce_sampled_grad_kernel with the eligibility test in front of the threshold test.
+template <typename T>
+__global__ __launch_bounds__(256) void nce_grouped_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
+                                                               const unsigned long long* __restrict__ thr, const float* __restrict__ mean,
+                                                               T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld, int softplus,
+                                                               float reg, const int* __restrict__ groups, int mode, unsigned long long seed,
+                                                               unsigned long long draw, const float* __restrict__ pairp, int npair,
+                                                               float* __restrict__ out) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
+    const int bp0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
+    const float inv_bk = 1.f / ((float)B * (float)K);
+    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
+    const int k = blockIdx.z;
+    const int bp = bp0 + tx;
+    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
+    const unsigned long long t = bp < B ? thr[k * B + bp] : 0ull;
+    const float l = bp < B ? lse[k * B + bp] : 0.f;
+    const int gp = bp < B ? groups[bp] : 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = b0 + ty + 8 * r;
+        float g = 0.f;
+        if (b < B && bp < B) {
+            const float x = S[((long long)k * B + b) * ld + bp];
+            const float sp = score_tf(x, softplus);
+            float dsp = reg_c * mean[(long long)b * ld + bp];
+            bool in = b == bp;
+            if (!in && nsg_eligible(groups[b], gp, mode))
+                in = t == NSG_ALL || (((unsigned long long)nsm_key(base, b) << 32) | (unsigned)b) <= t;
+            if (in) dsp += expf(sp - l) * inv_bk;
+            if (b == bp) dsp -= inv_bk;
+            g = dsp * score_grad(x, softplus);
+        }
+        if (b < B && bp < ld) dS[((long long)k * B + b) * ld + bp] = from_f32<T>(g);
+        tile[ty + 8 * r][tx] = g;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int bq = bp0 + ty + 8 * r, b = b0 + tx;
+        if (b < ld && bq < B) dST[((long long)k * B + bq) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(lse, K * B, pairp, npair, out, B, K, reg);
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void nce_group_mask_kernel(unsigned char* __restrict__ mask, const int* __restrict__ groups, int B, int K,
+                                                             int mode, int n_neg, unsigned long long seed, unsigned long long draw) {
+    const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
+    if (col >= K * B) return;                   // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    const int k = col / B, bp = col % B;
+    unsigned key[H];
+    unsigned ok;
+    const unsigned long long t = nsg_select<H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int row = lane + 64 * h;
+        if (row < B) mask[((long long)k * B + row) * B + bp] = nsg_in<H>(row, h, bp, B, ok, t, key) ? 1 : 0;
     }
 }
 
@@ -961,6 +1119,51 @@ int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigne
     const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
     if (B <= 256) hipLaunchKernelGGL(nce_sample_mask_kernel<4>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
     else hipLaunchKernelGGL(nce_sample_mask_kernel<16>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+// ---- grouped negatives ---- (workspace laid out as the sampled chain's)
+long long nce_grouped_workspace_floats(int B, int K) { return nce_sampled_workspace_floats(B, K); }
+
+int launch_nce_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
+                       const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw, int dtype,
+                       hipStream_t stream) {
+    if (B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 0 || n_neg > B - 1 || (mode != 0 && mode != 1)) return CPC_EINVAL;
+    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+    unsigned long long* thr = (unsigned long long*)workspace;
+    float* lse = workspace + 2LL * K * B;
+    float* pairp = lse + (long long)K * B;
+    const int nmb = (int)(((long long)B * B + 255) / 256);
+    float* mean = pairp + 3LL * nmb;
+    const int ncb = (K * B + NSM_COLS - 1) / NSM_COLS;
+    const int nb = (ld + 31) / 32;
+    const dim3 g1(ncb + nmb);
+#define NSG_COL(KT, H) \
+    hipLaunchKernelGGL((nce_grouped_col_mean_kernel<KT, H>), g1, dim3(256), 0, stream, S, thr, lse, mean, pairp, B, K, ld, softplus, groups, \
+                       mode, n_neg, seed, draw, ncb)
+    if (B <= 256) {
+        if (K == 12) NSG_COL(12, 4); else if (K == 16) NSG_COL(16, 4); else NSG_COL(0, 4);
+    } else {
+        if (K == 12) NSG_COL(12, 16); else if (K == 16) NSG_COL(16, 16); else NSG_COL(0, 16);
+    }
+#undef NSG_COL
+    if (dtype == CPC_DTYPE_BF16)
+        hipLaunchKernelGGL((nce_grouped_grad_kernel<bf16_t>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (bf16_t*)dS,
+                           (bf16_t*)dST, B, K, ld, softplus, reg, groups, mode, seed, draw, pairp, nmb, out);
+    else
+        hipLaunchKernelGGL((nce_grouped_grad_kernel<float>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (float*)dS,
+                           (float*)dST, B, K, ld, softplus, reg, groups, mode, seed, draw, pairp, nmb, out);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
+                          unsigned long long draw, hipStream_t stream) {
+    if (!mask || !groups || B <= 1 || B > NSM_MAXB || K <= 0 || n_neg < 0 || n_neg > B - 1 || (mode != 0 && mode != 1)) return CPC_EINVAL;
+    const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
+    if (B <= 256) hipLaunchKernelGGL(nce_group_mask_kernel<4>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
+    else hipLaunchKernelGGL(nce_group_mask_kernel<16>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }

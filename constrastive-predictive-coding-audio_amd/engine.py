@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _hip, switches
-from .sampled_negatives import check_negatives
+from .sampled_negatives import check_group_negatives, check_negatives, group_mode
 
 
 _SIDE_STREAMS = {}
@@ -41,10 +41,21 @@ def score_kind(softplus: bool, score: Optional[str] = None) -> str:
     return score
 
 
-def check_negatives_supported(negatives, all_timesteps=False, global_negatives=None, gradient_penalty=None):
-    """Sampled negatives (``negatives = (n_neg, seed, draw)``) exist for the default loss branch on one process's own batch; what
-    they do not cover is refused here, before any launch."""
+def check_negatives_supported(negatives, all_timesteps=False, global_negatives=None, gradient_penalty=None, negative_groups=None):
+    """Sampled negatives (``negatives = (n_neg, seed, draw)``) and grouped negatives (``negative_groups = (groups, mode)``) exist for
+    the default loss branch on one process's own batch; what they do not cover is refused here, before any launch."""
+    if negatives is None and negative_groups is None:
+        return
     if negatives is None:
+        if all_timesteps:
+            raise NotImplementedError("grouped negatives are defined for score_over_all_timesteps=False only: the all-timesteps "
+                                      "branch contrasts every (item, step) pair, and no selection over that set exists")
+        if global_negatives is not None:
+            raise NotImplementedError("grouped negatives are chosen from the process's own batch; with a global_negatives object the "
+                                      "candidates would span the gathered batches of all ranks, whose group ids this rank does not hold")
+        if gradient_penalty is not None:
+            raise NotImplementedError("the gradient penalty's tangent passes run the dense loss kernels; grouped negatives are not "
+                                      "carried through them")
         return
     if all_timesteps:
         raise NotImplementedError("sampled negatives are defined for score_over_all_timesteps=False only: the all-timesteps branch "
@@ -61,6 +72,20 @@ def normalize_negatives(negatives, B):
     """(n_neg, seed, draw) as Python ints the C ABI takes (seed and draw modulo 2^64); ValueError unless 1 <= n_neg <= B - 1."""
     n_neg, seed, draw = negatives
     return check_negatives(B, n_neg), int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
+
+
+def normalize_negative_groups(negative_groups, B, negatives=None):
+    """(groups, mode, n_neg, seed, draw) as cpc_nce_loss_grouped takes them: ``negative_groups = (groups, mode)`` with groups an int32
+    tensor [B] and mode "same" / "other"; ``negatives`` None (n_neg = 0: every eligible row) or (n_neg, seed, draw).  ValueError /
+    TypeError for anything else."""
+    groups, mode = negative_groups
+    mode = group_mode(mode)
+    n_neg, seed, draw = (0, 0, 0) if negatives is None else normalize_negatives(negatives, B)
+    if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int32:
+        raise TypeError("negative_groups: groups must be an int32 tensor")
+    if tuple(groups.shape) != (int(B),) or not groups.is_contiguous():
+        raise ValueError(f"negative_groups: groups must be a contiguous tensor of shape [{int(B)}], got {tuple(groups.shape)}")
+    return groups, mode, check_group_negatives(B, n_neg), seed, draw
 
 
 def side_stream(device):
@@ -569,23 +594,32 @@ class CPCEngine:
                      b_rpi=K, b_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
         return 2.0 * R * R * E
 
-    def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, negatives=None):
+    def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, negatives=None,
+                             negative_groups=None):
         """Equal-step scores, InfoNCE loss + regulariser, and d loss / d (predicted_z, targets).
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
         (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs).
         ``score``: see score_kind; "difference" runs _diff_forward_backward.
         ``negatives``: None, or (n_neg, seed, draw) — every target is contrasted against n_neg seeded negatives instead of the
-        whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask)."""
+        whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask).
+        ``negative_groups``: None, or (groups, mode) — groups an int32 device tensor [B], mode "same" / "other": a target's candidates
+        are the rows of its own group / of the other groups, all of them or, with ``negatives``, n_neg seeded ones
+        (cpc_nce_loss_grouped; sampled_negatives.grouped_negative_mask)."""
         if score_kind(softplus, score) == "difference":
-            return self._diff_forward_backward(False, regularization, negatives)
+            return self._diff_forward_backward(False, regularization, negatives, negative_groups)
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         top, dtop = self.act[-1], self.dact[-1]
-        if negatives is not None:
+        grouped = None
+        if negative_groups is not None:
+            grouped = normalize_negative_groups(negative_groups, B, negatives)
+        elif negatives is not None:
             negatives = normalize_negatives(negatives, B)
         self.score_gemm()
-        if negatives is None:
+        if grouped is not None:
+            self._nce_grouped(self.S, self.dS, self.dST, 1 if softplus else 0, regularization, grouped)
+        elif negatives is None:
             _hip.call("cpc_nce_loss", _hip.ptr(self.S), _hip.ptr(self.dS), _hip.ptr(self.dST), _hip.ptr(self.nce_out),
                       _hip.ptr(self.nce_ws), B, K, ld, 1 if softplus else 0, C.c_float(regularization), code)
         else:
@@ -601,6 +635,16 @@ class CPCEngine:
         P = _hip.ptr
         _hip.call("cpc_nce_loss_sampled", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_sampled_ws), self.B, self.K, self.ldS,
                   softplus, C.c_float(regularization), n_neg, C.c_ulonglong(seed), C.c_ulonglong(draw), self.code)
+
+    def _nce_grouped(self, S, dS, dST, softplus: int, regularization: float, grouped):
+        """cpc_nce_loss_grouped in place of cpc_nce_loss (same buffers and layouts; its workspace is allocated on first use)."""
+        groups, mode, n_neg, seed, draw = grouped
+        if getattr(self, "nce_grouped_ws", None) is None:
+            self.nce_grouped_ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(self.B, self.K)), device=self.device,
+                                              dtype=torch.float32)
+        P = _hip.ptr
+        _hip.call("cpc_nce_loss_grouped", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_grouped_ws), self.B, self.K, self.ldS,
+                  softplus, C.c_float(regularization), P(groups), mode, n_neg, C.c_ulonglong(seed), C.c_ulonglong(draw), self.code)
 
     def _score_grads(self, W, WT, pred, top, out_pred, out_top):
         """The two contractions behind d loss / d (predicted_z, targets) of the default branch, for any coefficients W[k][b][b']
@@ -759,13 +803,17 @@ class CPCEngine:
                   code, work=work)
         return work
 
-    def _diff_forward_backward(self, all_timesteps: bool, regularization: float, negatives=None):
+    def _diff_forward_backward(self, all_timesteps: bool, regularization: float, negatives=None, negative_groups=None):
         """InfoNCE loss + regulariser on difference scores and d loss / d (predicted_z, targets).  The loss kernels take the scores
         as linear scores (softplus = 0, as contrastive_estimation_training._InfoNCE does); with d = |p - t|^2 and s = 1 / d,
         d loss / d d = -g s^2 for g = d loss / d s, so the gradient is the linear score's two contractions with G = 2 g s^2
         minus the rank-1 terms (row / column sums of G) * (p / t): cpc_diff_scores_bwd, _score_grads(_all), cpc_diff_scores_rank1.
         In bf16 storage G is rounded to bf16 (the operand type of the contractions) and its sums are taken of the rounded values."""
-        if negatives is not None:
+        grouped = None
+        if negative_groups is not None:
+            check_negatives_supported(negatives, all_timesteps, negative_groups=negative_groups)
+            grouped = normalize_negative_groups(negative_groups, self.B, negatives)
+        elif negatives is not None:
             check_negatives_supported(negatives, all_timesteps)
             negatives = normalize_negatives(negatives, self.B)
         code, B, E, K = self.code, self.B, self.E, self.K
@@ -790,7 +838,9 @@ class CPCEngine:
                 self.ST = torch.zeros_like(self.S)
             S, ST, dS, dST = self.S, self.ST, self.dS, self.dST
             self.diff_scores(S, ST)
-            if negatives is None:
+            if grouped is not None:
+                self._nce_grouped(S, dS, dST, 0, regularization, grouped)
+            elif negatives is None:
                 _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_ws), B, K, ld, 0, C.c_float(regularization), code)
             else:
                 self._nce_sampled(S, dS, dST, 0, regularization, negatives)
@@ -1055,16 +1105,20 @@ class CPCEngine:
 
     # ------------------------------------------------------------------------------------------ whole step
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
-                       global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None):
+                       global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None, negative_groups=None):
         """Forward + loss + backward; returns the device tensor [loss, max_score, -mean valid, mean lse, reg, NaN indicator of
         this step, sticky NaN flag, -] (no sync; include/cpc_hip.h, cpc_nce_loss).
         ``global_negatives``: a GlobalNegatives object — the loss is then taken over the batches of ALL ranks.
         ``after_loss(nce_out)`` is called once the loss kernels are queued and before the backward pass is: data-parallel runs
         start the reduction of the NaN flag over the ranks there (GradAllReduce.reduce_flag).
         ``score``: "softplus" | "linear" | "difference" (score_kind; None: the ``softplus`` flag decides).
-        ``negatives``: None, or (n_neg, seed, draw): n_neg seeded negatives per target (nce_forward_backward); default branch only."""
+        ``negatives``: None, or (n_neg, seed, draw): n_neg seeded negatives per target (nce_forward_backward); default branch only.
+        ``negative_groups``: None, or (groups, mode): candidates by group id (nce_forward_backward); default branch only."""
         kind = score_kind(softplus, score)
-        if negatives is not None:
+        if negative_groups is not None:
+            check_negatives_supported(negatives, all_timesteps, global_negatives, negative_groups=negative_groups)
+            normalize_negative_groups(negative_groups, self.B, negatives)
+        elif negatives is not None:
             check_negatives_supported(negatives, all_timesteps, global_negatives)
             negatives = normalize_negatives(negatives, self.B)
         if kind == "difference" and global_negatives is not None:
@@ -1076,7 +1130,7 @@ class CPCEngine:
         elif all_timesteps:
             self.nce_all_forward_backward(softplus, regularization, score=kind)
         else:
-            self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives)
+            self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives, negative_groups=negative_groups)
         if after_loss is not None:
             after_loss(self.nce_out)
         self.backward(x, grad_ready_hook=grad_ready_hook)
@@ -2620,7 +2674,10 @@ class GraphedStep:
     (dropout seeds)."""
 
     def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None,
-                 negatives=None):
+                 negatives=None, negative_groups=None):
+        if negative_groups is not None:
+            raise NotImplementedError("grouped negatives take the group ids of each step's batch from the host, which a captured graph "
+                                      "cannot replay")
         if negatives is not None:
             raise NotImplementedError("sampled negatives draw a new set per step from a host-side counter (like dropout's seed), which a "
                                       "captured graph cannot replay")

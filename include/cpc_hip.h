@@ -50,6 +50,8 @@ extern "C" {
  *    cpc_gru_bwd, cpc_gru_gp_fwd and cpc_gru_gp_bwd accept hidden sizes up to 512 (were 256).
  *    Added later under 9 (backward compatible, no entry point changed): the loss over sampled negatives
  *    cpc_nce_sampled_workspace_floats, cpc_nce_loss_sampled, cpc_nce_sample_mask.
+ *    Added later under 9 (backward compatible, no entry point changed): the loss over grouped negatives
+ *    cpc_nce_grouped_workspace_floats, cpc_nce_loss_grouped, cpc_nce_group_mask.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -590,6 +592,29 @@ long long cpc_nce_sampled_workspace_floats(int B, int K);
 int cpc_nce_loss_sampled(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
                          float regularization, int n_neg, unsigned long long seed, unsigned long long draw, int dtype, void* stream);
 int cpc_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw, void* stream);
+
+/* cpc_nce_loss_sampled with the candidates restricted by a per-item group id (not in the reference; DESIGN.md, "Grouped negatives").
+ * groups: B int32 on the device, any values (only equality matters); mode 0 = same, 1 = other; n_neg 0 = every eligible row, else 1 .. B - 1.
+ *   Elig(b')  = { b != b' : (groups[b] == groups[b']) == (mode == 0) }                               (does not depend on k)
+ *   n(b')     = |Elig(b')| if n_neg == 0, else min(n_neg, |Elig(b')|)
+ *   C(k,b')   = {b'} + the n(b') rows of Elig(b') with the smallest (key, b), key the hash of cpc_nce_loss_sampled with the same
+ *               (seed, draw) and B the batch size
+ * Loss, dsp, out[8], the layouts, ld, softplus, dtype and the pad-column zeros are cpc_nce_loss_sampled's with this C (regulariser, max
+ * score and valid scores over ALL scores).  A target whose eligible set is empty has lse = sp[k][b'][b']: it contributes 0 and stays in
+ * the mean.  A column that keeps its whole eligible set (always with n_neg == 0) computes no hash.  One group for the whole batch with
+ * mode 0: n_neg = N selects cpc_nce_sample_mask's sets bit for bit, n_neg = 0 is cpc_nce_loss's loss.
+ * workspace: cpc_nce_grouped_workspace_floats(B,K) f32, 8-byte aligned.
+ * Limits: 2 <= B <= 1024, B <= ld <= B + 7, mode in {0, 1}, 0 <= n_neg <= B - 1; CPC_EINVAL otherwise, for a null pointer (groups
+ * included), for a dtype other than f32 / bf16 and for a workspace that is not 8-byte aligned — before any launch: a refused call
+ * writes nothing.
+ * cpc_nce_group_mask writes the candidate sets by the same device selection routine: mask[k][b][b'] (bytes, no padding) = 1 where b is
+ * in C(k,b') (the diagonal included), else 0. */
+long long cpc_nce_grouped_workspace_floats(int B, int K);
+int cpc_nce_loss_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
+                         float regularization, const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw,
+                         int dtype, void* stream);
+int cpc_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
+                       unsigned long long draw, void* stream);
 
 /* Wasserstein gradient penalty with softplus_score_function (contrastive_estimation_training.py:12-16 under :144-158): the
  * coefficients the penalty's seeds carry.  S (and the tangent scores St1 + St2, St2 may be NULL): nmat f32 matrices [rows][ld].

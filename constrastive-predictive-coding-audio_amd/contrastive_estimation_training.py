@@ -403,6 +403,16 @@ class ContrastiveEstimationTrainer:
         self.lr_schedule = None
         self.optimizer_state = None
         self.last_lr = None
+        # Not in the reference's signature: LAMB's layer-wise trust ratio ("LAMB trust ratios").
+        # trust_ratio: True scales the update of every parameter weight_decay_filter selects by ||p|| / ||u||, u = Adam's direction
+        #   + weight_decay * p (the decay then is part of the direction, not AdamW's multiply in front); the parameters the filter
+        #   leaves out keep Adam's update.  One filter chooses decay and ratio;
+        # trust_clip: None, or the largest ratio applied (finite and > 0).
+        # On the fused routes it is engine.FusedAdam's (cpc_lamb; trainer.last_optimizer.trust_ratios() reads the latest step's norms
+        # and ratios), on the generic route engine.TorchLamb in the place of torch.optim.Adam.  Not with use_graph (no captured LAMB
+        # step) and not with an optimizer other than torch.optim.Adam (a foreign optimizer's direction is not ours to rescale).
+        self.trust_ratio = False
+        self.trust_clip = None
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
         self.preprocess_ahead = True
         self.verbose = True
@@ -527,6 +537,19 @@ class ContrastiveEstimationTrainer:
             raise ValueError("optimizer_state must be None or an optimizer's state dict")
         return value, self.weight_decay_filter, self.lr_schedule
 
+    def _check_trust(self):
+        """Up-front checks of trust_ratio and trust_clip (before any GPU work): ValueError for a trust_ratio that is no bool or a
+        trust_clip that is not None or finite and > 0; with trust_ratio, NotImplementedError together with use_graph or an optimizer
+        other than torch.optim.Adam.  Returns (trust_ratio, trust_clip)."""
+        from .engine import check_trust
+        trust_ratio, trust_clip = check_trust(self.trust_ratio, self.trust_clip)
+        if trust_ratio and self.use_graph:
+            raise NotImplementedError("trust_ratio: use_graph replays one captured step, and no captured LAMB step exists")
+        if trust_ratio and self.optimizer is not torch.optim.Adam:
+            raise NotImplementedError("trust_ratio rescales Adam's direction (optimizer=torch.optim.Adam); the direction of "
+                                      f"{self.optimizer!r} is not ours to rescale")
+        return trust_ratio, trust_clip
+
     def _score_kind(self):
         if self.score_function is difference_score_function:
             return "difference"
@@ -603,6 +626,7 @@ class ContrastiveEstimationTrainer:
         grouping = self._check_negative_groups()
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
+        trust_ratio, trust_clip = self._check_trust()
         device = self._device()
         rank, world = self._world()
         self.model.train()
@@ -612,8 +636,9 @@ class ContrastiveEstimationTrainer:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
             self.model._flatten_parameters(device)
             graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
+            lamb = dict(trust_ratio=True, trust_clip=trust_clip) if trust_ratio else {}
             optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                                  decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step))
+                                  decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step), **lamb)
             self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
             graph_steps = {}
             glob_neg = {}
@@ -621,9 +646,14 @@ class ContrastiveEstimationTrainer:
             sync = GradAllReduce(self.model, optimizer=optimizer) if world > 1 else None
         else:
             self.model._flatten_parameters(device)
-            optimizer = self.optimizer(self.model.parameters(), lr=lr)
+            if trust_ratio:          # LAMB's decay is inside its direction: no multiply in front of the step
+                from .engine import TorchLamb
+                optimizer = TorchLamb(self.model.named_parameters(), lr=lr, weight_decay=weight_decay, decay_filter=decay_filter,
+                                      trust_clip=trust_clip)
+            else:
+                optimizer = self.optimizer(self.model.parameters(), lr=lr)
         decayed = []
-        if weight_decay > 0.0 and not fused:          # the generic route multiplies them itself, in front of optimizer.step()
+        if weight_decay > 0.0 and not fused and not trust_ratio:          # the generic route multiplies them itself, in front of optimizer.step()
             from .engine import default_decay_filter
             decayed = [p for n_, p in self.model.named_parameters() if (decay_filter or default_decay_filter)(n_, p)]
         if self.optimizer_state is not None:

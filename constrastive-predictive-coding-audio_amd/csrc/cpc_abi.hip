@@ -806,4 +806,15 @@ int cpc_lr_factors(int kind, long long warmup_steps, long long total_steps, floa
     return launch_lr_factors(kind, warmup_steps, total_steps, min_ratio, step0, count, out, (hipStream_t)stream);
 }
 
+long long cpc_lamb_workspace_floats(long long total_blocks) { return lamb_workspace_floats(total_blocks); }
+
+int cpc_lamb(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+             float grad_scale, float weight_decay, const unsigned* select_bits, long long first_block, const float* coef,
+             const int* param_block, const int* param_block_dev, const int* block_param, int first_param, int n_params,
+             int total_params, float trust_clip, float* workspace, float* trust, const float* skip, void* stream) {
+    return launch_lamb({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, coef, weight_decay, select_bits, first_block}, step,
+                       {param_block, param_block_dev, block_param, first_param, n_params, total_params, trust_clip, workspace, trust},
+                       (hipStream_t)stream);
+}
+
 }  // extern "C"

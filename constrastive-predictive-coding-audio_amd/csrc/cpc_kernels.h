@@ -189,6 +189,15 @@ struct AdamArgs {
 int launch_adam(const AdamArgs& a, int step, bool clip, hipStream_t stream);
 int launch_adam_dev(const AdamArgs& a, float* state, bool adamw, int kind, long long warmup_steps, long long total_steps, float min_ratio,
                     long long step_offset, hipStream_t stream);
+// What cpc_lamb adds to an update (pointwise.hip): param_block is the HOST copy of the parameter table (read during the call),
+// param_block_dev the same table on the device, block_param the per-block map; a.decay_bits is the selection bitmap.
+struct LambTables {
+    const int* param_block; const int* param_block_dev; const int* block_param;
+    int first_param, n_params, total_params;
+    float trust_clip; float* workspace; float* trust;
+};
+long long lamb_workspace_floats(long long total_blocks);
+int launch_lamb(const AdamArgs& a, int step, const LambTables& t, hipStream_t stream);
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
                       hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);

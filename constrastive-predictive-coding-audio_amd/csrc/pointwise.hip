@@ -444,6 +444,156 @@ int launch_adam_dev(const AdamArgs& a, float* state, bool adamw, int kind, long 
     return adam_stream(a, 0.f, 0.f, 1.f, state, stream);
 }
 
+// ---- LAMB layer-wise trust ratios (include/cpc_hip.h: cpc_lamb; DESIGN.md, "LAMB trust ratios") ----
+// adam_update's moments, then per parameter tensor P:  u = r + wd p (selected) or r,  r = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps);
+// trust = ||p|| / ||u|| where P is selected and both norms are finite and > 0, else 1;  p -= lr * trust * u.  Three launches over a
+// range of whole parameters (n is a multiple of 64: a parameter's alignment padding is zero, gives u = 0 and stays zero):
+//   1. lamb_moments_kernel: m, v, and the sums of p^2 and u^2 of every 64-float block (workspace[2 blk], [2 blk + 1], blk absolute);
+//   2. lamb_ratio_kernel:   one workgroup per parameter adds its blocks' sums and writes trust[0..2][param];
+//   3. lamb_apply_kernel:   u again from the stored m, v and the old p (lamb_direction, the text pass 1 runs), then p.
+// Every sum has a fixed shape and there is no atomic: the same data give the same bits for any grid and any split into ranges.
+// Roundings on the longest path from an element to a parameter's sum of squares (tests/test_lamb_gpu.py computes its bound from them):
+//   4 (a lane's four squares: one product, three fmas) + 4 (xor-shuffle levels 8, 4, 2, 1 inside the block's 16 lanes)
+//   + ceil(blocks / (256 LAMB_CHAINS)) (a thread's chain) + 2 (its LAMB_CHAINS = 4 chains) + 6 (wave tree) + 2 (four waves):
+//   34 for the 16 384 blocks of the headline model's layer-2 kernel.
+struct LambStep { float lr, inv_bc1, inv_bc2_sqrt, wd, b1, b2, eps, grad_scale, cf; };
+constexpr int LAMB_CHAINS = 4;
+
+// The moments of one element: adam_update's formulas with every fma written out and contraction off, so that the COEF and the plain
+// instantiation round alike (left to itself the compiler pairs the second moment's products differently in the two, as it does for
+// adam_kernel's scalar arguments); with cf == 1 and an exact g * grad_scale the two give the same bits.
+template <bool COEF>
+__device__ __forceinline__ void lamb_moments(float g, float& m, float& v, const LambStep& k) {
+#pragma clang fp contract(off)
+    float ge = g * k.grad_scale;
+    if (COEF) ge = ge * k.cf;
+    m = __builtin_fmaf(ge - m, 1.f - k.b1, m);
+    v = __builtin_fmaf((1.f - k.b2) * ge, ge, v * k.b2);
+}
+
+// LAMB's direction of one element, the only copy of it: passes 1 and 3 run this text, with its one fma written out and
+// contraction off, and so give the same bits.
+__device__ __forceinline__ float lamb_direction(float p, float m, float v, bool sel, const LambStep& k) {
+#pragma clang fp contract(off)
+    const float r = (m * k.inv_bc1) / (sqrtf(v) * k.inv_bc2_sqrt + k.eps);
+    return sel ? __builtin_fmaf(k.wd, p, r) : r;
+}
+
+template <bool COEF>
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, long long n4, LambStep k,
+                                                           const float* __restrict__ coef, const unsigned* __restrict__ bits,
+                                                           long long first_block, float* __restrict__ ws,
+                                                           const float* __restrict__ skip) {
+    if (skip && skip[0] != 0.f) return;
+    if (COEF) k.cf = coef[0];
+    // n4 is a multiple of 16 and so is the grid's stride: the 16 lanes of a block enter and leave the loop together
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const long long blk = first_block + (i >> 4);
+        const bool sel = decay_bit(bits, blk);
+        const f32x4 pp = ((const f32x4*)p)[i], gg = __builtin_nontemporal_load((const f32x4*)g + i);
+        f32x4 mm = __builtin_nontemporal_load((f32x4*)m + i), vv = __builtin_nontemporal_load((f32x4*)v + i);
+        float sp = 0.f, su = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float me = mm[e], ve = vv[e];
+            lamb_moments<COEF>(gg[e], me, ve, k);
+            mm[e] = me; vv[e] = ve;
+            const float u = lamb_direction(pp[e], me, ve, sel, k);
+            sp = e ? __builtin_fmaf(pp[e], pp[e], sp) : pp[e] * pp[e];
+            su = e ? __builtin_fmaf(u, u, su) : u * u;
+        }
+        // gradient and moments non-temporal, as in adam_kernel: they must not push the backward GEMMs' operands out of the cache
+        __builtin_nontemporal_store(mm, (f32x4*)m + i); __builtin_nontemporal_store(vv, (f32x4*)v + i);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); su += __shfl_xor(su, o, 64); }
+        if ((threadIdx.x & 15) == 0) ((float2*)ws)[blk] = make_float2(sp, su);
+    }
+}
+
+// One workgroup per parameter of the range: thread t adds the block sums t + 256 c into chain c % LAMB_CHAINS, in that order.
+// trust[0][q] = ||p||, trust[1][q] = ||u||, trust[2][q] = the ratio pass 3 applies (rows of total_params floats).
+__global__ __launch_bounds__(256) void lamb_ratio_kernel(const float* __restrict__ ws, const int* __restrict__ param_block,
+                                                         int first_param, int total_params, const unsigned* __restrict__ bits,
+                                                         float trust_clip, float* __restrict__ trust, const float* __restrict__ skip) {
+    __shared__ float lds_p[4], lds_u[4];
+    if (skip && skip[0] != 0.f) return;
+    const int q = first_param + blockIdx.x;
+    const int b0 = param_block[q], b1 = param_block[q + 1];
+    float ap[LAMB_CHAINS] = {0.f, 0.f, 0.f, 0.f}, au[LAMB_CHAINS] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = b0 + (int)threadIdx.x; j < b1; j += 256 * LAMB_CHAINS) {
+#pragma unroll
+        for (int c = 0; c < LAMB_CHAINS; ++c)
+            if (j + 256 * c < b1) {
+                const float2 s = ((const float2*)ws)[j + 256 * c];
+                ap[c] += s.x; au[c] += s.y;
+            }
+    }
+    const float sp = gn_block_sum((ap[0] + ap[1]) + (ap[2] + ap[3]), lds_p);
+    const float su = gn_block_sum((au[0] + au[1]) + (au[2] + au[3]), lds_u);
+    if (threadIdx.x != 0) return;
+    const float w_norm = sqrtf(sp), u_norm = sqrtf(su);
+    const bool usable = w_norm > 0.f && u_norm > 0.f && w_norm <= 3.402823466e38f && u_norm <= 3.402823466e38f;          // finite, not NaN
+    float ratio = (decay_bit(bits, b0) && usable) ? w_norm / u_norm : 1.f;
+    if (trust_clip > 0.f) ratio = fminf(ratio, trust_clip);
+    trust[q] = w_norm;
+    trust[total_params + q] = u_norm;
+    trust[2 * (long long)total_params + q] = ratio;
+}
+
+// block_param[blk] = the parameter block blk belongs to: a 4-byte load the block's 16 lanes share, from a map that stays in cache
+// (463 KB at 7.4 M parameters), against a search of the table per float4.
+__global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                         long long n4, LambStep k, const unsigned* __restrict__ bits,
+                                                         long long first_block, const int* __restrict__ block_param,
+                                                         const float* __restrict__ ratio, const float* __restrict__ skip) {
+    if (skip && skip[0] != 0.f) return;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const long long blk = first_block + (i >> 4);
+        const bool sel = decay_bit(bits, blk);
+        const float step = k.lr * ratio[block_param[blk]];
+        f32x4 pp = ((f32x4*)p)[i];
+        const f32x4 mm = __builtin_nontemporal_load((const f32x4*)m + i), vv = __builtin_nontemporal_load((const f32x4*)v + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pp[e] = pp[e] - step * lamb_direction(pp[e], mm[e], vv[e], sel, k);
+        ((f32x4*)p)[i] = pp;
+    }
+}
+
+long long lamb_workspace_floats(long long total_blocks) { return total_blocks > 0 ? 2 * total_blocks : 0; }
+
+int launch_lamb(const AdamArgs& a, int step, const LambTables& t, hipStream_t stream) {
+    if (!adam_args_ok(a) || step < 1 || !a.decay_bits) return CPC_EINVAL;
+    if (!t.param_block || !t.param_block_dev || !t.block_param || !t.workspace || !t.trust) return CPC_EINVAL;
+    if ((uintptr_t)t.workspace % 8) return CPC_EINVAL;          // a block's two sums travel as one 8-byte store and load
+    if (t.n_params <= 0 || t.first_param < 0 || t.total_params <= 0 || (long long)t.first_param + t.n_params > t.total_params)
+        return CPC_EINVAL;
+    if (!(t.trust_clip < 0.f) && !(t.trust_clip > 0.f && t.trust_clip <= 3.402823466e38f)) return CPC_EINVAL;
+    // the range is whole parameters: the host's copy of the table has to give it the blocks the caller says it has
+    const int* tb = t.param_block + t.first_param;
+    for (int q = 0; q < t.n_params; ++q)
+        if (tb[q + 1] < tb[q]) return CPC_EINVAL;
+    if (tb[0] != a.first_block || 64LL * ((long long)tb[t.n_params] - tb[0]) != a.n) return CPC_EINVAL;
+    const double bc1 = 1.0 - pow((double)a.b1, step), bc2 = 1.0 - pow((double)a.b2, step);
+    const LambStep k = {a.lr, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), a.weight_decay, a.b1, a.b2, a.eps, a.grad_scale, 1.f};
+    const long long n4 = a.n / 4;
+    const int blocks = (int)min((long long)2048, (n4 + 255) / 256);
+    if (a.coef)
+        hipLaunchKernelGGL(lamb_moments_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)a.p, a.g, a.m, a.v, n4, k, a.coef,
+                           a.decay_bits, a.first_block, t.workspace, a.skip);
+    else
+        hipLaunchKernelGGL(lamb_moments_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)a.p, a.g, a.m, a.v, n4, k, a.coef,
+                           a.decay_bits, a.first_block, t.workspace, a.skip);
+    hipLaunchKernelGGL(lamb_ratio_kernel, dim3(t.n_params), dim3(256), 0, stream, (const float*)t.workspace, t.param_block_dev,
+                       t.first_param, t.total_params, a.decay_bits, t.trust_clip, t.trust, a.skip);
+    hipLaunchKernelGGL(lamb_apply_kernel, dim3(blocks), dim3(256), 0, stream, a.p, (const float*)a.m, (const float*)a.v, n4, k,
+                       a.decay_bits, a.first_block, t.block_param, (const float*)(t.trust + 2LL * t.total_params), a.skip);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
 // Operands of a tall (kh,1) convolution computed G output rows per GEMM row (scalogram_engine._col_group): G shifted copies of the kernel
 // in a window of Rw (forward) / Rd (data gradient) rows, zero elsewhere.  W f32 [co][c][kh];
 //   fwd  [dh][co][r][c]  = W[co][c][r - dh]              for dh <= r < dh + kh      (output row G R + dh reads window rows dh .. dh+kh-1)

@@ -2413,6 +2413,78 @@ def default_decay_filter(name, parameter):
     return parameter.dim() >= 2
 
 
+def check_trust(trust_ratio, trust_clip=None):
+    """(trust_ratio, trust_clip as a float or None): ValueError unless trust_ratio is a bool and trust_clip None or finite and > 0
+    (what cpc_lamb admits)."""
+    if not isinstance(trust_ratio, bool):
+        raise ValueError(f"trust_ratio must be True or False, got {trust_ratio!r}")
+    if trust_clip is None:
+        return trust_ratio, None
+    try:
+        value = float(trust_clip)
+    except (TypeError, ValueError):
+        raise ValueError(f"trust_clip must be None or a positive finite number, got {trust_clip!r}") from None
+    if isinstance(trust_clip, bool) or not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"trust_clip must be None or a positive finite number, got {trust_clip!r}")
+    return trust_ratio, value
+
+
+class TorchLamb(torch.optim.Optimizer):
+    """LAMB in torch ops, the definition of DESIGN.md, "LAMB trust ratios" (include/cpc_hip.h, cpc_lamb, is the same on the flat
+    buffer): Adam's moments and bias-corrected direction r; u = r + weight_decay * p on the parameters
+    ``decay_filter(name, parameter)`` selects (default: dim() >= 2), u = r on the others; trust = ||p|| / ||u|| where the parameter is
+    selected and both norms are finite and > 0, else 1, at most ``trust_clip``; p <- p - lr * trust * u.  Takes
+    ``model.named_parameters()``; CPU or GPU tensors of any float dtype, nothing is read back to the host.  The state is
+    torch.optim.Adam's (step, exp_avg, exp_avg_sq), and ``load_state_dict`` takes a dict written by torch.optim.Adam / AdamW or
+    FusedAdam; ``last_trust`` = {name: (w_norm, u_norm, ratio)} of the latest step."""
+
+    def __init__(self, named_parameters, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decay_filter=None, trust_clip=None):
+        named = [(n, p) for n, p in named_parameters]
+        weight_decay = check_weight_decay(weight_decay, decay_filter)
+        _, trust_clip = check_trust(True, trust_clip)
+        chosen = decay_filter or default_decay_filter
+        self.names = {id(p): n for n, p in named}
+        self.selected = {id(p): bool(chosen(n, p)) for n, p in named}
+        self.last_trust = {}
+        super().__init__([p for _, p in named], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, trust_clip=trust_clip))
+
+    def load_state_dict(self, state_dict):
+        """Takes the moments and step counts; the hyper-parameters stay the constructor's, as in FusedAdam.load_state_dict (torch
+        replaces the param groups by the saved ones, which carry another optimizer's weight_decay and no trust_clip)."""
+        own = [{k: group[k] for k in self.defaults} for group in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, kept in zip(self.param_groups, own):
+            group.update(kept)
+
+    @torch.no_grad()
+    def step(self):
+        for group in self.param_groups:
+            (b1, b2), eps, wd, clip = group["betas"], group["eps"], group["weight_decay"], group["trust_clip"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st.update(step=torch.tensor(0.0), exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
+                st["step"] += 1
+                t, m, v, g = int(st["step"]), st["exp_avg"], st["exp_avg_sq"], p.grad
+                m.add_((g - m) * (1 - b1))
+                v.mul_(b2).addcmul_(g, g, value=1 - b2)
+                u = (m / (1 - b1 ** t)) / (v.sqrt() / math.sqrt(1 - b2 ** t) + eps)
+                selected = self.selected[id(p)]
+                if selected:
+                    u = u + wd * p
+                w_norm, u_norm = p.norm(), u.norm()
+                trust = torch.ones_like(w_norm)
+                if selected:
+                    usable = (w_norm > 0) & (u_norm > 0) & torch.isfinite(w_norm) & torch.isfinite(u_norm)
+                    trust = torch.where(usable, w_norm / u_norm, trust)
+                if clip is not None:
+                    trust = trust.clamp(max=clip)
+                self.last_trust[self.names[id(p)]] = (w_norm, u_norm, trust)
+                p.sub_((group["lr"] * trust) * u)
+
+
 class LRSchedule:
     """Warm-up, then a constant, linearly or cosine-decaying learning rate: step ``s`` (0-based) runs at ``lr * factor(s)``, what
     ``torch.optim.lr_scheduler.LambdaLR(optimizer, schedule.factor)`` with ``scheduler.step()`` behind every ``optimizer.step()``
@@ -2471,10 +2543,13 @@ class LRSchedule:
 
 class FusedAdam:
     """torch.optim.Adam (default betas / eps) over the model's flat f32 parameter buffer as one kernel; with ``weight_decay`` > 0
-    torch.optim.AdamW on the parameters ``decay_filter`` selects, with ``schedule`` at the learning rate lr * schedule.factor(step)."""
+    torch.optim.AdamW on the parameters ``decay_filter`` selects, with ``schedule`` at the learning rate lr * schedule.factor(step);
+    with ``trust_ratio`` LAMB (TorchLamb's definition): the decay joins Adam's direction and every selected parameter's update is
+    scaled by ||p|| / ||direction||, at most ``trust_clip``."""
 
     def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None,
-                 weight_decay: float = 0.0, decay_filter=None, schedule=None, step_offset: int = 0):
+                 weight_decay: float = 0.0, decay_filter=None, schedule=None, step_offset: int = 0, trust_ratio: bool = False,
+                 trust_clip=None):
         self.model = model
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         # weight_decay / decay_filter / schedule / step_offset (DESIGN.md, "AdamW and the learning-rate schedule").  Step number i of
@@ -2488,8 +2563,18 @@ class FusedAdam:
         if isinstance(step_offset, bool) or not isinstance(step_offset, int) or step_offset < 0:
             raise ValueError(f"step_offset must be an integer >= 0, got {step_offset!r}")
         self.base_lr, self.schedule, self.step_offset, self._t0 = self.lr, schedule, step_offset, 0
-        self.decay_bits = self._decay_bitmap(decay_filter or default_decay_filter) if self.weight_decay > 0.0 else None
+        # trust_ratio / trust_clip ("LAMB trust ratios"): every update is a cpc_lamb call over whole parameters.  The
+        # bitmap then also selects who gets a ratio and is built for weight_decay == 0 too; the parameter table, its inverse, the
+        # block sums' workspace and trust f32[3][parameters] are built once, here.  With trust_ratio=False none of them exists.
+        self.trust_ratio, self.trust_clip = check_trust(trust_ratio, trust_clip)
+        if self.trust_ratio and device_step:
+            raise NotImplementedError("trust_ratio with device_step=True: the three launches of a LAMB update take the step's bias "
+                                      "corrections and learning rate from the host; no captured LAMB step exists")
+        decays = self.weight_decay > 0.0 or self.trust_ratio
+        self.decay_bits = self._decay_bitmap(decay_filter or default_decay_filter) if decays else None
         flat = model._flat_param
+        if self.trust_ratio:
+            self._lamb_tables()
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
         self.t = 0
@@ -2548,6 +2633,8 @@ class FusedAdam:
         cpc_adam_dev; both keep the count themselves and ignore ``t``."""
         if hi <= lo:
             return
+        if self.trust_ratio:
+            return self._update_lamb(lo, hi, t, grad_scale, coef)
         model, dev, decayed = self.model, self.state is not None, self.decay_bits is not None
         model._raw_updates = getattr(model, "_raw_updates", 0) + 1
         dev_schedule = dev and (decayed or self.schedule is not None)
@@ -2571,6 +2658,48 @@ class FusedAdam:
         else:
             name, tail = "cpc_adam", []
         _hip.call(name, *head, *tail, _hip.ptr(self.skip_flag))
+
+    def _lamb_tables(self):
+        """The per-parameter buffers of cpc_lamb, from model._offset (parameters in buffer order, each at a 64-float boundary, its
+        padding behind it): _param_block (host int32 table, parameter q covers blocks [q], [q + 1]), its device copy, the per-block
+        inverse map, the workspace and ``trust``."""
+        flat, offset = self.model._flat_param, self.model._offset
+        names = sorted(offset, key=offset.get)
+        sizes = dict((n, p.numel()) for n, p in self.model.named_parameters())
+        edges = [offset[n] for n in names] + [flat.numel()]
+        assert edges[0] == 0 and all(e % 64 == 0 for e in edges), "parameters start at 64-float boundaries of the flat buffer"
+        assert all(0 < sizes[n] <= b - a for n, a, b in zip(names, edges, edges[1:]))
+        self._lamb_names = names
+        self._param_at = {e: q for q, e in enumerate(edges)}          # float offset -> index of the parameter that starts there
+        self._param_block = (C.c_int * len(edges))(*(e // 64 for e in edges))
+        table = torch.tensor(list(self._param_block), dtype=torch.int32)
+        self._param_block_dev = table.to(flat.device)
+        self._block_param = torch.repeat_interleave(torch.arange(len(names), dtype=torch.int32),
+                                                    (table[1:] - table[:-1]).long()).to(flat.device)
+        floats = int(_hip.lib().cpc_lamb_workspace_floats(flat.numel() // 64))
+        self._lamb_ws = torch.zeros(floats, device=flat.device, dtype=torch.float32)
+        self.trust = torch.zeros(3, len(names), device=flat.device, dtype=torch.float32)
+
+    def _update_lamb(self, lo, hi, t, grad_scale, coef):
+        """_update under trust_ratio: one cpc_lamb call (three launches) over the whole parameters of flat_param[lo:hi)."""
+        model = self.model
+        assert lo in self._param_at and hi in self._param_at, f"a LAMB update covers whole parameters, got [{lo}, {hi})"
+        first, count = self._param_at[lo], self._param_at[hi] - self._param_at[lo]
+        model._raw_updates = getattr(model, "_raw_updates", 0) + 1
+        _hip.call("cpc_lamb", *[_hip.ptr(x, lo) for x in (model._flat_param, model._flat_grad, self.m, self.v)],
+                  C.c_longlong(hi - lo), C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), t,
+                  C.c_float(grad_scale), C.c_float(self.weight_decay), _hip.ptr(self.decay_bits), C.c_longlong(lo // 64), coef,
+                  C.cast(self._param_block, C.c_void_p), _hip.ptr(self._param_block_dev), _hip.ptr(self._block_param), first, count,
+                  len(self._lamb_names), C.c_float(-1.0 if self.trust_clip is None else self.trust_clip), _hip.ptr(self._lamb_ws),
+                  _hip.ptr(self.trust), _hip.ptr(self.skip_flag))
+
+    def trust_ratios(self):
+        """{parameter name: (w_norm, u_norm, ratio applied)} of the latest step, with one synchronous read.  For inspection: not to
+        be called in the training loop."""
+        if not self.trust_ratio:
+            raise ValueError("trust_ratios() needs FusedAdam(trust_ratio=True)")
+        rows = self.trust.cpu().tolist()
+        return {n: (rows[0][q], rows[1][q], rows[2][q]) for q, n in enumerate(self._lamb_names)}
 
     def _scheduled_lr(self, steps_done):
         """With a schedule: self.lr becomes the rate of the step that follows ``steps_done`` finished ones."""

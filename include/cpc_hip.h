@@ -52,6 +52,7 @@ extern "C" {
  *    cpc_nce_sampled_workspace_floats, cpc_nce_loss_sampled, cpc_nce_sample_mask.
  *    Added later under 9 (backward compatible, no entry point changed): the loss over grouped negatives
  *    cpc_nce_grouped_workspace_floats, cpc_nce_loss_grouped, cpc_nce_group_mask.
+ *    Added later under 9 (backward compatible, no entry point changed): LAMB trust ratios cpc_lamb_workspace_floats, cpc_lamb.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -771,6 +772,42 @@ int cpc_adamw_dev(float* p, const float* g, float* m, float* v, long long n, flo
  * step0 < 0, count <= 0, out NULL. */
 int cpc_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count,
                    float* out, void* stream);
+
+
+/* LAMB: a layer-wise trust ratio on Adam's direction (You et al., "Large Batch Optimization for Deep Learning"; not in the
+ * reference's train step; DESIGN.md, "LAMB trust ratios").  Per step t, for every parameter tensor P of the range, with the gradient
+ * g' = g * grad_scale, or (g * grad_scale) * coef[0] when coef is given, in that order as in cpc_adamw:
+ *   m  = m + (g' - m)(1 - b1);   v = b2 v + (1 - b2) g'^2                 cpc_adam's moments, unchanged
+ *   r  = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps)                          Adam's direction; bc1 = 1 - b1^t, bc2 = 1 - b2^t
+ *   u  = r + weight_decay * p   if P is selected, else  u = r             the decay is part of the direction (not AdamW's multiply)
+ *   w_norm = ||p||_2, u_norm = ||u||_2 over P's blocks (its alignment padding is zero and stays zero)
+ *   trust  = w_norm / u_norm    if P is selected and both norms are finite and > 0, else 1
+ *   trust  = min(trust, trust_clip)                                       if trust_clip >= 0 (a negative value: no clip)
+ *   p  <- p - lr * trust * u                                              lr: the step's rate, schedule factor multiplied in
+ * select_bits: cpc_adamw's bitmap (one bit per 64-float block of the whole buffer); it selects decay AND trust ratio and is required
+ * also with weight_decay == 0.  The range [p, p + n) is a run of whole parameters, which start at 64-float boundaries:
+ *   param_block      HOST pointer, int32[total_params + 1], ascending: parameter q covers blocks [param_block[q], param_block[q + 1])
+ *                    of the whole buffer, its padding included (0 ... total blocks); read during the call, to check the range;
+ *   param_block_dev  the same table in device memory;
+ *   block_param      device int32[total blocks]: the parameter a block belongs to (the inverse of the table);
+ *   first_param, n_params: the range is parameters first_param ... first_param + n_params - 1, first_block = param_block[first_param],
+ *                    n = 64 * (param_block[first_param + n_params] - first_block);
+ *   workspace        device, 8-byte aligned, cpc_lamb_workspace_floats(total blocks) floats: the sums of p^2 and u^2 of block j at
+ *                    [2 j], [2 j + 1], written and read as one 8-byte pair;
+ *   trust            device f32[3][total_params]: w_norm, u_norm and the ratio applied, written for the range's parameters.
+ * Three launches: moments and block sums; one workgroup per parameter for the ratios; the update (u is formed again from the new
+ * m, v and the old p — nothing is parked in g).  All sums are float32 in a fixed order without atomics: the same data give the same
+ * bits for any split of the buffer into ranges.  skip as in cpc_adam: while *skip != 0, p, m, v, workspace and trust keep their bits.
+ * CPC_EINVAL before any launch: cpc_adamw's cases; select_bits, param_block, param_block_dev, block_param, workspace or trust NULL;
+ * a workspace that is not 8-byte aligned;
+ * n_params <= 0, first_param < 0 or first_param + n_params > total_params; a table that descends inside the range, whose
+ * param_block[first_param] is not first_block, or that gives the range another size than n; trust_clip >= 0 (given) but not finite
+ * and > 0. */
+long long cpc_lamb_workspace_floats(long long total_blocks);
+int cpc_lamb(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+             float grad_scale, float weight_decay, const unsigned* select_bits, long long first_block, const float* coef,
+             const int* param_block, const int* param_block_dev, const int* block_param, int first_param, int n_params,
+             int total_params, float trust_clip, float* workspace, float* trust, const float* skip, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@ Mirrors the reference's ``contrastive_estimation_training.py`` (score functions 
 DeterministicSampler :363-382, grad_mean_var :385-391).  ``train`` has two routes:
 
 * fused (the hot path): AudioEncoder + AudioGRUModel model, softplus/linear score (either ``score_over_all_timesteps``
-  setting), Adam; the difference score with Adam takes it too (``_engine_difference``), except under global negatives.  Forward, InfoNCE loss, analytic backward and the Adam update all run as
+  setting), Adam; the difference score and NormalizedScoreFunction with Adam take it too (``_engine_difference``,
+  ``_engine_normalized``), except under global negatives.  Forward, InfoNCE loss, analytic backward and the Adam update all run as
   HIP kernels (engine.CPCEngine); with torch.distributed initialised, one process per GPU, the flat gradient buffer is
   all-reduced over RCCL before the update (per-GPU in-batch negatives).
 * generic: any other score function or optimizer: the model forward and backward run on the HIP path through the autograd
@@ -179,6 +180,63 @@ def difference_score_function(predicted_z, targets):
     """1 / squared distance between every prediction and every target (reference :25-33), as HIP kernels (_DifferenceScores):
     O((B K)^2) memory instead of the reference broadcast's O(B^2 K^2 E)."""
     return _DifferenceScores.apply(predicted_z, targets)
+
+
+class _NormalizeRows(torch.autograd.Function):
+    """rows / max(|row|, eps) * scale over the last axis of an (R, E) f32 matrix: cpc_norm_rows, and cpc_norm_rows_bwd in the backward
+    (the kernels of the engine route, so that both routes share one arithmetic)."""
+
+    @staticmethod
+    def forward(ctx, rows, scale):
+        from . import _hip
+        from .engine import NORM_EPS
+        R, E = rows.shape
+        X = rows.detach().float().contiguous()
+        Y = torch.empty_like(X)
+        inv = torch.empty(R, device=X.device, dtype=torch.float32)
+        L, F_ = ctypes.c_longlong, ctypes.c_float
+        _hip.call("cpc_norm_rows", _hip.ptr(X), _hip.ptr(Y), _hip.ptr(inv), R, E, 0, L(0), L(E), F_(scale), F_(NORM_EPS), _hip.F32)
+        ctx.save_for_backward(Y, inv)
+        ctx.scale = scale
+        return Y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dY):
+        from . import _hip
+        from .engine import NORM_EPS
+        Y, inv = ctx.saved_tensors
+        R, E = Y.shape
+        G = torch.empty_like(Y)              # overwritten in place below: never autograd's own buffer
+        G.copy_(dY)
+        L, F_ = ctypes.c_longlong, ctypes.c_float
+        _hip.call("cpc_norm_rows_bwd", _hip.ptr(Y), _hip.ptr(inv), _hip.ptr(G), R, E, 0, L(0), L(E), F_(ctx.scale), F_(NORM_EPS), _hip.F32)
+        return G, None
+
+
+class NormalizedScoreFunction:
+    """Cosine similarity over a temperature (not in the reference; wav2vec 2.0 / SimCLR / CLIP-style scores):
+    scores[b, k, b', k'] = <predicted_z[b, k] / max(|.|, 1e-8), targets[b', :, k'] / max(|.|, 1e-8)> / temperature, i.e.
+    linear_score_function(F.normalize(predicted_z, dim=2) / temperature, F.normalize(targets, dim=1)).  Bounded by 1 / temperature
+    whatever the norms of the encodings.  As ``score_function=`` of ContrastiveEstimationTrainer with Adam the whole step runs on the
+    engine (score kind "normalized"); called on tensors it is an autograd function over the same kernels (f32: cpc_norm_rows, the score
+    contraction, cpc_norm_rows_bwd).  The temperature is a constant of the run (finite and > 0)."""
+
+    def __init__(self, temperature=0.1):
+        from .engine import check_temperature
+        self.temperature = check_temperature(temperature)
+
+    def __repr__(self):
+        return f"NormalizedScoreFunction(temperature={self.temperature!r})"
+
+    def __call__(self, predicted_z, targets):
+        _need_gpu(predicted_z, "the normalized score function")
+        B, K, E = predicted_z.shape
+        if tuple(targets.shape) != (B, E, K):
+            raise ValueError("normalized scores: expected predicted_z (B, K, E) and targets (B, E, K)")
+        pn = _NormalizeRows.apply(predicted_z.reshape(B * K, E), 1.0 / self.temperature).view(B, K, E)
+        tn = _NormalizeRows.apply(targets.permute(0, 2, 1).reshape(B * K, E), 1.0).view(B, K, E).permute(0, 2, 1)
+        return _ScoreContraction.apply(pn, tn)
 
 
 def _score_layout(scores4, all_timesteps):
@@ -451,6 +509,12 @@ class ContrastiveEstimationTrainer:
         device NaN guard); under global negatives it keeps the generic route."""
         return self.score_function is difference_score_function and self.optimizer is torch.optim.Adam and not self.global_negatives
 
+    def _engine_normalized(self):
+        """NormalizedScoreFunction + Adam also runs the whole step on the engine (cpc_norm_rows around the linear score's chain,
+        FusedAdam, the device NaN guard); under global negatives it keeps the generic route."""
+        return (isinstance(self.score_function, NormalizedScoreFunction) and self.optimizer is torch.optim.Adam
+                and not self.global_negatives)
+
     def _check_negatives(self, batch_size):
         """Up-front checks of num_negatives (before any GPU work): ValueError unless 1 <= N <= batch_size - 1, NotImplementedError
         for what the sampled loss does not cover."""
@@ -553,7 +617,16 @@ class ContrastiveEstimationTrainer:
     def _score_kind(self):
         if self.score_function is difference_score_function:
             return "difference"
+        if isinstance(self.score_function, NormalizedScoreFunction):
+            return "normalized"
         return "softplus" if self.score_function is softplus_score_function else "linear"
+
+    def _score_kw(self):
+        """The engine's score keywords: score=kind and, with NormalizedScoreFunction, its temperature."""
+        kw = {"score": self._score_kind()}
+        if kw["score"] == "normalized":
+            kw["temperature"] = self.score_function.temperature
+        return kw
 
     @staticmethod
     def _world():
@@ -630,8 +703,8 @@ class ContrastiveEstimationTrainer:
         device = self._device()
         rank, world = self._world()
         self.model.train()
-        fused = self._fused() or self._engine_difference()
-        kind = self._score_kind()
+        fused = self._fused() or self._engine_difference() or self._engine_normalized()
+        score_kw = self._score_kw()
         if fused:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
             self.model._flatten_parameters(device)
@@ -815,7 +888,7 @@ class ContrastiveEstimationTrainer:
                         key = (batch.shape[0], batch.shape[1])
                         if key not in graph_steps:
                             graph_steps[key] = GraphedStep(eng, optimizer, self.score_function is softplus_score_function,
-                                                           float(self.regularization), bool(self.score_over_all_timesteps), score=kind)
+                                                           float(self.regularization), bool(self.score_over_all_timesteps), **score_kw)
                         if id(eng) not in guarded:
                             eng.nan_flag().zero_()
                             guarded.add(id(eng))
@@ -868,7 +941,7 @@ class ContrastiveEstimationTrainer:
                                                      all_timesteps=bool(self.score_over_all_timesteps),
                                                      grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
                                                      global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
-                                                     score=kind, **self._negatives_kw(), **groups_kw)
+                                                     **score_kw, **self._negatives_kw(), **groups_kw)
                         if sync is not None:
                             sync.finish()
                         # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
@@ -979,7 +1052,8 @@ class ContrastiveEstimationTrainer:
                                    verbose=self.verbose)
         sums = torch.zeros(2 * K + 1, device=device, dtype=torch.float32)
         ws = torch.empty(int(_hip.lib().cpc_nce_eval_workspace_floats(batch_size, K)), device=device, dtype=torch.float32)
-        kernel_scores = self.score_function in (softplus_score_function, linear_score_function, difference_score_function)
+        kernel_scores = (self.score_function in (softplus_score_function, linear_score_function, difference_score_function)
+                         or isinstance(self.score_function, NormalizedScoreFunction))
         self.model.eval()
         done = 0
         with torch.no_grad():
@@ -990,7 +1064,7 @@ class ContrastiveEstimationTrainer:
                 if kernel_scores:
                     eng = self.model.engine_for(x)
                     eng.forward(x.float() if x.dim() == 4 else x[:, 0, :].contiguous().float())
-                    eng.nce_eval(self.score_function is softplus_score_function, all_t, sums, ws, score=self._score_kind())
+                    eng.nce_eval(self.score_function is softplus_score_function, all_t, sums, ws, **self._score_kw())
                 else:
                     predicted_z, targets, _, _ = self.model(x)
                     S, ld = _score_layout(self.score_function(predicted_z, targets), all_t)

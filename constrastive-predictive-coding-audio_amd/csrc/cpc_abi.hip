@@ -770,6 +770,24 @@ int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, i
     return launch_diff_scores_rank1(mu, X, out, rows, E, rpi, item, ld, dtype, (hipStream_t)stream);
 }
 
+// (the argument checks shared by cpc_norm_rows and cpc_norm_rows_bwd)
+static bool norm_rows_args_ok(int rows, int E, int rpi, float scale, float eps, int dtype) {
+    return rows >= 1 && E >= 1 && E <= 4096 && rpi >= 0 && std::isfinite(scale) && scale > 0.f && std::isfinite(eps) && eps > 0.f &&
+           (dtype == CPC_DTYPE_F32 || dtype == CPC_DTYPE_BF16);
+}
+
+int cpc_norm_rows(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, float scale, float eps,
+                  int dtype, void* stream) {
+    if (!X || !Y || !inv || !norm_rows_args_ok(rows, E, rpi, scale, eps, dtype)) return CPC_EINVAL;
+    return launch_norm_rows(X, Y, inv, rows, E, rpi, item, ld, scale, eps, dtype, (hipStream_t)stream);
+}
+
+int cpc_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E, int rpi, long long item, long long ld, float scale,
+                      float eps, int dtype, void* stream) {
+    if (!Y || !inv || !G || !norm_rows_args_ok(rows, E, rpi, scale, eps, dtype)) return CPC_EINVAL;
+    return launch_norm_rows_bwd(Y, inv, G, rows, E, rpi, item, ld, scale, eps, dtype, (hipStream_t)stream);
+}
+
 int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
              float grad_scale, const float* skip, void* stream) {
     return launch_adam({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, nullptr, 0.f, nullptr, 0}, step, false, (hipStream_t)stream);

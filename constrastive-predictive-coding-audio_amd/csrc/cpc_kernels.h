@@ -174,6 +174,10 @@ int launch_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const
                            long long s_batch, int batch, int dtype, hipStream_t stream);
 int launch_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
                              hipStream_t stream);
+int launch_norm_rows(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, float scale, float eps,
+                     int dtype, hipStream_t stream);
+int launch_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E, int rpi, long long item, long long ld, float scale,
+                         float eps, int dtype, hipStream_t stream);
 int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype, hipStream_t stream);
 long long grad_norm_workspace_floats(long long n);
 int launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,

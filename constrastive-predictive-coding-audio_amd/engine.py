@@ -28,17 +28,36 @@ from .sampled_negatives import check_group_negatives, check_negatives, group_mod
 
 _SIDE_STREAMS = {}
 
-SCORE_KINDS = ("softplus", "linear", "difference")
+SCORE_KINDS = ("softplus", "linear", "difference", "normalized")
+NORM_EPS = 1e-8          # F.normalize's clamp under the norms of the "normalized" score (cosine similarity / temperature)
 
 
 def score_kind(softplus: bool, score: Optional[str] = None) -> str:
-    """The score function a loss call runs: ``score`` ("softplus" | "linear" | "difference") when given, else the ``softplus`` flag's
-    choice between the two dot-product scores (contrastive_estimation_training.py:12-33)."""
+    """The score function a loss call runs: ``score`` ("softplus" | "linear" | "difference" | "normalized") when given, else the
+    ``softplus`` flag's choice between the two dot-product scores (contrastive_estimation_training.py:12-33)."""
     if score is None:
         return "softplus" if softplus else "linear"
     if score not in SCORE_KINDS:
         raise ValueError(f"score must be one of {SCORE_KINDS}, got {score!r}")
     return score
+
+
+def check_temperature(temperature, kind: Optional[str] = None):
+    """The temperature of the "normalized" score as a float: ValueError unless it is finite and > 0.  With ``kind`` also the pairing:
+    the "normalized" kind needs one, and every other kind refuses one (returns None there)."""
+    if kind is not None and kind != "normalized":
+        if temperature is not None:
+            raise ValueError(f"temperature belongs to score='normalized'; score {kind!r} has none")
+        return None
+    if temperature is None:
+        raise ValueError("score='normalized' needs a temperature (finite and > 0)")
+    try:
+        value = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a positive finite number, got {temperature!r}") from None
+    if not math.isfinite(value) or value <= 0.0:
+        raise ValueError(f"temperature must be a positive finite number, got {temperature!r}")
+    return value
 
 
 def check_negatives_supported(negatives, all_timesteps=False, global_negatives=None, gradient_penalty=None, negative_groups=None):
@@ -595,19 +614,24 @@ class CPCEngine:
         return 2.0 * R * R * E
 
     def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, negatives=None,
-                             negative_groups=None):
+                             negative_groups=None, temperature=None):
         """Equal-step scores, InfoNCE loss + regulariser, and d loss / d (predicted_z, targets).
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
         (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs).
-        ``score``: see score_kind; "difference" runs _diff_forward_backward.
+        ``score``: see score_kind; "difference" runs _diff_forward_backward, "normalized" (with its ``temperature``)
+        _norm_forward_backward.
         ``negatives``: None, or (n_neg, seed, draw) — every target is contrasted against n_neg seeded negatives instead of the
         whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask).
         ``negative_groups``: None, or (groups, mode) — groups an int32 device tensor [B], mode "same" / "other": a target's candidates
         are the rows of its own group / of the other groups, all of them or, with ``negatives``, n_neg seeded ones
         (cpc_nce_loss_grouped; sampled_negatives.grouped_negative_mask)."""
-        if score_kind(softplus, score) == "difference":
+        kind = score_kind(softplus, score)
+        temperature = check_temperature(temperature, kind)
+        if kind == "difference":
             return self._diff_forward_backward(False, regularization, negatives, negative_groups)
+        if kind == "normalized":
+            return self._norm_forward_backward(False, regularization, temperature, negatives, negative_groups)
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         top, dtop = self.act[-1], self.dact[-1]
@@ -667,13 +691,15 @@ class CPCEngine:
         return (self.dt == torch.bfloat16 and switches.fused_score() and rows % 256 == 0 and cols % 256 == 0
                 and self.E % 64 == 0 and self.E >= 128 and self.K % 2 == 0 and self.K <= 24)
 
-    def _nce_all_fused(self, softplus: bool, regularization: float):
+    def _nce_all_fused(self, softplus: bool, regularization: float, pred=None, top=None):
         """One persistent MFMA launch forms the (B K) x (B K) scores tile by tile and leaves the f32 scores + per-tile column
         (max, sum-exp) pairs + the diagonal; a merge, one gradient pass (dS and its transpose) and the loss scalars follow.  Replaces: the second (transposed) score GEMM, two f32 score matrices, the 16-way split column pass and the
-        two element-wise gradient passes of nce_all_forward_backward."""
+        two element-wise gradient passes of nce_all_forward_backward.  ``pred`` / ``top``: the score operands in the layouts of
+        self.pred / the top-layer buffer (None: those two)."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
-        top, dtop = self.act[-1], self.dact[-1]
+        pred = self.pred if pred is None else pred
+        top, dtop = (self.act[-1] if top is None else top), self.dact[-1]
         R = B * K
         f = getattr(self, "_fs", None)
         if f is None:
@@ -687,14 +713,14 @@ class CPCEngine:
                 dS=torch.empty(R, R, device=dev, dtype=self.dt), dST=torch.empty(R, R, device=dev, dtype=self.dt))
         P = _hip.ptr
         f.targ.view(B, K, E).copy_(top.view(B, Ltop, E)[:, T - K:T, :])
-        _hip.call("cpc_score_lse", P(self.pred), P(f.targ), P(f.Sb), P(f.pm), P(f.ps), P(f.valid), R, R, E, C.c_longlong(E), C.c_longlong(E),
+        _hip.call("cpc_score_lse", P(pred), P(f.targ), P(f.Sb), P(f.pm), P(f.ps), P(f.valid), R, R, E, C.c_longlong(E), C.c_longlong(E),
                   C.c_longlong(R), 0, key="score_lse<bf16,256>", work=2.0 * R * R * E)
         _hip.call("cpc_nce_lse_merge", P(f.pm), P(f.ps), R // 256, R, 1 if softplus else 0, C.c_float(R), P(f.lse), P(f.colp))
         _hip.call("cpc_nce_fused_grad", P(f.Sb), P(f.lse), P(f.dS), P(f.dST), P(f.gradp), B, K, R, C.c_longlong(R), C.c_longlong(R), 0,
                   1 if softplus else 0, C.c_float(regularization), C.c_float(R), C.c_float(B))
         _hip.call("cpc_nce_fused_finalize", P(f.colp), f.colp.shape[0], P(f.valid), R, P(f.gradp), f.gradp.numel(), None, 0, C.c_float(R),
                   C.c_float(B), K, C.c_float(regularization), 1 if softplus else 0, P(self.nce_out))
-        self._score_grads_all(f.dS, f.dST, self.pred, top, self.dpred, dtop)
+        self._score_grads_all(f.dS, f.dST, pred, top, self.dpred, dtop)
 
     def _all_buffers(self):
         """Score, gradient and workspace buffers of the unfused all-timesteps loss (allocated on first use)."""
@@ -711,14 +737,19 @@ class CPCEngine:
             self.nce_all_ws = torch.empty(int(_hip.lib().cpc_nce_all_workspace_floats(B, K)), device=self.device, dtype=f32)
         return ld
 
-    def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None):
+    def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, temperature=None):
         """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
         matrix (and its transpose, as a second tiny GEMM, so that both gradient layouts are written coalesced), the
         log-sum-exp over ALL predictions for every (target item, step), and d loss / d (predicted_z, targets).
         bf16 storage and tile-sized problems take the fused route (_nce_all_fused) instead; difference scores never do
-        (cpc_score_lse is a dot-product kernel): they run _diff_forward_backward."""
-        if score_kind(softplus, score) == "difference":
+        (cpc_score_lse is a dot-product kernel): they run _diff_forward_backward.  "normalized" scores (with their ``temperature``)
+        run _norm_forward_backward, which takes either route on the normalised operands."""
+        kind = score_kind(softplus, score)
+        temperature = check_temperature(temperature, kind)
+        if kind == "difference":
             return self._diff_forward_backward(True, regularization)
+        if kind == "normalized":
+            return self._norm_forward_backward(True, regularization, temperature)
         if self.fused_scores_ok():
             return self._nce_all_fused(softplus, regularization)
         code, B, E, K = self.code, self.B, self.E, self.K
@@ -753,13 +784,16 @@ class CPCEngine:
         _hip.gemm_nt(_hip.ptr(WT), _hip.ptr(self.predT), _hip.ptr(out_top, tg), R, E, ld, ld, ld, E, code,
                      c_rpi=K, c_item=Ltop * E, c_valid=K)
 
-    def nce_eval(self, softplus: bool, all_timesteps: bool, sums, workspace, score: Optional[str] = None):
+    def nce_eval(self, softplus: bool, all_timesteps: bool, sums, workspace, score: Optional[str] = None, temperature=None):
         """Adds this batch's validation quantities (per-step losses, per-step accuracies, mean score: include/cpc_hip.h,
         cpc_nce_eval) to ``sums`` (2 K + 1 floats) — from the score matrices of the train step (forward() must have run).
-        ``score``: see score_kind (difference scores are formed by cpc_diff_scores, then read as linear scores)."""
-        code, B, E, K = self.code, self.B, self.E, self.K
+        ``score``: see score_kind (difference scores are formed by cpc_diff_scores, "normalized" scores by the score GEMM on the
+        operands cpc_norm_rows leaves for ``temperature``; both are then read as linear scores)."""
         kind = score_kind(softplus, score)
+        temperature = check_temperature(temperature, kind)
+        code, B, E, K = self.code, self.B, self.E, self.K
         diff = kind == "difference"
+        pn, tn = self._norm_operands(temperature) if kind == "normalized" else (None, None)
         if all_timesteps:
             ld = _ceil_div(B * K, 8) * 8
             if diff:
@@ -767,14 +801,14 @@ class CPCEngine:
                     self.S_all = torch.zeros(B * K * ld, device=self.device, dtype=torch.float32)
                 self.diff_scores_all(self.S_all, None)
             else:
-                self.score_gemm_all()
+                self.score_gemm_all(pn, tn)
             S = self.S_all
         else:
             ld = self.ldS
             if diff:
                 self.diff_scores(self.S, None)
             else:
-                self.score_gemm()
+                self.score_gemm(pn, tn)
             S = self.S
         _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), B, K, ld, 1 if kind == "softplus" else 0,
                   1 if all_timesteps else 0, 1)
@@ -850,6 +884,83 @@ class CPCEngine:
         _hip.call("cpc_diff_scores_rank1", P(mu), P(self.pred), P(self.dpred), R, E, 0, C.c_longlong(0), C.c_longlong(E), code)
         tg = (T - K) * E
         _hip.call("cpc_diff_scores_rank1", P(nu), P(top, tg), P(dtop, tg), R, E, K, C.c_longlong(Ltop * E), C.c_longlong(E), code)
+
+    # ---- cosine similarity / temperature ("normalized"; include/cpc_hip.h, cpc_norm_rows) ----
+    def _norm_scratch(self):
+        """Scratch of the "normalized" kind, allocated on first use (GraphedStep asks for it in front of its capture, so that the
+        zero fill of tn is not replayed with every step)."""
+        n = getattr(self, "_norm", None)
+        if n is None:
+            R = self.B * self.K
+            n = self._norm = SimpleNamespace(pn=torch.empty_like(self.pred), tn=torch.zeros_like(self.act[-1]),
+                                             inv_p=torch.empty(R, device=self.device, dtype=torch.float32),
+                                             inv_t=torch.empty(R, device=self.device, dtype=torch.float32))
+        return n
+
+    def _norm_operands(self, temperature: float):
+        """The score operands of the "normalized" kind, from the engine's own layouts: pn = predicted_z rows / max(norm, eps) /
+        temperature (shaped like self.pred) and tn = the K target rows of every item / max(norm, eps) inside a zero buffer shaped like
+        the top layer (only rows [T-K, T) are ever written).  Scratch allocated on first use; 1 / max(norm, eps) per row stays in
+        inv_p / inv_t (f32) for the backward."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        R = B * K
+        n = self._norm_scratch()
+        P, L, tg = _hip.ptr, C.c_longlong, (T - K) * E
+        nbytes = 2.0 * R * E * self.pred.element_size()
+        _hip.call("cpc_norm_rows", P(self.pred), P(n.pn), P(n.inv_p), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
+                  C.c_float(NORM_EPS), code, work=nbytes)
+        _hip.call("cpc_norm_rows", P(self.act[-1], tg), P(n.tn, tg), P(n.inv_t), R, E, K, L(Ltop * E), L(E), C.c_float(1.0),
+                  C.c_float(NORM_EPS), code, work=nbytes)
+        return n.pn, n.tn
+
+    def _norm_forward_backward(self, all_timesteps: bool, regularization: float, temperature: float, negatives=None,
+                               negative_groups=None):
+        """InfoNCE loss + regulariser on cosine-similarity scores over a temperature and d loss / d (predicted_z, targets): the rows
+        are normalised (cpc_norm_rows; predictions also divided by the temperature), the linear score's own chain — score GEMM, loss
+        kernels with softplus = 0 (dense, sampled or grouped; the fused all-timesteps route where fused_scores_ok() holds) and the two
+        contractions — runs on the normalised operands, and cpc_norm_rows_bwd turns the gradients with respect to the normalised rows
+        into those with respect to the rows, in place in dpred and in rows [T-K, T) of the top-layer gradient.  All on the current
+        stream: the target-row lane of backward() starts from those rows behind the event it records there.
+        ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward)."""
+        grouped = None
+        if negative_groups is not None:
+            check_negatives_supported(negatives, all_timesteps, negative_groups=negative_groups)
+            grouped = normalize_negative_groups(negative_groups, self.B, negatives)
+        elif negatives is not None:
+            check_negatives_supported(negatives, all_timesteps)
+            negatives = normalize_negatives(negatives, self.B)
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        dtop = self.dact[-1]
+        R = B * K
+        P, L, tg = _hip.ptr, C.c_longlong, (T - K) * E
+        pn, tn = self._norm_operands(temperature)
+        if all_timesteps and self.fused_scores_ok():
+            self._nce_all_fused(False, regularization, pn, tn)
+        elif all_timesteps:
+            ld = self._all_buffers()
+            self.score_gemm_all(pn, tn)
+            _hip.gemm_nt(P(tn, tg), P(pn), P(self.ST_all), R, R, E, E, E, ld, code, a_rpi=K, a_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
+            _hip.call("cpc_nce_loss_all", P(self.S_all), P(self.ST_all), P(self.dS_all), P(self.dST_all), P(self.nce_out),
+                      P(self.nce_all_ws), B, K, ld, 0, C.c_float(regularization), code)
+            self._score_grads_all(self.dS_all, self.dST_all, pn, tn, self.dpred, dtop)
+        else:
+            self.score_gemm(pn, tn)
+            if grouped is not None:
+                self._nce_grouped(self.S, self.dS, self.dST, 0, regularization, grouped)
+            elif negatives is None:
+                _hip.call("cpc_nce_loss", P(self.S), P(self.dS), P(self.dST), P(self.nce_out), P(self.nce_ws), B, K, self.ldS, 0,
+                          C.c_float(regularization), code)
+            else:
+                self._nce_sampled(self.S, self.dS, self.dST, 0, regularization, negatives)
+            self._score_grads(self.dS, self.dST, pn, tn, self.dpred, dtop)
+        n = self._norm
+        nbytes = 3.0 * R * E * self.pred.element_size()
+        _hip.call("cpc_norm_rows_bwd", P(pn), P(n.inv_p), P(self.dpred), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
+                  C.c_float(NORM_EPS), code, work=nbytes)
+        _hip.call("cpc_norm_rows_bwd", P(tn, tg), P(n.inv_t), P(dtop, tg), R, E, K, L(Ltop * E), L(E), C.c_float(1.0),
+                  C.c_float(NORM_EPS), code, work=nbytes)
 
     # ------------------------------------------------------------------------------------------ backward
     def _tn_to_grad(self, A, B_, grad, M, I, J, lda, ldb, nsplit, grad_offset=0, scratch=None, **kw):
@@ -1105,16 +1216,19 @@ class CPCEngine:
 
     # ------------------------------------------------------------------------------------------ whole step
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
-                       global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None, negative_groups=None):
+                       global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None, negative_groups=None,
+                       temperature=None):
         """Forward + loss + backward; returns the device tensor [loss, max_score, -mean valid, mean lse, reg, NaN indicator of
         this step, sticky NaN flag, -] (no sync; include/cpc_hip.h, cpc_nce_loss).
         ``global_negatives``: a GlobalNegatives object — the loss is then taken over the batches of ALL ranks.
         ``after_loss(nce_out)`` is called once the loss kernels are queued and before the backward pass is: data-parallel runs
         start the reduction of the NaN flag over the ranks there (GradAllReduce.reduce_flag).
-        ``score``: "softplus" | "linear" | "difference" (score_kind; None: the ``softplus`` flag decides).
+        ``score``: "softplus" | "linear" | "difference" | "normalized" (score_kind; None: the ``softplus`` flag decides).
+        ``temperature``: the temperature of "normalized" scores (finite and > 0; required there, a ValueError with any other kind).
         ``negatives``: None, or (n_neg, seed, draw): n_neg seeded negatives per target (nce_forward_backward); default branch only.
         ``negative_groups``: None, or (groups, mode): candidates by group id (nce_forward_backward); default branch only."""
         kind = score_kind(softplus, score)
+        temperature = check_temperature(temperature, kind)
         if negative_groups is not None:
             check_negatives_supported(negatives, all_timesteps, global_negatives, negative_groups=negative_groups)
             normalize_negative_groups(negative_groups, self.B, negatives)
@@ -1124,13 +1238,17 @@ class CPCEngine:
         if kind == "difference" and global_negatives is not None:
             raise NotImplementedError("difference scores under global negatives are not on the HIP path: the trainer takes the generic "
                                       "route there (contrastive_estimation_training.difference_score_function)")
+        if kind == "normalized" and global_negatives is not None:
+            raise NotImplementedError("normalized scores under global negatives are not on the HIP path: the trainer takes the generic "
+                                      "route there (contrastive_estimation_training.NormalizedScoreFunction)")
+        tkw = {} if temperature is None else {"temperature": temperature}
         self.forward(x)
         if global_negatives is not None:
             global_negatives.forward_backward(softplus, regularization, all_timesteps)
         elif all_timesteps:
-            self.nce_all_forward_backward(softplus, regularization, score=kind)
+            self.nce_all_forward_backward(softplus, regularization, score=kind, **tkw)
         else:
-            self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives, negative_groups=negative_groups)
+            self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives, negative_groups=negative_groups, **tkw)
         if after_loss is not None:
             after_loss(self.nce_out)
         self.backward(x, grad_ready_hook=grad_ready_hook)
@@ -2803,7 +2921,8 @@ class GraphedStep:
     (dropout seeds)."""
 
     def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None,
-                 negatives=None, negative_groups=None):
+                 negatives=None, negative_groups=None, temperature=None):
+        temperature = check_temperature(temperature, score_kind(softplus, score))
         if negative_groups is not None:
             raise NotImplementedError("grouped negatives take the group ids of each step's batch from the host, which a captured graph "
                                       "cannot replay")
@@ -2821,6 +2940,9 @@ class GraphedStep:
         args = dict(softplus=softplus, regularization=regularization, all_timesteps=all_timesteps)
         if score is not None:
             args["score"] = score
+        if temperature is not None:          # (a launch argument of the captured normalise kernels: nothing on the host per step)
+            args["temperature"] = temperature
+            eng._norm_scratch()                # (allocated and zeroed here: torch.cuda.graph synchronises the device on entry)
         # no warm-up run: nothing here initialises lazily on first use except buffers, which the capture allocates from the
         # graph's own pool — and a real step on a dummy batch would move BatchNorm's running statistics
         # captured on ONE stream: a capture with the side-stream forks replays slower (6.4 vs 5.0 ms at B = 256), and the graph

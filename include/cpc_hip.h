@@ -53,6 +53,8 @@ extern "C" {
  *    Added later under 9 (backward compatible, no entry point changed): the loss over grouped negatives
  *    cpc_nce_grouped_workspace_floats, cpc_nce_loss_grouped, cpc_nce_group_mask.
  *    Added later under 9 (backward compatible, no entry point changed): LAMB trust ratios cpc_lamb_workspace_floats, cpc_lamb.
+ *    Added later under 9 (backward compatible, no entry point changed): row normalisation for the cosine-similarity scores
+ *    cpc_norm_rows, cpc_norm_rows_bwd.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -695,6 +697,28 @@ int cpc_diff_scores_bwd(void* G, const float* S, float* sums, void* GT, const fl
                         long long s_batch, int batch, int dtype, void* stream);
 int cpc_diff_scores_rank1(const float* mu, const void* X, void* out, int rows, int E, int rpi, long long item, long long ld, int dtype,
                           void* stream);
+
+/* Row normalisation behind the cosine-similarity scores with a temperature (score kind "normalized"; no counterpart in the reference,
+ * whose scores are the dot product, its softplus and the inverse squared distance):
+ *   scores[b,k,b',k'] = < predicted_z[b,k,:] / max(|predicted_z[b,k,:]|, eps), targets[b',:,k'] / max(|targets[b',:,k']|, eps) > / tau,
+ * i.e. linear scores of F.normalize(predicted_z, dim=2, eps) / tau and F.normalize(targets, dim=1, eps).  Row `row` of X, Y and G starts
+ * at the row address (row, rpi, item, ld) (row addressing above): rpi = 0, ld = E for predicted_z; rpi = K, item = L_top * E, ld = E from
+ * row T - K of the top layer for the K target rows of every item.  Elements the map does not name are never touched.  T: storage type.
+ *   cpc_norm_rows      inv[row] = 1 / max(|X[row]|, eps) (f32 sum of the squares of the stored values, not rescaled) and
+ *                      Y[row] = X[row] * (scale * inv[row]), one rounding to T.  scale = 1 / tau for predictions, 1 for targets.
+ *                      A row of zeros gives zeros; a NaN in a row makes the whole row NaN (torch's clamp_min keeps it too).
+ *   cpc_norm_rows_bwd  overwrites G, d loss / d Y in T, with d loss / d X = scale inv G - (inv / scale) <Y, G> Y per row (autograd's
+ *                      gradient of the expression above: exact for the stored Y and G, f32 dot product, one rounding to T); rows with
+ *                      inv >= 1 / eps (norm at or below eps) take the first term only.
+ * One wave per row, the row in registers between the sum and the scaling (each row read once), 16-byte loads where the rows start
+ * 16-byte aligned (X / Y / G, ld and item in 16-byte units; an E that is no multiple of that width leaves a scalar tail), else scalar
+ * ones; sums in one fixed order (lane chain + xor butterfly): bit-identical from run to run and for any
+ * rows.  CPC_EINVAL before any launch: a NULL pointer, rows < 1, E outside [1, 4096], rpi < 0, scale or eps not finite and > 0, an
+ * unknown dtype. */
+int cpc_norm_rows(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, float scale, float eps,
+                  int dtype, void* stream);
+int cpc_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E, int rpi, long long item, long long ld, float scale,
+                      float eps, int dtype, void* stream);
 
 /* torch.optim.Adam.step with default betas/eps semantics over one flat f32 buffer
  * (contrastive_estimation_training.py:83, :162).  step counts from 1; g is multiplied by grad_scale first.

@@ -198,6 +198,8 @@ _SIGNATURES = {
     "cpc_lr_factors": ([_I, _L, _L, _F, _L, _I, _P, _P], _I),
     "cpc_lamb_workspace_floats": ([_L], _L),
     "cpc_lamb": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _P, _L, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "cpc_ema": ([_P, _P, _L, _F, _I, _I, _P, _P, _P], _I),
+    "cpc_ema_swap": ([_P, _P, _L, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

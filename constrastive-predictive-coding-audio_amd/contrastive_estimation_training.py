@@ -471,6 +471,20 @@ class ContrastiveEstimationTrainer:
         # step) and not with an optimizer other than torch.optim.Adam (a foreign optimizer's direction is not ours to rescale).
         self.trust_ratio = False
         self.trust_clip = None
+        # Not in the reference's signature: an exponential moving average (EMA) of the weights ("EMA of the weights").
+        # ema_decay: None, or d in [0, 1): behind every update, shadow <- shadow + (p - shadow) * (1 - d);
+        # ema_warmup: True uses min(d, (1 + t) / (10 + t)) at the optimizer's update number t, so that a short run's average is not
+        #   held at its start (t counts from the start of a train() call, or from the step count of a loaded optimizer_state).
+        # train() builds a new optimizer on every call, so the trainer owns the shadow: the first train() with a decay starts it as a copy
+        # of the parameters, later calls go on with it, reset_ema() drops it, and an optimizer_state that carries "ema" replaces it.
+        # validate(use_ema=True) / calc_test_task_data(use_ema=True) evaluate the averaged weights, ema_state_dict() exports them.
+        # BatchNorm's running statistics are buffers and are not averaged.  On the fused routes it is engine.FusedAdam's (cpc_ema behind
+        # every update, also inside the captured step of use_graph, frozen by the device NaN guard), on the generic route
+        # engine.TorchEma behind optimizer.step().  Single process or data parallel alike: every rank averages the same parameters.
+        self.ema_decay = None
+        self.ema_warmup = False
+        self._ema = None          # the shadow: a flat f32 tensor shaped like model._flat_param
+        self._ema_owner = None    # who updates it at present: the latest train() call's FusedAdam or TorchEma
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
         self.preprocess_ahead = True
         self.verbose = True
@@ -614,6 +628,44 @@ class ContrastiveEstimationTrainer:
                                       f"{self.optimizer!r} is not ours to rescale")
         return trust_ratio, trust_clip
 
+    def _check_ema(self):
+        """Up-front checks of ema_decay and ema_warmup (before any GPU work): ValueError for a decay that is not None or a number in
+        [0, 1), a warmup that is no bool, or a warmup without a decay.  Returns (ema_decay or None, ema_warmup)."""
+        from .engine import check_ema
+        return check_ema(self.ema_decay, self.ema_warmup)
+
+    def reset_ema(self):
+        """Drops the average: the next train() with an ema_decay starts it over from the parameters as they then stand."""
+        self._ema = self._ema_owner = None
+
+    def ema_state_dict(self):
+        """The model's state_dict() with the parameters taken from the average and the buffers (BatchNorm's running statistics, which
+        are not averaged) from the live model.  ValueError when no average exists."""
+        owner = self._ema_holder()
+        if hasattr(owner, "ema_state_dict"):
+            return owner.ema_state_dict()
+        out = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        out.update(owner.state_dict()["ema"])
+        return out
+
+    def _ema_holder(self):
+        if self._ema is None or self._ema_owner is None:
+            raise ValueError("no average of the weights exists: set ema_decay and train() first")
+        return self._ema_owner
+
+    def _ema_weights(self, use_ema):
+        """Context of validate() / calc_test_task_data(): the averaged weights in the model's place when asked, else nothing."""
+        import contextlib
+        if not use_ema:
+            return contextlib.nullcontext()
+        owner = self._ema_holder()
+        return owner.ema_weights() if hasattr(owner, "ema_weights") else owner.weights()
+
+    def _shadow_views(self):
+        """{parameter name: view of the flat shadow}, the form engine.TorchEma takes."""
+        off = self.model._offset
+        return {n: self._ema[off[n]:off[n] + p.numel()].view(p.shape) for n, p in self.model.named_parameters()}
+
     def _score_kind(self):
         if self.score_function is difference_score_function:
             return "difference"
@@ -700,6 +752,7 @@ class ContrastiveEstimationTrainer:
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
         trust_ratio, trust_clip = self._check_trust()
+        ema_decay, ema_warmup = self._check_ema()
         device = self._device()
         rank, world = self._world()
         self.model.train()
@@ -710,8 +763,15 @@ class ContrastiveEstimationTrainer:
             self.model._flatten_parameters(device)
             graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
             lamb = dict(trust_ratio=True, trust_clip=trust_clip) if trust_ratio else {}
+            if ema_decay is not None:          # (without a decay FusedAdam is called as before the keywords existed)
+                flat = self.model._flat_param
+                if self._ema is not None and (self._ema.shape != flat.shape or self._ema.device != flat.device):
+                    self.reset_ema()          # another model or device: the old average means nothing here
+                lamb.update(ema_decay=ema_decay, ema_warmup=ema_warmup, ema=self._ema)
             optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
                                   decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step), **lamb)
+            if ema_decay is not None:
+                self._ema, self._ema_owner = optimizer.ema, optimizer
             self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
             graph_steps = {}
             glob_neg = {}
@@ -725,6 +785,13 @@ class ContrastiveEstimationTrainer:
                                       trust_clip=trust_clip)
             else:
                 optimizer = self.optimizer(self.model.parameters(), lr=lr)
+        generic_ema = None
+        if ema_decay is not None and not fused:
+            from .engine import TorchEma
+            flat = self.model._flat_param
+            if self._ema is None or self._ema.shape != flat.shape or self._ema.device != flat.device:
+                self._ema = flat.detach().float().clone()
+            generic_ema = self._ema_owner = TorchEma(self.model.named_parameters(), ema_decay, ema_warmup, shadow=self._shadow_views())
         decayed = []
         if weight_decay > 0.0 and not fused and not trust_ratio:          # the generic route multiplies them itself, in front of optimizer.step()
             from .engine import default_decay_filter
@@ -732,6 +799,14 @@ class ContrastiveEstimationTrainer:
         if self.optimizer_state is not None:
             state, self.optimizer_state = self.optimizer_state, None
             optimizer.load_state_dict(state)
+            if generic_ema is not None:          # (FusedAdam.load_state_dict has taken its "ema" itself)
+                entries = state.get("state", {})
+                names = [n for n, _ in self.model.named_parameters()]
+                if entries and all(i in entries and "ema" in entries[i] for i in range(len(names))):
+                    generic_ema.load_state_dict({"ema": {n: entries[i]["ema"] for i, n in enumerate(names)}})
+                else:
+                    with torch.no_grad():
+                        self._ema.copy_(self.model._flat_param.detach())
         sampler = FileBatchSampler(index_count_per_file=self.dataset.get_example_count_per_file(),
                                    batch_size=batch_size * world, file_batch_size=self.file_batch_size, drop_last=True,
                                    verbose=self.verbose)
@@ -950,7 +1025,7 @@ class ContrastiveEstimationTrainer:
                     else:
                         vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm,
                                                   (step_lr if schedule is not None else None, step_lr * weight_decay, decayed),
-                                                  **groups_kw)
+                                                  ema=generic_ema, **groups_kw)
                     stash(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
                         nan_step = flush()
@@ -982,14 +1057,17 @@ class ContrastiveEstimationTrainer:
             return {}
         return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
 
-    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ()), negative_groups=None):
+    def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ()), negative_groups=None,
+                      ema=None):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
         the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133).  With max_grad_norm,
         torch.nn.utils.clip_grad_norm_ runs between the gradient all-reduce and optimizer.step() and the returned values grow by
         (norm before clipping, coefficient); a norm that is not finite raises the indicator and skips the update.
         adamw = (the step's learning rate under a schedule or None, lr * weight_decay of the step, the parameters that decay): every
-        param group gets the rate, and the decay p <- p (1 - lr weight_decay) is applied right before optimizer.step()."""
+        param group gets the rate, and the decay p <- p (1 - lr weight_decay) is applied right before optimizer.step().
+        ema: None or the run's engine.TorchEma, updated right behind optimizer.step() with the number of the updates it has seen (the
+        early returns above it — a NaN loss, a gradient norm that is not finite — leave the average where it is)."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
         if negative_groups is not None:
@@ -1029,10 +1107,26 @@ class ContrastiveEstimationTrainer:
             with torch.no_grad():
                 torch._foreach_mul_(list(decayed), 1.0 - lr_wd)
         optimizer.step()
+        if ema is not None:
+            ema.update(ema.updates + 1)
         return vals
 
     # ------------------------------------------------------------------------------------------ validate
-    def validate(self, batch_size=64, num_workers=1, max_steps=None):
+    def validate(self, batch_size=64, num_workers=1, max_steps=None, use_ema=False):
+        """_validate's measurement; with use_ema=True on the averaged weights (ema_decay): they take the model's place for the call and
+        the raw weights are back afterwards, bit for bit, so it may be called from logger.log() in the middle of train().  ValueError
+        when no average exists.  (The validation sampler seeds Python's random generator, as the reference's does; with use_ema=True
+        the generator's state is put back, so that the epochs train() draws after the call are the ones it would have drawn.)"""
+        if not use_ema:
+            return self._validate(batch_size, num_workers, max_steps)
+        state = random.getstate()
+        try:
+            with self._ema_weights(True):
+                return self._validate(batch_size, num_workers, max_steps)
+        finally:
+            random.setstate(state)
+
+    def _validate(self, batch_size=64, num_workers=1, max_steps=None):
         """Reference validate (:178-269): per-step loss, per-step arg-max accuracy, mean score and the mutual-information lower
         bound log(n) - loss over the validation set (eval mode, FileBatchSampler(seed=0, file_batch_size=8)).  The per-batch
         quantities come from cpc_nce_eval on the train step's own score matrices and are summed on the device; the host reads
@@ -1060,6 +1154,9 @@ class ContrastiveEstimationTrainer:
             for batch in self._batches(self.validation_set, sampler, device, num_workers, False, 0, 1):
                 if done >= steps:
                     break
+                if batch.shape[0] > batch_size:          # (the workspace and the sums above are sized for batch_size)
+                    raise ValueError(f"validate(batch_size={batch_size}): the sampler draws runs of 8 clips per file and handed out a "
+                                     f"batch of {batch.shape[0]}; use a batch size of at least 8")
                 x = self._model_input(batch)
                 if kernel_scores:
                     eng = self.model.engine_for(x)
@@ -1076,8 +1173,13 @@ class ContrastiveEstimationTrainer:
         step_losses, step_accuracy = sums[:K].clone(), sums[K:2 * K].clone()
         return step_losses, step_accuracy, float(sums[2 * K]), math.log(n) - step_losses
 
-    def calc_test_task_data(self, batch_size=64, num_workers=1):
-        """Context vectors c of every item of the test-task set (reference :271-303)."""
+    def calc_test_task_data(self, batch_size=64, num_workers=1, use_ema=False):
+        """Context vectors c of every item of the test-task set (reference :271-303); use_ema=True: from the averaged weights, as in
+        validate()."""
+        with self._ema_weights(use_ema):
+            return self._calc_test_task_data(batch_size, num_workers)
+
+    def _calc_test_task_data(self, batch_size=64, num_workers=1):
         if self.test_task_set is None:
             print("No test task set")
         device = self._device()

@@ -835,4 +835,11 @@ int cpc_lamb(float* p, const float* g, float* m, float* v, long long n, float lr
                        (hipStream_t)stream);
 }
 
+int cpc_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
+            void* stream) {
+    return launch_ema(p, ema, n, decay, warmup, step, state, skip, (hipStream_t)stream);
+}
+
+int cpc_ema_swap(float* p, float* ema, long long n, void* stream) { return launch_ema_swap(p, ema, n, (hipStream_t)stream); }
+
 }  // extern "C"

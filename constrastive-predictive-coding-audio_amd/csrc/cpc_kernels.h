@@ -202,6 +202,10 @@ struct LambTables {
 };
 long long lamb_workspace_floats(long long total_blocks);
 int launch_lamb(const AdamArgs& a, int step, const LambTables& t, hipStream_t stream);
+// The exponential moving average of the weights behind an update, and the exchange of the two buffers (pointwise.hip).
+int launch_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
+               hipStream_t stream);
+int launch_ema_swap(float* p, float* ema, long long n, hipStream_t stream);
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
                       hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);

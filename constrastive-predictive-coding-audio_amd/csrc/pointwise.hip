@@ -594,6 +594,86 @@ int launch_lamb(const AdamArgs& a, int step, const LambTables& t, hipStream_t st
     return CPC_OK;
 }
 
+// ---- EMA of the weights (include/cpc_hip.h: cpc_ema, cpc_ema_swap; DESIGN.md, "EMA of the weights") ----
+// ema = ema + (p - ema) * w, w = 1 - d: the difference rounds once and the product and the sum are one fma written out, so that the
+// float4 body and the tail run the same arithmetic and a buffer averaged in pieces carries the whole call's bits.  w == 1 (decay 0) is
+// the exact result p: (p - ema) + ema rounds twice and would not give it.
+__device__ __forceinline__ float ema_update(float e, float p, float w) {
+#pragma clang fp contract(off)
+    return w == 1.f ? p : __builtin_fmaf(p - e, w, e);
+}
+
+// A launch of its own behind the update (adam_kernel's text is pinned by its tests' bits), of adam_kernel's shape.  With ``state``
+// (FusedAdam.state, advanced by adam_tick_kernel in front of the update) every thread derives w from the device's step count t:
+// 1 - min(decay, (1 + t) / (10 + t)) = max(1 - decay, 9 / (10 + t)), one correctly rounded float division where the host divides in
+// double and rounds once — at most one unit in the last place of w apart.  Otherwise w is the argument.
+__global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ p, float* __restrict__ ema, long long n, float w, float decay,
+                                                  int warmup, const float* __restrict__ state, const float* __restrict__ skip) {
+    // NaN guard, as in adam_kernel: the update in front of this launch was a no-op, so the average stays where it is too
+    if (skip && skip[0] != 0.f) return;
+    if (state) {
+        w = 1.f - decay;
+        if (warmup) w = fmaxf(w, 9.f / (10.f + (float)__float_as_int(state[0])));
+    }
+    const long long n4 = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        // the parameters were just written and are read again by the layout kernels: a plain load.  The average is touched once per
+        // step: non-temporal both ways, as adam_kernel's moments, so that it does not push the backward GEMMs' operands out of the cache
+        const f32x4 pp = ((const f32x4*)p)[i];
+        f32x4 ee = __builtin_nontemporal_load((f32x4*)ema + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ee[e] = ema_update(ee[e], pp[e], w);
+        __builtin_nontemporal_store(ee, (f32x4*)ema + i);
+    }
+    // tail: at most three elements
+    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) ema[i] = ema_update(ema[i], p[i], w);
+}
+
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ ema, long long n) {
+    const long long n4 = n / 4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const f32x4 pp = ((const f32x4*)p)[i], ee = __builtin_nontemporal_load((const f32x4*)ema + i);
+        ((f32x4*)p)[i] = ee;
+        __builtin_nontemporal_store(pp, (f32x4*)ema + i);
+    }
+    for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float pe = p[i];
+        p[i] = ema[i];
+        ema[i] = pe;
+    }
+}
+
+// What both entry points refuse: the buffers move as float4.
+static bool ema_args_ok(const float* p, const float* ema, long long n) {
+    return p && ema && n > 0 && !((uintptr_t)p % 16) && !((uintptr_t)ema % 16);
+}
+
+// adam_stream's grid: at most 2048 workgroups walk the float4 bodies with a grid stride, the "+ 1" keeps a thread for the tail.
+static int ema_blocks(long long n) { return (int)min((long long)2048, (n / 4 + 255) / 256 + 1); }
+
+int launch_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
+               hipStream_t stream) {
+    if (!ema_args_ok(p, ema, n) || !(decay >= 0.f && decay < 1.f) || (!state && step < 1)) return CPC_EINVAL;          // NaN fails the range
+    float w = 0.f;
+    if (!state) {          // in double, rounded once
+        double d = (double)decay;
+        if (warmup) d = fmin(d, (1.0 + (double)step) / (10.0 + (double)step));
+        w = (float)(1.0 - d);
+    }
+    hipLaunchKernelGGL(ema_kernel, dim3(ema_blocks(n)), dim3(256), 0, stream, p, ema, n, w, decay, warmup ? 1 : 0, state, skip);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+int launch_ema_swap(float* p, float* ema, long long n, hipStream_t stream) {
+    if (!ema_args_ok(p, ema, n)) return CPC_EINVAL;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(ema_blocks(n)), dim3(256), 0, stream, p, ema, n);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
 // Operands of a tall (kh,1) convolution computed G output rows per GEMM row (scalogram_engine._col_group): G shifted copies of the kernel
 // in a window of Rw (forward) / Rd (data gradient) rows, zero elsewhere.  W f32 [co][c][kh];
 //   fwd  [dh][co][r][c]  = W[co][c][r - dh]              for dh <= r < dh + kh      (output row G R + dh reads window rows dh .. dh+kh-1)

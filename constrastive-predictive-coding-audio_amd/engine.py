@@ -17,6 +17,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
+import numbers
 from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
@@ -2547,6 +2548,108 @@ def check_trust(trust_ratio, trust_clip=None):
     return trust_ratio, value
 
 
+def check_ema(ema_decay, ema_warmup=False):
+    """(ema_decay as a float or None, ema_warmup): ValueError unless ema_decay is None or a number (no bool) in [0, 1) — what cpc_ema
+    admits —, ema_warmup a bool, and ema_warmup False without a decay."""
+    if not isinstance(ema_warmup, bool):
+        raise ValueError(f"ema_warmup must be True or False, got {ema_warmup!r}")
+    if ema_decay is None:
+        if ema_warmup:
+            raise ValueError("ema_warmup=True needs an ema_decay")
+        return None, False
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, numbers.Real):
+        raise ValueError(f"ema_decay must be None or a number in [0, 1), got {ema_decay!r}")
+    value = float(ema_decay)
+    if not (math.isfinite(value) and 0.0 <= value < 1.0):
+        raise ValueError(f"ema_decay must be None or a number in [0, 1), got {ema_decay!r}")
+    return value, ema_warmup
+
+
+def ema_weight(decay, warmup, t):
+    """w = 1 - d of update number ``t`` (1-based) in Python floats: d = decay, or min(decay, (1 + t) / (10 + t)) under warmup
+    ("EMA of the weights"; cpc_ema's host route computes the same double and rounds it once to float)."""
+    if isinstance(t, bool) or not isinstance(t, int) or t < 1:
+        raise ValueError(f"the number of the update being averaged must be an integer >= 1, got {t!r}")
+    return 1.0 - (min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay)
+
+
+class TorchEma:
+    """The exponential moving average of the weights in torch ops, the definition of DESIGN.md, "EMA of the weights" (include/cpc_hip.h,
+    cpc_ema, is the same on the flat buffer): after update number t, shadow <- shadow + (p - shadow) * (1 - d), d = ``decay`` or, with
+    ``warmup``, min(decay, (1 + t) / (10 + t)); 1 - d == 1 copies the parameter.  Takes ``model.named_parameters()``; CPU or GPU tensors
+    of any float dtype, nothing is read back to the host.  The shadow starts as a copy of the parameters (no bias correction), or is
+    ``shadow`` = {name: tensor of the parameter's shape}, which is then updated in place.  Buffers (BatchNorm's running statistics) are
+    not averaged."""
+
+    def __init__(self, named_parameters, decay, warmup=False, shadow=None):
+        self.decay, self.warmup = check_ema(decay, warmup)
+        if self.decay is None:
+            raise ValueError("TorchEma needs a decay in [0, 1)")
+        self.named = [(n, p) for n, p in named_parameters]
+        if shadow is None:
+            shadow = {n: p.detach().clone() for n, p in self.named}
+        self._check(shadow, "shadow")
+        self.shadow = {n: shadow[n] for n, _ in self.named}
+        self.updates = 0          # the number of the latest update averaged
+        self._swapped = False
+
+    def _check(self, tensors, what):
+        if not isinstance(tensors, dict) or set(tensors) != {n for n, _ in self.named}:
+            raise ValueError(f"{what} must be a dict with one tensor per parameter name")
+        for n, p in self.named:
+            if tuple(tensors[n].shape) != tuple(p.shape):
+                raise ValueError(f"{what} of {n} has shape {tuple(tensors[n].shape)}, expected {tuple(p.shape)}")
+
+    @torch.no_grad()
+    def update(self, t):
+        """Averages the parameters as they stand, as update number ``t`` (1-based: right behind the t-th optimizer.step())."""
+        if self._swapped:
+            raise RuntimeError("TorchEma.update inside weights(): the model holds the averaged weights")
+        w = ema_weight(self.decay, self.warmup, t)
+        for n, p in self.named:
+            e = self.shadow[n]
+            if w == 1.0:
+                e.copy_(p)
+            else:
+                e.add_((p - e) * w)
+        self.updates = t
+
+    @torch.no_grad()
+    def swap(self):
+        """Exchanges parameters and shadow (in-place copies: every engine rebuilds its operand copies)."""
+        for n, p in self.named:
+            e = self.shadow[n]
+            raw = p.detach().clone()
+            p.copy_(e)
+            e.copy_(raw)
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def weights(self):
+        """The model holds the averaged weights inside the block and the raw ones after it, also on an exception; does not nest."""
+        if self._swapped:
+            raise RuntimeError("TorchEma.weights() does not nest")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def state_dict(self):
+        if self._swapped:
+            raise RuntimeError("TorchEma.state_dict inside weights(): the shadow holds the raw weights")
+        return {"decay": self.decay, "warmup": self.warmup, "ema": {n: e.detach().clone() for n, e in self.shadow.items()}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Takes the shadow ('ema': {name: tensor}); decay and warmup stay the constructor's.  ValueError for a missing or misshapen entry."""
+        if self._swapped:
+            raise RuntimeError("TorchEma.load_state_dict inside weights()")
+        self._check(state_dict.get("ema") if isinstance(state_dict, dict) else None, "state_dict['ema']")
+        for n, e in self.shadow.items():
+            e.copy_(state_dict["ema"][n])
+
+
 class TorchLamb(torch.optim.Optimizer):
     """LAMB in torch ops, the definition of DESIGN.md, "LAMB trust ratios" (include/cpc_hip.h, cpc_lamb, is the same on the flat
     buffer): Adam's moments and bias-corrected direction r; u = r + weight_decay * p on the parameters
@@ -2667,8 +2770,20 @@ class FusedAdam:
 
     def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None,
                  weight_decay: float = 0.0, decay_filter=None, schedule=None, step_offset: int = 0, trust_ratio: bool = False,
-                 trust_clip=None):
+                 trust_clip=None, ema_decay=None, ema_warmup: bool = False, ema=None):
         self.model = model
+        # ema_decay / ema_warmup / ema ("EMA of the weights"): every update issued by _update is followed by a cpc_ema launch
+        # over the same range, stream, step number and skip flag.  self.ema is the shadow, a flat f32 tensor shaped like the parameter
+        # buffer: the caller's ``ema`` (updated in place) or a copy of the parameters as they stand.  Without a decay it is None: nothing
+        # is allocated and no launch is added.
+        self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
+        if ema is not None:
+            if self.ema_decay is None:
+                raise ValueError("ema given without an ema_decay")
+            flat_ = model._flat_param
+            if (not isinstance(ema, torch.Tensor) or ema.dtype != torch.float32 or tuple(ema.shape) != tuple(flat_.shape)
+                    or ema.device != flat_.device or not ema.is_contiguous()):
+                raise ValueError(f"ema must be a contiguous float32 tensor of shape {tuple(flat_.shape)} on {flat_.device}")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         # weight_decay / decay_filter / schedule / step_offset ("AdamW and the learning-rate schedule").  Step number i of
         # this object (0-based, counted from construction or from load_state_dict) has the schedule index step_offset + i and runs at
@@ -2695,6 +2810,8 @@ class FusedAdam:
             self._lamb_tables()
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
+        self.ema = None if self.ema_decay is None else (ema if ema is not None else flat.detach().clone())
+        self._ema_in = False          # True inside ema_weights(): the model holds the averaged weights, self.ema the raw ones
         self.t = 0
         self._done_lo = None
         self._piece_scale = 1.0
@@ -2735,6 +2852,7 @@ class FusedAdam:
         the ranks, with the step count of the step in progress; step(grad_scale) then updates the head of the buffer."""
         if self.state is not None:
             raise ValueError("piecewise updates need the host-side step count (device_step=False)")
+        self._not_swapped_in()
         self._done_lo = lo if self._done_lo is None else min(self._done_lo, lo)
         self._piece_scale = float(grad_scale)
         if self.max_grad_norm is not None:          # the update waits for the norm of the whole gradient: step()
@@ -2752,7 +2870,8 @@ class FusedAdam:
         if hi <= lo:
             return
         if self.trust_ratio:
-            return self._update_lamb(lo, hi, t, grad_scale, coef)
+            self._update_lamb(lo, hi, t, grad_scale, coef)
+            return self._update_ema(lo, hi, t)
         model, dev, decayed = self.model, self.state is not None, self.decay_bits is not None
         model._raw_updates = getattr(model, "_raw_updates", 0) + 1
         dev_schedule = dev and (decayed or self.schedule is not None)
@@ -2776,6 +2895,63 @@ class FusedAdam:
         else:
             name, tail = "cpc_adam", []
         _hip.call(name, *head, *tail, _hip.ptr(self.skip_flag))
+        self._update_ema(lo, hi, t)
+
+    def _update_ema(self, lo, hi, t):
+        """The average of flat_param[lo:hi) behind its update as step ``t``: one cpc_ema launch on the update's stream, under its skip
+        flag; under device_step the step count is the device's (self.state, which the update has advanced).  Every range starts at a
+        parameter, a 64-float boundary, so the pieces carry the whole buffer's bits."""
+        if self.ema is None:
+            return
+        dev = self.state is not None
+        _hip.call("cpc_ema", _hip.ptr(self.model._flat_param, lo), _hip.ptr(self.ema, lo), C.c_longlong(hi - lo), C.c_float(self.ema_decay),
+                  1 if self.ema_warmup else 0, 0 if dev else t, _hip.ptr(self.state) if dev else None, _hip.ptr(self.skip_flag))
+
+    # ---- the averaged weights in the model's place
+    def _not_swapped_in(self):
+        if self._ema_in:
+            raise RuntimeError("an optimizer step inside ema_weights(): the model holds the averaged weights")
+
+    def swap_ema(self):
+        """Exchanges the parameter buffer and the shadow (cpc_ema_swap over the whole buffer) and bumps model._raw_updates: every
+        engine's prepare_weights() rebuilds its operand copies and a pending prepare_ahead token is void.  An evaluation-time call: it
+        waits for the device first, so that nothing on another stream still reads or writes the parameters."""
+        if self.ema is None:
+            raise ValueError("swap_ema() needs FusedAdam(ema_decay=...)")
+        model = self.model
+        if model._flat_param.is_cuda:
+            torch.cuda.synchronize(model._flat_param.device)
+        _hip.call("cpc_ema_swap", _hip.ptr(model._flat_param), _hip.ptr(self.ema), C.c_longlong(model._flat_param.numel()))
+        model._raw_updates = getattr(model, "_raw_updates", 0) + 1
+        self._ema_in = not self._ema_in
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The model computes with the averaged weights inside the block and has its raw ones back after it, bit for bit, also on an
+        exception.  RuntimeError when nested, and while pieces of a step are outstanding; step() / update_range() refuse inside."""
+        if self.ema is None:
+            raise ValueError("ema_weights() needs FusedAdam(ema_decay=...)")
+        if self._ema_in:
+            raise RuntimeError("ema_weights() does not nest")
+        if self._done_lo is not None:
+            raise RuntimeError("ema_weights() between the pieces of a step and its step(): the parameters are half updated")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self):
+        """The model's state_dict() with every parameter taken from the shadow and every buffer from the live model (copies).
+        BatchNorm's running statistics are buffers: they are not averaged."""
+        if self.ema is None:
+            raise ValueError("ema_state_dict() needs FusedAdam(ema_decay=...)")
+        source = self.model._flat_param if self._ema_in else self.ema
+        out = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for name, p in self.model.named_parameters():
+            lo = self.model._offset[name]
+            out[name] = source[lo:lo + p.numel()].view(p.shape).detach().clone()
+        return out
 
     def _lamb_tables(self):
         """The per-parameter buffers of cpc_lamb, from model._offset (parameters in buffer order, each at a 64-float boundary, its
@@ -2848,6 +3024,9 @@ class FusedAdam:
             lo, n = offset[name], p.numel()
             state[i] = {"step": torch.tensor(float(self.t)), "exp_avg": self.m[lo:lo + n].view(p.shape).clone(),
                         "exp_avg_sq": self.v[lo:lo + n].view(p.shape).clone()}
+            if self.ema is not None:          # (the shadow rides along, as a fourth per-parameter tensor; without it: Adam's dict)
+                self._not_swapped_in()
+                state[i]["ema"] = self.ema[lo:lo + n].view(p.shape).clone()
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": True, "params": list(range(len(state)))}
@@ -2863,11 +3042,15 @@ class FusedAdam:
         if saved and sorted(saved) != list(range(len(named))):
             raise ValueError(f"the state dict has entries {sorted(saved)} for {len(named)} parameters")
         steps = set()
+        # the shadow: taken where every entry carries it, otherwise started over from the parameters as they stand
+        takes_ema = self.ema is not None and bool(saved) and all("ema" in saved[i] for i in range(len(named)))
+        if self.ema is not None:
+            self._not_swapped_in()
         for i, (name, p) in enumerate(named):
             if not saved:
                 break
             entry = saved[i]
-            for key in ("exp_avg", "exp_avg_sq"):
+            for key in ("exp_avg", "exp_avg_sq") + (("ema",) if takes_ema else ()):
                 if tuple(entry[key].shape) != tuple(p.shape):
                     raise ValueError(f"{key} of parameter {i} ({name}) has shape {tuple(entry[key].shape)}, expected {tuple(p.shape)}")
             steps.add(int(entry["step"]))
@@ -2882,6 +3065,10 @@ class FusedAdam:
                 lo, n = offset[name], p.numel()
                 self.m[lo:lo + n].view(p.shape).copy_(saved[i]["exp_avg"])
                 self.v[lo:lo + n].view(p.shape).copy_(saved[i]["exp_avg_sq"])
+                if takes_ema:
+                    self.ema[lo:lo + n].view(p.shape).copy_(saved[i]["ema"])
+            if self.ema is not None and not takes_ema:
+                self.ema.copy_(self.model._flat_param.detach())
             self.t = self._t0 = steps.pop() if steps else 0
             self._done_lo = None
             if self.state is not None:          # cpc_adam_dev keeps the count as the bits of an int
@@ -2896,6 +3083,7 @@ class FusedAdam:
         return _hip.ptr(self.clip_state, 1)
 
     def step(self, grad_scale: float = 1.0):
+        self._not_swapped_in()
         self._scheduled_lr(self.t)
         self.t += 1
         hi, clip = self.model._flat_param.numel(), self.max_grad_norm is not None

@@ -55,6 +55,8 @@ extern "C" {
  *    Added later under 9 (backward compatible, no entry point changed): LAMB trust ratios cpc_lamb_workspace_floats, cpc_lamb.
  *    Added later under 9 (backward compatible, no entry point changed): row normalisation for the cosine-similarity scores
  *    cpc_norm_rows, cpc_norm_rows_bwd.
+ *    Added later under 9 (backward compatible, no entry point changed): the exponential moving average of the weights cpc_ema,
+ *    cpc_ema_swap.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -832,6 +834,30 @@ int cpc_lamb(float* p, const float* g, float* m, float* v, long long n, float lr
              float grad_scale, float weight_decay, const unsigned* select_bits, long long first_block, const float* coef,
              const int* param_block, const int* param_block_dev, const int* block_param, int first_param, int n_params,
              int total_params, float trust_clip, float* workspace, float* trust, const float* skip, void* stream);
+
+
+/* Exponential moving average (EMA) of the weights behind an optimizer update (not in the reference's train step; DESIGN.md, "EMA of
+ * the weights").  For every i in [0, n):
+ *   ema[i] = ema[i] + (p[i] - ema[i]) * w,   w = 1 - d
+ *   d = decay                                 when warmup == 0
+ *   d = min(decay, (1 + t) / (10 + t))        otherwise; t is the 1-based number of the update being averaged.
+ * One float32 rounding for the difference and one for the fused product and sum; w == 1 (decay 0) stores p[i] itself.  The same data
+ * give the same bits for any split of the buffer into ranges that start at multiples of four floats.
+ *   state == NULL (host route): t = step, step >= 1; w is formed in double and rounded once to float.
+ *   state != NULL (device route): state is the f32[4] of cpc_adam_dev / cpc_adamw_dev, t the int whose bits are in state[0], which
+ *     that call has already advanced; step is ignored.  Every thread forms w = max(1 - decay, 9 / (10 + t)) in float (the same
+ *     number, at most one unit in the last place of w from the host route's).  No argument changes from step to step, so the launch
+ *     can be captured behind cpc_adam_dev.
+ *   skip as in cpc_adam: while *skip != 0 the call changes nothing.
+ * p is read with plain loads, ema is read and written non-temporally (it is touched once per step).  One launch, no scratch memory,
+ * no atomics.  CPC_EINVAL before any launch: p or ema NULL, n <= 0, p or ema not 16-byte aligned, decay outside [0, 1) or not
+ * finite, step < 1 on the host route.
+ * cpc_ema_swap exchanges p[i] and ema[i] for every i in [0, n) in one pass (the averaged weights go into the model and the raw ones
+ * are parked in ema; a second call restores both).  CPC_EINVAL: p or ema NULL, n <= 0, p or ema not 16-byte aligned.  p and ema must
+ * not overlap, in either call. */
+int cpc_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
+            void* stream);
+int cpc_ema_swap(float* p, float* ema, long long n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,10 @@ _SIGNATURES = {
     "cpc_diff_scores_rank1": ([_P, _P, _P, _I, _I, _I, _L, _L, _I, _P], _I),
     "cpc_norm_rows": ([_P, _P, _P, _I, _I, _I, _L, _L, _F, _F, _I, _P], _I),
     "cpc_norm_rows_bwd": ([_P, _P, _P, _I, _I, _I, _L, _L, _F, _F, _I, _P], _I),
+    "cpc_norm_rows_dev": ([_P, _P, _P, _I, _I, _I, _L, _L, _P, _F, _I, _P], _I),
+    "cpc_norm_rows_bwd_dev": ([_P, _P, _P, _P, _I, _I, _I, _L, _L, _P, _F, _I, _P], _I),
+    "cpc_temperature_step": ([_P, _P, _I, _F, _F, _F, _F, _I, _P, _F, _F, _F, _P, _P], _I),
+    "cpc_temperature_set": ([_P, _I, _D, _D, _L, _L, _P, _L, _P], _I),
     "cpc_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P], _I),
     "cpc_adam_dev": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _F, _P, _P], _I),
     "cpc_grad_norm_workspace_floats": ([_L], _L),

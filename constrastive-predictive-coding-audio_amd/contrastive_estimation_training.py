@@ -31,6 +31,7 @@ from . import switches
 from .sampled_negatives import (check_negatives, empty_negative_sets, file_group_ids, group_mode,        # noqa: F401
                                 grouped_negative_mask, sampled_negative_mask)                                        # (public: the host restatements)
 from .engine import LRSchedule          # noqa: F401  (public: trainer.lr_schedule takes one)
+from .engine import DeviceTemperature, TemperatureSchedule          # noqa: F401  (public: NormalizedScoreFunction(schedule=...))
 
 
 def _need_gpu(t, what):
@@ -220,21 +221,70 @@ class NormalizedScoreFunction:
     linear_score_function(F.normalize(predicted_z, dim=2) / temperature, F.normalize(targets, dim=1)).  Bounded by 1 / temperature
     whatever the norms of the encodings.  As ``score_function=`` of ContrastiveEstimationTrainer with Adam the whole step runs on the
     engine (score kind "normalized"); called on tensors it is an autograd function over the same kernels (f32: cpc_norm_rows, the score
-    contraction, cpc_norm_rows_bwd).  The temperature is a constant of the run (finite and > 0)."""
+    contraction, cpc_norm_rows_bwd).  The temperature (finite and > 0) is a constant of the run, or
+      learnable=True: a parameter of the run, s = log(1 / temperature), trained by Adam beside the weights at
+        lr * schedule factor * ``temperature_lr_scale`` (the run's betas and eps, no decay) and kept inside
+        [min_temperature, max_temperature]; ``temperature`` is where it starts.  Engine route, one process;
+      schedule=TemperatureSchedule(...): step s of the run scores at schedule.value(s) (``temperature`` is then ignored).
+    In both cases the trainer keeps the value in device memory (engine.DeviceTemperature; DESIGN.md, "Learnable and scheduled
+    temperature"); called on tensors, the function uses the value as it stands as a constant."""
 
-    def __init__(self, temperature=0.1):
-        from .engine import check_temperature
+    def __init__(self, temperature=0.1, learnable=False, min_temperature=0.01, max_temperature=1.0, temperature_lr_scale=1.0,
+                 schedule=None):
+        from .engine import check_temperature, check_temperature_bounds, check_temperature_range
+        if not isinstance(learnable, bool):
+            raise ValueError(f"learnable must be True or False, got {learnable!r}")
+        if schedule is not None and not isinstance(schedule, TemperatureSchedule):
+            raise ValueError(f"schedule must be None or a TemperatureSchedule, got {schedule!r}")
+        if learnable and schedule is not None:
+            raise ValueError("a temperature is either learnable or scheduled, not both")
+        self.learnable, self.schedule = learnable, schedule
+        if schedule is not None:
+            temperature = schedule.value(0)
+        # (the pair is checked in every mode, so that a bad one does not wait for learnable=True to be noticed; only a learnable
+        # temperature has to start inside it)
+        self.min_temperature, self.max_temperature = check_temperature_range(min_temperature, max_temperature)
         self.temperature = check_temperature(temperature)
+        if learnable:
+            check_temperature_bounds(self.temperature, self.min_temperature, self.max_temperature)
+        try:
+            self.temperature_lr_scale = float(temperature_lr_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"temperature_lr_scale must be a finite number >= 0, got {temperature_lr_scale!r}") from None
+        if isinstance(temperature_lr_scale, bool) or not math.isfinite(self.temperature_lr_scale) or self.temperature_lr_scale < 0.0:
+            raise ValueError(f"temperature_lr_scale must be a finite number >= 0, got {temperature_lr_scale!r}")
+        self.device_temperature = None          # the trainer's engine.DeviceTemperature, once a run has made one
+
+    def make_device_temperature(self, device):
+        """The engine.DeviceTemperature of this configuration on ``device`` (None for a constant)."""
+        if self.learnable:
+            return DeviceTemperature(self.temperature, "learnable", self.min_temperature, self.max_temperature,
+                                     self.temperature_lr_scale, device=device)
+        if self.schedule is not None:
+            return DeviceTemperature(mode="scheduled", schedule=self.schedule, device=device)
+        return None
+
+    def current_temperature(self):
+        """The value as it stands: the device's (one synchronous read) where a run keeps it there, else the constant."""
+        if self.device_temperature is not None:
+            return self.device_temperature.value()
+        return self.temperature
 
     def __repr__(self):
-        return f"NormalizedScoreFunction(temperature={self.temperature!r})"
+        extra = ""
+        if self.learnable:
+            extra = (f", learnable=True, min_temperature={self.min_temperature!r}, max_temperature={self.max_temperature!r}, "
+                     f"temperature_lr_scale={self.temperature_lr_scale!r}")
+        elif self.schedule is not None:
+            extra = f", schedule={self.schedule!r}"
+        return f"NormalizedScoreFunction(temperature={self.temperature!r}{extra})"
 
     def __call__(self, predicted_z, targets):
         _need_gpu(predicted_z, "the normalized score function")
         B, K, E = predicted_z.shape
         if tuple(targets.shape) != (B, E, K):
             raise ValueError("normalized scores: expected predicted_z (B, K, E) and targets (B, E, K)")
-        pn = _NormalizeRows.apply(predicted_z.reshape(B * K, E), 1.0 / self.temperature).view(B, K, E)
+        pn = _NormalizeRows.apply(predicted_z.reshape(B * K, E), 1.0 / self.current_temperature()).view(B, K, E)
         tn = _NormalizeRows.apply(targets.permute(0, 2, 1).reshape(B * K, E), 1.0).view(B, K, E).permute(0, 2, 1)
         return _ScoreContraction.apply(pn, tn)
 
@@ -483,6 +533,12 @@ class ContrastiveEstimationTrainer:
         # engine.TorchEma behind optimizer.step().  Single process or data parallel alike: every rank averages the same parameters.
         self.ema_decay = None
         self.ema_warmup = False
+        # Not in the reference: NormalizedScoreFunction(learnable=True) / (schedule=...) keep the temperature in device memory
+        # (engine.DeviceTemperature), which the trainer owns across train() calls: the learned value, its Adam moments and the schedule's
+        # place carry on, and optimizer_state["temperature"] (FusedAdam.state_dict() writes it) replaces them.  last_temperature: the
+        # value behind the latest step read back; every step's value goes to logger.temperature_meter where the logger has one.
+        self._temperature = None
+        self.last_temperature = None
         self._ema = None          # the shadow: a flat f32 tensor shaped like model._flat_param
         self._ema_owner = None    # who updates it at present: the latest train() call's FusedAdam or TorchEma
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
@@ -674,11 +730,42 @@ class ContrastiveEstimationTrainer:
         return "softplus" if self.score_function is softplus_score_function else "linear"
 
     def _score_kw(self):
-        """The engine's score keywords: score=kind and, with NormalizedScoreFunction, its temperature."""
+        """The engine's score keywords: score=kind and, with NormalizedScoreFunction, its temperature — the device's where this
+        trainer keeps one for that function, else the constant."""
         kw = {"score": self._score_kind()}
         if kw["score"] == "normalized":
-            kw["temperature"] = self.score_function.temperature
+            sf = self.score_function
+            own = self._temperature is not None and sf.device_temperature is self._temperature
+            kw["temperature"] = self._temperature if own else sf.temperature
         return kw
+
+    def _check_temperature(self, world):
+        """Up-front checks of a learnable or scheduled temperature (before any GPU work): NotImplementedError for learnable=True off
+        the engine route (a foreign optimizer, global_negatives) or in a data-parallel run.  Returns None (a constant, or another score
+        function), "device" (the engine route keeps it in device memory) or "host" (a schedule on the generic route or under data
+        parallelism: the constant is set to schedule.value(step) before every step)."""
+        sf = self.score_function
+        if not isinstance(sf, NormalizedScoreFunction) or not (sf.learnable or sf.schedule is not None):
+            return None
+        if sf.learnable:
+            if not self._engine_normalized():
+                raise NotImplementedError("a learnable temperature is trained by the fused optimizer on the engine route "
+                                          "(optimizer=torch.optim.Adam, no global_negatives): a foreign optimizer does not know the scalar, "
+                                          "and under global_negatives its gradient is spread over the ranks")
+            if world > 1:
+                raise NotImplementedError("a learnable temperature in a data-parallel run: the scalar's gradient would need a reduction "
+                                          "of its own over the ranks")
+            return "device"
+        return "device" if self._engine_normalized() and world == 1 else "host"
+
+    def _device_temperature(self, device):
+        """The DeviceTemperature this trainer keeps for its score function, made on first use."""
+        sf = self.score_function
+        kept = self._temperature
+        if kept is None or sf.device_temperature is not kept or kept.device != torch.device(device):
+            kept = self._temperature = sf.make_device_temperature(device)
+            sf.device_temperature = kept
+        return kept
 
     @staticmethod
     def _world():
@@ -755,8 +842,16 @@ class ContrastiveEstimationTrainer:
         ema_decay, ema_warmup = self._check_ema()
         device = self._device()
         rank, world = self._world()
+        temp_route = self._check_temperature(world)
         self.model.train()
         fused = self._fused() or self._engine_difference() or self._engine_normalized()
+        device_temp = None
+        if temp_route == "device":
+            device_temp = self._device_temperature(device)
+            device_temp.bind(None)          # (a captured step of an earlier call had it read the step from its optimizer's count)
+        elif temp_route == "host":          # the callable's constant follows the schedule; no device value takes part
+            self.score_function.device_temperature = self._temperature = None
+            self.score_function.temperature = self.score_function.schedule.value(int(continue_training_at_step))
         score_kw = self._score_kw()
         if fused:
             from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
@@ -768,6 +863,8 @@ class ContrastiveEstimationTrainer:
                 if self._ema is not None and (self._ema.shape != flat.shape or self._ema.device != flat.device):
                     self.reset_ema()          # another model or device: the old average means nothing here
                 lamb.update(ema_decay=ema_decay, ema_warmup=ema_warmup, ema=self._ema)
+            if device_temp is not None:          # (without one FusedAdam is called as before the keyword existed)
+                lamb.update(temperature=device_temp)
             optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
                                   decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step), **lamb)
             if ema_decay is not None:
@@ -820,14 +917,16 @@ class ContrastiveEstimationTrainer:
         ring, ring_pos = [], [0]
 
         clip = max_grad_norm is not None
-        width = 8 if clip else 6          # with clipping: + the norm before clipping and the coefficient applied (clip_state[0:2])
+        base_width = 8 if clip else 6     # with clipping: + the norm before clipping and the coefficient applied (clip_state[0:2])
+        width = base_width + (1 if device_temp is not None else 0)          # + the temperature as the step left it (tstate[5])
 
         def stash(step, vals):
             """Queues a step's (loss, max score) for the logger.  On the GPU they travel to a pinned host buffer right behind the
             step's own kernels and an event marks their arrival: reading them later does not wait for LATER steps' work, which a
             synchronous read of a device tensor — queued behind everything launched since — would."""
+            host_tau = self.score_function.temperature if temp_route == "host" else None
             if not on_gpu:
-                pending.append((step, vals.detach()[:width].clone(), None, self.last_lr))
+                pending.append((step, vals.detach()[:width].clone(), None, self.last_lr, host_tau))
                 return
             need = self.host_sync_interval + self.host_sync_lag + 2
             while len(ring) < need:
@@ -836,25 +935,28 @@ class ContrastiveEstimationTrainer:
             ring_pos[0] += 1
             if clip and fused:          # the engine's result cell and FusedAdam.clip_state: two copies, one event
                 buf[:6].copy_(vals.detach()[:6].float(), non_blocking=True)
-                buf[6:].copy_(optimizer.clip_state[:2], non_blocking=True)
+                buf[6:base_width].copy_(optimizer.clip_state[:2], non_blocking=True)
             else:
-                buf.copy_(vals.detach()[:width].float(), non_blocking=True)
+                buf[:base_width].copy_(vals.detach()[:base_width].float(), non_blocking=True)
+            if device_temp is not None:          # the same buffer and event: no further wait
+                buf[base_width:].copy_(device_temp.tstate[5:6], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            pending.append((step, buf, ev, self.last_lr))          # (the host knows the step's learning rate: it rides along)
+            pending.append((step, buf, ev, self.last_lr, host_tau))          # (the host knows the step's learning rate: it rides along)
 
         bad_grad_norm = [False]
 
         def flush(keep=0):
             """Reads back all pending steps but the ``keep`` most recent ones (in order); returns the step of a NaN loss."""
             n = max(len(pending) - keep, 0)
-            for step, vals, ev, lr_v in pending[:n]:
+            for step, vals, ev, lr_v, host_tau in pending[:n]:
                 if ev is not None:
                     ev.synchronize()
                 row = vals.tolist()
                 loss_v, score_v, nan_v = float(row[0]), float(row[1]), float(row[5])        # cpc_nce_loss: out[0], out[1], out[5]
                 if clip:
                     self.last_grad_norm = float(row[6])
+                tau_v = float(row[base_width]) if device_temp is not None else host_tau
                 # reference order (:124-133 before :164-169): a NaN loss ends the run before anything is logged for that step
                 if nan_v != 0.0 or math.isnan(loss_v):
                     # (the indicator is also what cpc_grad_norm raises: a finite loss under it means the gradient was the cause)
@@ -868,9 +970,13 @@ class ContrastiveEstimationTrainer:
                         self.logger.grad_norm_meter.update(self.last_grad_norm)
                     if hasattr(self.logger, "lr_meter"):
                         self.logger.lr_meter.update(lr_v)
+                    if tau_v is not None and hasattr(self.logger, "temperature_meter"):
+                        self.logger.temperature_meter.update(tau_v)
                     self.logger.log(step)
                 elif self.verbose:
                     print("loss at step step " + str(step) + ":", loss_v)
+                if tau_v is not None:
+                    self.last_temperature = tau_v
             del pending[:n]
             return None
 
@@ -958,6 +1064,11 @@ class ContrastiveEstimationTrainer:
                     self.last_lr = step_lr = lr if schedule is None else lr * schedule.factor(self.training_step)
                     if fused and schedule is not None:
                         optimizer.lr = step_lr
+                    if device_temp is not None:          # scheduled: the tick's step (a captured step reads the device's count instead)
+                        device_temp.step = int(self.training_step)
+                    elif temp_route == "host":
+                        self.score_function.temperature = score_kw["temperature"] = \
+                            self.score_function.schedule.value(int(self.training_step))
                     if fused and graphed:
                         eng = self.model.engine(batch.shape[0], batch.shape[1], device)
                         key = (batch.shape[0], batch.shape[1])

@@ -788,6 +788,36 @@ int cpc_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E,
     return launch_norm_rows_bwd(Y, inv, G, rows, E, rpi, item, ld, scale, eps, dtype, (hipStream_t)stream);
 }
 
+int cpc_norm_rows_dev(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, const float* scale,
+                      float eps, int dtype, void* stream) {
+    if (!X || !Y || !inv || !scale || !norm_rows_args_ok(rows, E, rpi, 1.f, eps, dtype)) return CPC_EINVAL;
+    return launch_norm_rows_dev(X, Y, inv, rows, E, rpi, item, ld, scale, eps, dtype, (hipStream_t)stream);
+}
+
+int cpc_norm_rows_bwd_dev(const void* Y, const float* inv, void* G, float* dots, int rows, int E, int rpi, long long item, long long ld,
+                          const float* scale, float eps, int dtype, void* stream) {
+    if (!Y || !inv || !G || !dots || !scale || !norm_rows_args_ok(rows, E, rpi, 1.f, eps, dtype)) return CPC_EINVAL;
+    return launch_norm_rows_bwd_dev(Y, inv, G, dots, rows, E, rpi, item, ld, scale, eps, dtype, (hipStream_t)stream);
+}
+
+int cpc_temperature_step(float* tstate, const float* dots, int rows, float lr, float beta1, float beta2, float eps, int step,
+                         const float* adam_state, float grad_scale, float s_min, float s_max, const float* skip, void* stream) {
+    if (!tstate || !dots || rows < 1 || (!adam_state && step < 1)) return CPC_EINVAL;
+    for (float x : {lr, beta1, beta2, eps, grad_scale, s_min, s_max})
+        if (!std::isfinite(x)) return CPC_EINVAL;
+    if (s_min > s_max) return CPC_EINVAL;
+    return launch_temperature_step(tstate, dots, rows, lr, beta1, beta2, eps, step, adam_state, grad_scale, s_min, s_max, skip,
+                                   (hipStream_t)stream);
+}
+
+int cpc_temperature_set(float* tstate, int kind, double start, double end, long long total_steps, long long step, const float* adam_state,
+                        long long step_offset, void* stream) {
+    if (!tstate || kind < 0 || kind > 1 || total_steps < 1 || !(std::isfinite(start) && start > 0.0) || !(std::isfinite(end) && end > 0.0))
+        return CPC_EINVAL;
+    if (adam_state ? step_offset < 0 : step < 0) return CPC_EINVAL;
+    return launch_temperature_set(tstate, kind, start, end, total_steps, step, adam_state, step_offset, (hipStream_t)stream);
+}
+
 int cpc_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
              float grad_scale, const float* skip, void* stream) {
     return launch_adam({p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, skip, nullptr, 0.f, nullptr, 0}, step, false, (hipStream_t)stream);

@@ -178,6 +178,16 @@ int launch_norm_rows(const void* X, void* Y, float* inv, int rows, int E, int rp
                      int dtype, hipStream_t stream);
 int launch_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E, int rpi, long long item, long long ld, float scale,
                          float eps, int dtype, hipStream_t stream);
+// The same two with the scale read from device memory (scale[0]); the backward also writes dots[row] = <Y[row], G[row]> (nrows.hip).
+int launch_norm_rows_dev(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, const float* scale,
+                         float eps, int dtype, hipStream_t stream);
+int launch_norm_rows_bwd_dev(const void* Y, const float* inv, void* G, float* dots, int rows, int E, int rpi, long long item, long long ld,
+                             const float* scale, float eps, int dtype, hipStream_t stream);
+// The temperature's Adam update from the per-row dots, and its schedule tick (nrows.hip); arguments checked by the entry points.
+int launch_temperature_step(float* tstate, const float* dots, int rows, float lr, float b1, float b2, float eps, int step,
+                            const float* adam_state, float grad_scale, float s_min, float s_max, const float* skip, hipStream_t stream);
+int launch_temperature_set(float* tstate, int kind, double start, double end, long long total_steps, long long step,
+                           const float* adam_state, long long step_offset, hipStream_t stream);
 int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype, hipStream_t stream);
 long long grad_norm_workspace_floats(long long n);
 int launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, float* workspace, float* state, float* nan_pair,

@@ -52,6 +52,8 @@ def check_temperature(temperature, kind: Optional[str] = None):
         return None
     if temperature is None:
         raise ValueError("score='normalized' needs a temperature (finite and > 0)")
+    if isinstance(temperature, DeviceTemperature):          # checked when it was built; the float checks below are for floats
+        return temperature
     try:
         value = float(temperature)
     except (TypeError, ValueError):
@@ -59,6 +61,175 @@ def check_temperature(temperature, kind: Optional[str] = None):
     if not math.isfinite(value) or value <= 0.0:
         raise ValueError(f"temperature must be a positive finite number, got {temperature!r}")
     return value
+
+
+def check_temperature_range(min_temperature, max_temperature):
+    """(min_temperature, max_temperature) as floats: ValueError unless both are finite and > 0 and in order."""
+    out = []
+    for value, what in ((min_temperature, "min_temperature"), (max_temperature, "max_temperature")):
+        try:
+            number = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a positive finite number, got {value!r}") from None
+        if isinstance(value, bool) or not math.isfinite(number) or number <= 0.0:
+            raise ValueError(f"{what} must be a positive finite number, got {value!r}")
+        out.append(number)
+    lo, hi = out
+    if lo > hi:
+        raise ValueError(f"min_temperature ({lo!r}) must not exceed max_temperature ({hi!r})")
+    return lo, hi
+
+
+def check_temperature_bounds(temperature, min_temperature, max_temperature):
+    """(temperature, min_temperature, max_temperature) as floats: check_temperature_range's checks, and ValueError unless the
+    temperature is finite and > 0 and lies inside the pair."""
+    lo, hi = check_temperature_range(min_temperature, max_temperature)
+    tau = check_temperature(temperature)
+    if not lo <= tau <= hi:
+        raise ValueError(f"temperature {tau!r} lies outside [min_temperature, max_temperature] = [{lo!r}, {hi!r}]")
+    return tau, lo, hi
+
+
+class TemperatureSchedule:
+    """An annealed temperature: step ``s`` (0-based) scores at ``value(s)``, with q = min(s / total_steps, 1):
+    'linear': start + (end - start) q;  'cosine': end + (start - end) * 0.5 (1 + cos(pi q)).  From step ``total_steps`` on it stays at
+    ``end``.  cpc_temperature_set evaluates the same function on the device, in double."""
+
+    KINDS = ("linear", "cosine")
+
+    def __init__(self, kind, start, end, total_steps):
+        if kind not in self.KINDS:
+            raise ValueError(f"TemperatureSchedule kind must be one of {self.KINDS}, got {kind!r}")
+        if isinstance(total_steps, bool) or not isinstance(total_steps, int) or total_steps < 1:
+            raise ValueError(f"TemperatureSchedule total_steps must be an integer >= 1, got {total_steps!r}")
+        self.kind, self.total_steps = kind, total_steps
+        self.start, self.end = check_temperature(start), check_temperature(end)
+
+    def value(self, step):
+        """The temperature of the step with 0-based index ``step``, in Python floats (the tick's expressions)."""
+        if isinstance(step, bool) or not isinstance(step, int) or step < 0:
+            raise ValueError(f"the step index must be an integer >= 0, got {step!r}")
+        q = min(step / self.total_steps, 1.0)
+        if self.kind == "linear":
+            return self.start + (self.end - self.start) * q
+        return self.end + (self.start - self.end) * (0.5 * (1.0 + math.cos(math.pi * q)))
+
+    def abi_args(self):
+        """(kind, start, end, total_steps) as cpc_temperature_set takes them."""
+        return self.KINDS.index(self.kind), C.c_double(self.start), C.c_double(self.end), C.c_longlong(self.total_steps)
+
+    def __repr__(self):
+        return f"TemperatureSchedule({self.kind!r}, start={self.start!r}, end={self.end!r}, total_steps={self.total_steps})"
+
+
+class DeviceTemperature:
+    """The temperature of the "normalized" score as device state (include/cpc_hip.h, cpc_temperature_step / cpc_temperature_set;
+    DESIGN.md, "Learnable and scheduled temperature"): ``tstate`` f32[8] = {s = log(1 / tau), scale = exp(s), Adam's m and v of s, the
+    latest d loss / d s, tau, 0, 0}.  The normalise kernels read the scale from it, so a captured step can change it.
+      mode "learnable": FusedAdam(temperature=this) updates s behind every parameter update, at lr * ``lr_scale``, and clamps tau to
+        [min_temperature, max_temperature];
+      mode "scheduled": every loss call sets tau = ``schedule``.value(step) in front of its normalise launches; ``step`` is this object's
+        0-based count (the trainer sets it to its training step, FusedAdam advances it), or the device's own under a captured step
+        (``bind``).
+    Passed as ``temperature=`` wherever a float is; an evaluation (nce_eval) reads the value as it stands."""
+
+    MODES = ("learnable", "scheduled")
+
+    def __init__(self, temperature=0.1, mode="learnable", min_temperature=0.01, max_temperature=1.0, lr_scale=1.0, schedule=None,
+                 device=None):
+        if mode not in self.MODES:
+            raise ValueError(f"DeviceTemperature mode must be one of {self.MODES}, got {mode!r}")
+        if mode == "scheduled":
+            if not isinstance(schedule, TemperatureSchedule):
+                raise ValueError(f"mode 'scheduled' needs a TemperatureSchedule, got {schedule!r}")
+            temperature = schedule.value(0)
+            self.min_temperature = self.max_temperature = None
+        else:
+            if schedule is not None:
+                raise ValueError("a learnable temperature takes no schedule")
+            temperature, self.min_temperature, self.max_temperature = check_temperature_bounds(temperature, min_temperature,
+                                                                                                max_temperature)
+        try:
+            self.lr_scale = float(lr_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"lr_scale must be a finite number >= 0, got {lr_scale!r}") from None
+        if isinstance(lr_scale, bool) or not math.isfinite(self.lr_scale) or self.lr_scale < 0.0:
+            raise ValueError(f"lr_scale must be a finite number >= 0, got {lr_scale!r}")
+        self.mode, self.schedule = mode, schedule
+        self.device = torch.device("cuda" if device is None else device)
+        self.tstate = torch.zeros(8, device=self.device, dtype=torch.float32)
+        self.step = 0                 # scheduled: the 0-based index of the step the next loss call belongs to
+        self.dots = None              # the per-row dots of the latest backward (the engine's scratch): what cpc_temperature_step adds up
+        self._adam_state, self._step_offset = None, 0
+        self._fill(temperature)
+
+    @staticmethod
+    def host_state(temperature):
+        """(s, scale, tau) as float32 values: scale = float32(1 / tau) — the bits the constant path passes as its launch argument —,
+        s = log of that value, tau rounded once."""
+        import numpy as np
+        scale = np.float32(1.0 / float(temperature))
+        return float(np.float32(math.log(float(scale)))), float(scale), float(np.float32(float(temperature)))
+
+    def _fill(self, temperature, m=0.0, v=0.0, g=0.0, s=None, scale=None, tau=None):
+        s0, scale0, tau0 = self.host_state(temperature)
+        if s is not None:          # a saved s: the derived values as saved, else as the kernel forms them (double, rounded once)
+            import numpy as np
+            s0 = float(np.float32(s))
+            scale0 = float(np.float32(math.exp(s0))) if scale is None else float(scale)
+            tau0 = float(np.float32(math.exp(-s0))) if tau is None else float(tau)
+        self.tstate.copy_(torch.tensor([s0, scale0, m, v, g, tau0, 0.0, 0.0], dtype=torch.float32))
+
+    @property
+    def bounds(self):
+        """(s_min, s_max) = (log(1 / max_temperature), log(1 / min_temperature)) of the learnable mode."""
+        return math.log(1.0 / self.max_temperature), math.log(1.0 / self.min_temperature)
+
+    def bind(self, adam_state, step_offset=0):
+        """Scheduled mode inside a captured step: the tick takes its step from the device (``adam_state``, the f32[4] of FusedAdam under
+        device_step, whose count is the number of steps finished) plus ``step_offset``.  bind(None) goes back to this object's ``step``."""
+        self._adam_state, self._step_offset = adam_state, int(step_offset)
+
+    def scale_ptr(self):
+        return _hip.ptr(self.tstate, 1)
+
+    def tick(self):
+        """Scheduled mode: queues cpc_temperature_set for the step at hand on the current stream (nothing in learnable mode)."""
+        if self.mode != "scheduled":
+            return
+        bound = self._adam_state is not None
+        _hip.call("cpc_temperature_set", _hip.ptr(self.tstate), *self.schedule.abi_args(), C.c_longlong(0 if bound else self.step),
+                  _hip.ptr(self._adam_state), C.c_longlong(self._step_offset if bound else 0))
+
+    def value(self):
+        """The temperature as it stands (tstate[5]); waits for the device."""
+        return float(self.tstate[5].item())
+
+    def state_dict(self):
+        """{'mode', 's', 'm', 'v', 'step'} and the derived 'scale', 'tau' and latest gradient 'g', with one synchronous read."""
+        row = self.tstate.detach().cpu().tolist()
+        return {"mode": self.mode, "s": row[0], "scale": row[1], "m": row[2], "v": row[3], "g": row[4], "tau": row[5],
+                "step": int(self.step)}
+
+    def load_state_dict(self, state):
+        """Takes s, m and v (and the schedule's step); ValueError for another mode or a missing or non-finite entry.  In scheduled mode
+        the next tick overwrites the value from ``step``."""
+        if not isinstance(state, dict) or state.get("mode") != self.mode:
+            raise ValueError(f"the saved temperature has mode {state.get('mode') if isinstance(state, dict) else state!r}, "
+                             f"this one is {self.mode!r}")
+        try:
+            s, m, v = (float(state[k]) for k in ("s", "m", "v"))
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("the saved temperature needs finite numbers 's', 'm' and 'v'") from None
+        if not all(math.isfinite(x) for x in (s, m, v)):
+            raise ValueError("the saved temperature needs finite numbers 's', 'm' and 'v'")
+        extra = {k: float(state[k]) for k in ("scale", "tau") if isinstance(state.get(k), float) and math.isfinite(state[k])}
+        g = float(state["g"]) if isinstance(state.get("g"), float) and math.isfinite(state["g"]) else 0.0
+        self._fill(math.exp(-s), m, v, g, s=s, **extra)
+        self.step = int(state.get("step", self.step))
+
+    def __repr__(self):
+        return f"DeviceTemperature(mode={self.mode!r}, schedule={self.schedule!r}, lr_scale={self.lr_scale})"
 
 
 def check_negatives_supported(negatives, all_timesteps=False, global_negatives=None, gradient_penalty=None, negative_groups=None):
@@ -895,27 +1066,42 @@ class CPCEngine:
             R = self.B * self.K
             n = self._norm = SimpleNamespace(pn=torch.empty_like(self.pred), tn=torch.zeros_like(self.act[-1]),
                                              inv_p=torch.empty(R, device=self.device, dtype=torch.float32),
-                                             inv_t=torch.empty(R, device=self.device, dtype=torch.float32))
+                                             inv_t=torch.empty(R, device=self.device, dtype=torch.float32), dots=None)
         return n
 
-    def _norm_operands(self, temperature: float):
+    def _norm_dots(self):
+        """dots (R floats) of the scratch, allocated when a DeviceTemperature first comes by (a float temperature never needs it)."""
+        n = self._norm_scratch()
+        if n.dots is None:
+            n.dots = torch.zeros(self.B * self.K, device=self.device, dtype=torch.float32)
+        return n.dots
+
+    def _norm_operands(self, temperature, tick: bool = False):
         """The score operands of the "normalized" kind, from the engine's own layouts: pn = predicted_z rows / max(norm, eps) /
         temperature (shaped like self.pred) and tn = the K target rows of every item / max(norm, eps) inside a zero buffer shaped like
         the top layer (only rows [T-K, T) are ever written).  Scratch allocated on first use; 1 / max(norm, eps) per row stays in
-        inv_p / inv_t (f32) for the backward."""
+        inv_p / inv_t (f32) for the backward.  ``temperature``: a float (the launch argument), or a DeviceTemperature: the prediction
+        rows then go through cpc_norm_rows_dev, which reads the scale from its tstate, and with ``tick`` a scheduled one is set for the
+        step at hand first (cpc_temperature_set; an evaluation leaves the value as it stands)."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
         R = B * K
         n = self._norm_scratch()
         P, L, tg = _hip.ptr, C.c_longlong, (T - K) * E
         nbytes = 2.0 * R * E * self.pred.element_size()
-        _hip.call("cpc_norm_rows", P(self.pred), P(n.pn), P(n.inv_p), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
-                  C.c_float(NORM_EPS), code, work=nbytes)
+        if isinstance(temperature, DeviceTemperature):
+            if tick:
+                temperature.tick()
+            _hip.call("cpc_norm_rows_dev", P(self.pred), P(n.pn), P(n.inv_p), R, E, 0, L(0), L(E), temperature.scale_ptr(),
+                      C.c_float(NORM_EPS), code, work=nbytes)
+        else:
+            _hip.call("cpc_norm_rows", P(self.pred), P(n.pn), P(n.inv_p), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
+                      C.c_float(NORM_EPS), code, work=nbytes)
         _hip.call("cpc_norm_rows", P(self.act[-1], tg), P(n.tn, tg), P(n.inv_t), R, E, K, L(Ltop * E), L(E), C.c_float(1.0),
                   C.c_float(NORM_EPS), code, work=nbytes)
         return n.pn, n.tn
 
-    def _norm_forward_backward(self, all_timesteps: bool, regularization: float, temperature: float, negatives=None,
+    def _norm_forward_backward(self, all_timesteps: bool, regularization: float, temperature, negatives=None,
                                negative_groups=None):
         """InfoNCE loss + regulariser on cosine-similarity scores over a temperature and d loss / d (predicted_z, targets): the rows
         are normalised (cpc_norm_rows; predictions also divided by the temperature), the linear score's own chain — score GEMM, loss
@@ -923,7 +1109,10 @@ class CPCEngine:
         contractions — runs on the normalised operands, and cpc_norm_rows_bwd turns the gradients with respect to the normalised rows
         into those with respect to the rows, in place in dpred and in rows [T-K, T) of the top-layer gradient.  All on the current
         stream: the target-row lane of backward() starts from those rows behind the event it records there.
-        ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward)."""
+        ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward).  A DeviceTemperature takes
+        the _dev kernels for the prediction rows: the scale comes from its tstate (set first in scheduled mode), and the backward leaves
+        dots[row] = <pn[row], d loss / d pn[row]> in the scratch, whose sum is d loss / d log(1 / tau) for every loss chain above —
+        FusedAdam(temperature=...) adds them up (cpc_temperature_step)."""
         grouped = None
         if negative_groups is not None:
             check_negatives_supported(negatives, all_timesteps, negative_groups=negative_groups)
@@ -936,7 +1125,10 @@ class CPCEngine:
         dtop = self.dact[-1]
         R = B * K
         P, L, tg = _hip.ptr, C.c_longlong, (T - K) * E
-        pn, tn = self._norm_operands(temperature)
+        on_device = isinstance(temperature, DeviceTemperature)
+        if on_device:
+            temperature.dots = self._norm_dots()
+        pn, tn = self._norm_operands(temperature, tick=True)
         if all_timesteps and self.fused_scores_ok():
             self._nce_all_fused(False, regularization, pn, tn)
         elif all_timesteps:
@@ -958,8 +1150,12 @@ class CPCEngine:
             self._score_grads(self.dS, self.dST, pn, tn, self.dpred, dtop)
         n = self._norm
         nbytes = 3.0 * R * E * self.pred.element_size()
-        _hip.call("cpc_norm_rows_bwd", P(pn), P(n.inv_p), P(self.dpred), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
-                  C.c_float(NORM_EPS), code, work=nbytes)
+        if on_device:
+            _hip.call("cpc_norm_rows_bwd_dev", P(pn), P(n.inv_p), P(self.dpred), P(n.dots), R, E, 0, L(0), L(E), temperature.scale_ptr(),
+                      C.c_float(NORM_EPS), code, work=nbytes)
+        else:
+            _hip.call("cpc_norm_rows_bwd", P(pn), P(n.inv_p), P(self.dpred), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
+                      C.c_float(NORM_EPS), code, work=nbytes)
         _hip.call("cpc_norm_rows_bwd", P(tn, tg), P(n.inv_t), P(dtop, tg), R, E, K, L(Ltop * E), L(E), C.c_float(1.0),
                   C.c_float(NORM_EPS), code, work=nbytes)
 
@@ -2770,8 +2966,15 @@ class FusedAdam:
 
     def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, device_step: bool = False, max_grad_norm=None,
                  weight_decay: float = 0.0, decay_filter=None, schedule=None, step_offset: int = 0, trust_ratio: bool = False,
-                 trust_clip=None, ema_decay=None, ema_warmup: bool = False, ema=None):
+                 trust_clip=None, ema_decay=None, ema_warmup: bool = False, ema=None, temperature=None):
         self.model = model
+        # temperature ("Learnable and scheduled temperature"): a DeviceTemperature.  In learnable mode step() issues one
+        # cpc_temperature_step behind its final update — the same stream, step number and skip flag — at lr * temperature.lr_scale: the
+        # scalar's gradient is no part of cpc_grad_norm, is not scaled by the clipping coefficient and gets no trust ratio and no decay.
+        # In scheduled mode step() only advances the object's step index.  None: no launch is added.
+        if temperature is not None and not isinstance(temperature, DeviceTemperature):
+            raise ValueError(f"temperature must be None or a DeviceTemperature, got {temperature!r}")
+        self.temperature = temperature
         # ema_decay / ema_warmup / ema ("EMA of the weights"): every update issued by _update is followed by a cpc_ema launch
         # over the same range, stream, step number and skip flag.  self.ema is the shadow, a flat f32 tensor shaped like the parameter
         # buffer: the caller's ``ema`` (updated in place) or a copy of the parameters as they stand.  Without a decay it is None: nothing
@@ -2907,6 +3110,26 @@ class FusedAdam:
         _hip.call("cpc_ema", _hip.ptr(self.model._flat_param, lo), _hip.ptr(self.ema, lo), C.c_longlong(hi - lo), C.c_float(self.ema_decay),
                   1 if self.ema_warmup else 0, 0 if dev else t, _hip.ptr(self.state) if dev else None, _hip.ptr(self.skip_flag))
 
+    def _update_temperature(self, t, grad_scale):
+        """The temperature behind the step's final update, as step ``t``.  Learnable: Adam on s = log(1 / tau) from the dots the latest
+        backward left (cpc_temperature_step), with the run's betas and eps; under device_step the step size comes from self.state, which
+        the update has advanced (state[1] carries lr * schedule factor / (1 - beta1^t)), times lr_scale.  Scheduled: the step index moves on."""
+        temp = self.temperature
+        if temp is None:
+            return
+        if temp.mode == "scheduled":
+            temp.step = self.step_offset + t - self._t0
+            return
+        if temp.dots is None:
+            raise ValueError("FusedAdam(temperature=...): no backward pass has run with this DeviceTemperature (pass it as temperature= of "
+                             "the loss call)")
+        dev = self.state is not None
+        s_min, s_max = temp.bounds
+        _hip.call("cpc_temperature_step", _hip.ptr(temp.tstate), _hip.ptr(temp.dots), int(temp.dots.numel()),
+                  C.c_float(temp.lr_scale if dev else self.lr * temp.lr_scale), C.c_float(self.betas[0]), C.c_float(self.betas[1]),
+                  C.c_float(self.eps), 0 if dev else t, _hip.ptr(self.state) if dev else None, C.c_float(grad_scale), C.c_float(s_min),
+                  C.c_float(s_max), _hip.ptr(self.skip_flag))
+
     # ---- the averaged weights in the model's place
     def _not_swapped_in(self):
         if self._ema_in:
@@ -3030,7 +3253,10 @@ class FusedAdam:
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": True, "params": list(range(len(state)))}
-        return {"state": state, "param_groups": [group]}
+        out = {"state": state, "param_groups": [group]}
+        if self.temperature is not None:          # (the scalar rides along under a key of its own; without it: Adam's dict)
+            out["temperature"] = self.temperature.state_dict()
+        return out
 
     def load_state_dict(self, state_dict):
         """Takes the moments and the step count of a state dict in torch.optim.Adam's format (an empty 'state' — an optimizer that
@@ -3073,6 +3299,9 @@ class FusedAdam:
             self._done_lo = None
             if self.state is not None:          # cpc_adam_dev keeps the count as the bits of an int
                 self.state[0:1].copy_(torch.tensor([self.t], dtype=torch.int32).view(torch.float32))
+        if self.temperature is not None and state_dict.get("temperature") is not None:
+            self.temperature.load_state_dict(state_dict["temperature"])
+            self.temperature.step = self.step_offset
 
     def _grad_norm(self, grad_scale):
         """Queues the norm of grad_scale * (whole flat gradient) — under data parallelism the gradient summed over the ranks, the same
@@ -3096,6 +3325,7 @@ class FusedAdam:
             self._done_lo = None
         coef = self._grad_norm(grad_scale) if clip else None
         self._update(0, hi, self.t, grad_scale, coef)
+        self._update_temperature(self.t, grad_scale)
         if self.after_update is not None and self.state is None:
             self.after_update(0, hi, True)
 
@@ -3131,6 +3361,16 @@ class GraphedStep:
         if temperature is not None:          # (a launch argument of the captured normalise kernels: nothing on the host per step)
             args["temperature"] = temperature
             eng._norm_scratch()                # (allocated and zeroed here: torch.cuda.graph synchronises the device on entry)
+        if isinstance(temperature, DeviceTemperature):
+            # device state: the captured kernels read and write tstate, and a scheduled one takes its step from the optimizer's own count
+            # on the device (the count starts at opt._t0 where the schedule stands at opt.step_offset)
+            eng._norm_dots()
+            if temperature.mode == "scheduled":
+                if opt.step_offset - opt._t0 < 0:
+                    raise ValueError(f"the loaded step count {opt._t0} lies beyond step_offset {opt.step_offset}")
+                temperature.bind(opt.state, opt.step_offset - opt._t0)
+            elif opt.temperature is not temperature:
+                raise ValueError("a learnable DeviceTemperature needs FusedAdam(temperature=...) with the same object")
         # no warm-up run: nothing here initialises lazily on first use except buffers, which the capture allocates from the
         # graph's own pool — and a real step on a dummy batch would move BatchNorm's running statistics
         # captured on ONE stream: a capture with the side-stream forks replays slower (6.4 vs 5.0 ms at B = 256), and the graph

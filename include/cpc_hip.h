@@ -56,7 +56,7 @@ extern "C" {
  *    Added later under 9 (backward compatible, no entry point changed): row normalisation for the cosine-similarity scores
  *    cpc_norm_rows, cpc_norm_rows_bwd.
  *    Added later under 9 (backward compatible, no entry point changed): the exponential moving average of the weights cpc_ema,
- *    cpc_ema_swap.
+ *    cpc_ema_swap; the temperature in device memory cpc_norm_rows_dev, cpc_norm_rows_bwd_dev, cpc_temperature_step, cpc_temperature_set.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -721,6 +721,44 @@ int cpc_norm_rows(const void* X, void* Y, float* inv, int rows, int E, int rpi, 
                   int dtype, void* stream);
 int cpc_norm_rows_bwd(const void* Y, const float* inv, void* G, int rows, int E, int rpi, long long item, long long ld, float scale,
                       float eps, int dtype, void* stream);
+
+/* A learnable or scheduled temperature ("Learnable and scheduled temperature"): the scale of the prediction rows lives in
+ * device memory, so that a captured step can change it.  tstate f32[8] (device):
+ *   [0] s = log(scale)   [1] scale = exp(s), what the two _dev kernels read   [2], [3] Adam's m and v of s
+ *   [4] the latest g = d loss / d s, after grad_scale   [5] tau = 1 / scale   [6], [7] zero.
+ *   cpc_norm_rows_dev      cpc_norm_rows with the scale read from scale[0] (device pointer, pass tstate + 1): for the same value it
+ *                          writes cpc_norm_rows' bits.
+ *   cpc_norm_rows_bwd_dev  cpc_norm_rows_bwd with the scale read from scale[0]; it also writes dots[row] = <Y[row], G[row]> (f32, over the
+ *                          stored values, in the order of the kernel's own dot product, before G is overwritten), for every row: a row
+ *                          whose norm was clamped still carries the scale.  dX has cpc_norm_rows_bwd's bits.  With pn = scale * p^ and
+ *                          s = log(scale), d loss / d s = sum over the rows of <pn[row], d loss / d pn[row]> = the sum of dots.
+ *   CPC_EINVAL as for cpc_norm_rows (the scale's value is not inspected), and for scale or dots NULL.
+ *   cpc_temperature_step   g = grad_scale * sum(dots[0 .. rows)), one workgroup of 256 threads (thread i adds dots[i], dots[i + 256], ...
+ *                          in that order, then a fixed tree in LDS: no atomics, the same data give the same bits); then
+ *                          torch.optim.Adam's update of s without decay (cpc_adam's expressions in float32), s <- clamp(s, s_min, s_max),
+ *                          scale = exp(s) and tau = exp(-s), each formed in double and rounded once.  tstate[0 .. 5] are written.
+ *                          adam_state NULL: lr is the step's rate and the bias corrections of ``step`` (>= 1) are formed on the host in
+ *                          double and rounded once, as in cpc_adam.  adam_state given (the f32[4] of cpc_adam_dev / cpc_adamw_dev, which
+ *                          that call has already advanced; ``step`` is ignored): the step size is adam_state[1] * lr — lr then carries
+ *                          only the scalar's own multiplier — and the second-moment correction adam_state[2]; no argument changes from
+ *                          step to step, so the launch can be captured.  skip as in cpc_adam: while *skip != 0 nothing is written.
+ *                          CPC_EINVAL before any launch: tstate or dots NULL, rows < 1, s_min > s_max, lr, beta1, beta2, eps, grad_scale,
+ *                          s_min or s_max not finite, step < 1 without adam_state.
+ *   cpc_temperature_set    a one-thread tick: tau of the 0-based step, in double (as cpc_lr_factors evaluates its factor), with
+ *                          q = min(step / total_steps, 1):  kind 0 (linear) tau = start + (end - start) q;  kind 1 (cosine)
+ *                          tau = end + (start - end) * 0.5 (1 + cos(pi q)).  Writes tstate[1] = (float)(1.0 / tau), tstate[0] = the log of
+ *                          that float and tstate[5] = (float)tau.  adam_state given: step = step_offset + the device's step count (the
+ *                          steps finished so far; ``step`` is ignored), so the launch can be captured in front of a step.
+ *                          CPC_EINVAL: tstate NULL, kind outside {0, 1}, total_steps < 1, start or end not finite and > 0, a negative
+ *                          step (step_offset with adam_state). */
+int cpc_norm_rows_dev(const void* X, void* Y, float* inv, int rows, int E, int rpi, long long item, long long ld, const float* scale,
+                      float eps, int dtype, void* stream);
+int cpc_norm_rows_bwd_dev(const void* Y, const float* inv, void* G, float* dots, int rows, int E, int rpi, long long item, long long ld,
+                          const float* scale, float eps, int dtype, void* stream);
+int cpc_temperature_step(float* tstate, const float* dots, int rows, float lr, float beta1, float beta2, float eps, int step,
+                         const float* adam_state, float grad_scale, float s_min, float s_max, const float* skip, void* stream);
+int cpc_temperature_set(float* tstate, int kind, double start, double end, long long total_steps, long long step, const float* adam_state,
+                        long long step_offset, void* stream);
 
 /* torch.optim.Adam.step with default betas/eps semantics over one flat f32 buffer
  * (contrastive_estimation_training.py:83, :162).  step counts from 1; g is multiplied by grad_scale first.

@@ -406,7 +406,9 @@ int cpc_bn_apply(const void* x, const int* gx, void* out, const int* go, const f
                  int relu, int x_f32, int dtype, void* stream);
 /* Backward: g = dy * (y > 0) if relu.  cpc_bn_bwd_reduce: slabs [nblocks][2][C] partials of (sum g*xhat, sum g) = (dgamma,
  * dbeta) to be summed by cpc_reduce_slabs; cpc_bn_bwd_apply: dx = gamma*rstd*(g - dbeta/count - xhat*dgamma/count) with
- * train != 0, g*gamma*rstd otherwise (running statistics). */
+ * train != 0, g*gamma*rstd otherwise (running statistics).  With relu = 0 the activation is not read: both calls accept y = NULL
+ * (the tangent pass of the gradient penalty calls them so); with relu != 0 a NULL y is CPC_EINVAL.  The reductions take C a multiple
+ * of 4 up to 1024 (their shared-memory layout); the two apply passes take any multiple of 4. */
 int cpc_bn_bwd_reduce(const void* dy, const void* y, const int* gy, const void* x, const int* gx, const float* stats, float* slabs,
                       int relu, int nblocks, int x_f32, int dtype, void* stream);
 int cpc_bn_bwd_apply(const void* dy, const void* y, const int* gy, const void* x, void* dx, const int* gx, const float* stats,
@@ -424,12 +426,18 @@ int cpc_bn_bwd_apply_bits(const void* dy, const void* y_bits, const int* gy, con
                           const float* gamma, const float* dgamma, const float* dbeta, double count, int train, int dtype, void* stream);
 /* nn.MaxPool2d(kernel = stride = p): ceil mode (residual branches, scalogram_model.py:434-436; window clipped at the border)
  * or floor mode (main-branch pooling, :401-403; remainder dropped) according to the extents of the output grid; the backward
- * routes dout to the first maximum of each window (+= if accumulate; positions outside every window are not written). */
+ * routes dout to the first maximum of each window in (dh outer, dw inner) scan order (+= if accumulate).
+ * Contract of accumulate = 0: the call writes EXACTLY the positions covered by a window — the gradient at the first maximum, 0 at
+ * the window's other positions.  In ceil mode that is every valid position; in floor mode the dropped remainder rows / columns are
+ * not written and keep whatever din held: the caller owns them (clear din first, or never write them).  Pad and guard rows are
+ * never written. */
 int cpc_maxpool2d_fwd(const void* in, const int* gi, void* out, const int* go, int p, int in_f32, int dtype, void* stream);
 int cpc_maxpool2d_bwd(const void* in, void* din, const int* gi, const void* dout, const int* go, int p, int accumulate, int dtype,
                       void* stream);
 /* out = act(a + r(w + ow, h + oh)) — the cropped residual add (scalogram_model.py:453-472) with the inter-block ReLU
- * (:525-526) folded in; backward: da = g, dr(w + ow, h + oh) = g with g = dout * (out > 0) if relu (dr is cleared by the caller).
+ * (:525-526) folded in; backward: da = g, dr(w + ow, h + oh) = g with g = dout * (out > 0) if relu.  Contract: the backward writes dr
+ * only inside the crop window and leaves every position outside it untouched — a caller that wants zeros there clears dr once (the
+ * engine relies on its allocation's zeros: every step overwrites the same interior).  With relu = 0, out is not read and may be NULL.
  * r_f32: the residual grid r / dr is float32 although dtype is bf16 (first block, see x_f32 above). */
 int cpc_residual_add(const void* a, const int* ga, const void* r, const int* gr, void* out, const int* go, int oh, int ow, int relu,
                      int r_f32, int dtype, void* stream);

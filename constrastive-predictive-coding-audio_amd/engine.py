@@ -279,6 +279,18 @@ def normalize_negative_groups(negative_groups, B, negatives=None):
     return groups, mode, check_group_negatives(B, n_neg), seed, draw
 
 
+def select_negatives(B, negatives, negative_groups, all_timesteps=False, global_negatives=None):
+    """The negative selection of a loss call, checked (check_negatives_supported) and normalised once for every score kind, as the
+    loss-kernel stage takes it: None (the whole batch), ("sampled", n_neg, seed, draw) or ("grouped", groups, mode, n_neg, seed, draw)."""
+    if negative_groups is not None:
+        check_negatives_supported(negatives, all_timesteps, global_negatives, negative_groups=negative_groups)
+        return ("grouped",) + normalize_negative_groups(negative_groups, B, negatives)
+    if negatives is not None:
+        check_negatives_supported(negatives, all_timesteps, global_negatives)
+        return ("sampled",) + normalize_negatives(negatives, B)
+    return None
+
+
 def side_stream(device):
     """ONE high-priority side stream per device for the whole process, shared by every engine: HIP multiplexes its streams
     onto a few hardware queues, and an engine created late in a process that had made one stream per engine ended up with a
@@ -760,6 +772,39 @@ class CPCEngine:
         return pred, targets, z, self.ctx.c_float().clone()
 
     # ------------------------------------------------------------------------------------------ loss
+    # One chain for every score kind and both branches (_loss_chain); each stage below is written once.
+    @property
+    def ldS_all(self):
+        """Leading dimension of the (B K) x (B K) matrices of the all-timesteps branch."""
+        R = self.B * self.K
+        return _ceil_div(R, 8) * 8
+
+    def _all_scores(self):
+        """S_all, allocated on first use: all that score_gemm_all and nce_eval need of the all-timesteps buffers."""
+        if getattr(self, "S_all", None) is None:
+            self.S_all = torch.zeros(self.B * self.K * self.ldS_all, device=self.device, dtype=torch.float32)
+        return self.S_all
+
+    def _all_buffers(self):
+        """(S_all, ST_all, dS_all, dST_all) of the unfused all-timesteps loss, and its workspace nce_all_ws (allocated on first use)."""
+        S = self._all_scores()
+        if getattr(self, "ST_all", None) is None:
+            self.ST_all = torch.zeros_like(S)
+            self.dS_all = torch.zeros(S.numel(), device=self.device, dtype=self.dt)
+            self.dST_all = torch.zeros(S.numel(), device=self.device, dtype=self.dt)
+            self.nce_all_ws = torch.empty(int(_hip.lib().cpc_nce_all_workspace_floats(self.B, self.K)), device=self.device,
+                                          dtype=torch.float32)
+        return S, self.ST_all, self.dS_all, self.dST_all
+
+    def _loss_buffers(self, all_timesteps: bool, transposed: bool):
+        """(S, ST, dS, dST) of a branch.  The default branch's transposed scores ST exist only for the kinds whose fix-up reads them
+        (``transposed``; allocated on first use, else None): its loss kernels write dST from S themselves."""
+        if all_timesteps:
+            return self._all_buffers()
+        if transposed and getattr(self, "ST", None) is None:
+            self.ST = torch.zeros_like(self.S)
+        return self.S, (self.ST if transposed else None), self.dS, self.dST
+
     def score_gemm(self, pred=None, top=None, out=None):
         """The score contraction of the default branch (contrastive_estimation_training.py:12-22 restricted to equal steps,
         :116): K batched B x E x B products S[k] = predicted_z[:, k, :] targets[:, :, k]^T.  Returns its algorithmic FLOPs."""
@@ -776,12 +821,10 @@ class CPCEngine:
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
         R = B * K
-        ld = _ceil_div(R, 8) * 8
-        if getattr(self, "S_all", None) is None:
-            self.S_all = torch.zeros(R * ld, device=self.device, dtype=torch.float32)
+        S = self._all_scores()
         pred = self.pred if pred is None else pred
         top = self.act[-1] if top is None else top
-        _hip.gemm_nt(_hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(self.S_all if out is None else out), R, R, E, E, E, ld, code,
+        _hip.gemm_nt(_hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(S if out is None else out), R, R, E, E, E, self.ldS_all, code,
                      b_rpi=K, b_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
         return 2.0 * R * R * E
 
@@ -791,56 +834,100 @@ class CPCEngine:
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
         (B x B) blocks of the reference's (B K)^2 score tensor are ever formed (12x fewer FLOPs).
-        ``score``: see score_kind; "difference" runs _diff_forward_backward, "normalized" (with its ``temperature``)
-        _norm_forward_backward.
+        ``score``: see score_kind; every kind (with the ``temperature`` of "normalized") runs _loss_chain.
         ``negatives``: None, or (n_neg, seed, draw) — every target is contrasted against n_neg seeded negatives instead of the
         whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask).
         ``negative_groups``: None, or (groups, mode) — groups an int32 device tensor [B], mode "same" / "other": a target's candidates
         are the rows of its own group / of the other groups, all of them or, with ``negatives``, n_neg seeded ones
         (cpc_nce_loss_grouped; sampled_negatives.grouped_negative_mask)."""
         kind = score_kind(softplus, score)
-        temperature = check_temperature(temperature, kind)
-        if kind == "difference":
-            return self._diff_forward_backward(False, regularization, negatives, negative_groups)
+        self._loss_chain(kind, False, regularization, check_temperature(temperature, kind), negatives, negative_groups)
+
+    def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, temperature=None):
+        """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
+        matrix (and its transpose, as a second tiny GEMM, so that both gradient layouts are written coalesced), the
+        log-sum-exp over ALL predictions for every (target item, step), and d loss / d (predicted_z, targets): _loss_chain.
+        bf16 storage and tile-sized problems take the fused route (_nce_all_fused) instead, "normalized" scores (with their
+        ``temperature``) on the normalised operands; difference scores never do (cpc_score_lse is a dot-product kernel)."""
+        kind = score_kind(softplus, score)
+        self._loss_chain(kind, True, regularization, check_temperature(temperature, kind))
+
+    def _loss_chain(self, kind: str, all_timesteps: bool, regularization: float, temperature=None, negatives=None,
+                    negative_groups=None):
+        """InfoNCE loss + regulariser on the scores of ``kind`` and d loss / d (predicted_z, targets), into dpred and rows [T-K, T) of
+        the top-layer gradient.  The stages, in order:
+          selection   select_negatives: checked and normalised before anything of the engine but B is read
+          operands    as they are; "normalized": the rows over their norms, predictions also over the temperature (_norm_operands)
+          scores      _scores: score GEMM(s) or cpc_diff_scores
+          loss        _nce_loss: dense, sampled, grouped or all-timesteps kernel ("linear" scores for every kind but "softplus", as
+                      contrastive_estimation_training._InfoNCE does); or scores and loss in one, _nce_all_fused, where
+                      fused_scores_ok() holds
+          fix-up      "difference": _diff_coefficients
+          gradients   the linear score's two contractions, _score_grads / _score_grads_all
+          operands'   "difference": the rank-1 terms (_diff_rank1); "normalized": cpc_norm_rows_bwd, in place (_norm_backward)
+          backward
+        All on the current stream: the target-row lane of backward() starts from those rows behind the event it records there.
+        ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward)."""
+        selection = select_negatives(self.B, negatives, negative_groups, all_timesteps)
+        pred, top, dpred, dtop = self.pred, self.act[-1], self.dpred, self.dact[-1]
         if kind == "normalized":
-            return self._norm_forward_backward(False, regularization, temperature, negatives, negative_groups)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
-        top, dtop = self.act[-1], self.dact[-1]
-        grouped = None
-        if negative_groups is not None:
-            grouped = normalize_negative_groups(negative_groups, B, negatives)
-        elif negatives is not None:
-            negatives = normalize_negatives(negatives, B)
-        self.score_gemm()
-        if grouped is not None:
-            self._nce_grouped(self.S, self.dS, self.dST, 1 if softplus else 0, regularization, grouped)
-        elif negatives is None:
-            _hip.call("cpc_nce_loss", _hip.ptr(self.S), _hip.ptr(self.dS), _hip.ptr(self.dST), _hip.ptr(self.nce_out),
-                      _hip.ptr(self.nce_ws), B, K, ld, 1 if softplus else 0, C.c_float(regularization), code)
+            if isinstance(temperature, DeviceTemperature):
+                temperature.dots = self._norm_dots()
+            pred, top = self._norm_operands(temperature, tick=True)
+        softplus = 1 if kind == "softplus" else 0
+        if all_timesteps and kind != "difference" and self.fused_scores_ok():
+            self._nce_all_fused(softplus, regularization, pred, top)
         else:
-            self._nce_sampled(self.S, self.dS, self.dST, 1 if softplus else 0, regularization, negatives)
-        self._score_grads(self.dS, self.dST, self.pred, top, self.dpred, dtop)
+            S, ST, dS, dST = self._loss_buffers(all_timesteps, transposed=kind == "difference")
+            self._scores(kind, all_timesteps, pred, top, S, ST)
+            self._nce_loss(S, ST, dS, dST, softplus, regularization, selection, all_timesteps)
+            if kind == "difference":
+                self._diff_coefficients(S, ST, dS, dST, all_timesteps)
+            (self._score_grads_all if all_timesteps else self._score_grads)(dS, dST, pred, top, dpred, dtop)
+        if kind == "difference":
+            self._diff_rank1(pred, top, dpred, dtop)
+        elif kind == "normalized":
+            self._norm_backward(temperature, pred, top, dpred, dtop)
 
-    def _nce_sampled(self, S, dS, dST, softplus: int, regularization: float, negatives):
-        """cpc_nce_loss_sampled in place of cpc_nce_loss (same buffers and layouts; its workspace is allocated on first use)."""
-        n_neg, seed, draw = negatives
-        if getattr(self, "nce_sampled_ws", None) is None:
-            self.nce_sampled_ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(self.B, self.K)), device=self.device,
-                                              dtype=torch.float32)
-        P = _hip.ptr
-        _hip.call("cpc_nce_loss_sampled", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_sampled_ws), self.B, self.K, self.ldS,
-                  softplus, C.c_float(regularization), n_neg, C.c_ulonglong(seed), C.c_ulonglong(draw), self.code)
+    def _scores(self, kind: str, all_timesteps: bool, pred, top, S, ST=None):
+        """The scores of a kind and a branch into S and, unless None, their transpose into ST, from operands in the layouts of
+        self.pred / the top-layer buffer: one cpc_diff_scores pass for "difference"; else the score GEMM, and for the ST of the
+        all-timesteps branch a second one with the operands swapped."""
+        if kind == "difference":
+            (self.diff_scores_all if all_timesteps else self.diff_scores)(S, ST, pred, top)
+            return
+        (self.score_gemm_all if all_timesteps else self.score_gemm)(pred, top, S)
+        if ST is not None:
+            assert all_timesteps, "the default branch's dot-product scores have no transposed GEMM"
+            code, B, E, K = self.code, self.B, self.E, self.K
+            Ltop, T, R = self.geo.alloc[-1], self.T, B * K
+            _hip.gemm_nt(_hip.ptr(top, (T - K) * E), _hip.ptr(pred), _hip.ptr(ST), R, R, E, E, E, self.ldS_all, code,
+                         a_rpi=K, a_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
 
-    def _nce_grouped(self, S, dS, dST, softplus: int, regularization: float, grouped):
-        """cpc_nce_loss_grouped in place of cpc_nce_loss (same buffers and layouts; its workspace is allocated on first use)."""
-        groups, mode, n_neg, seed, draw = grouped
-        if getattr(self, "nce_grouped_ws", None) is None:
-            self.nce_grouped_ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(self.B, self.K)), device=self.device,
-                                              dtype=torch.float32)
-        P = _hip.ptr
-        _hip.call("cpc_nce_loss_grouped", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_grouped_ws), self.B, self.K, self.ldS,
-                  softplus, C.c_float(regularization), P(groups), mode, n_neg, C.c_ulonglong(seed), C.c_ulonglong(draw), self.code)
+    def _nce_loss(self, S, ST, dS, dST, softplus: int, regularization: float, selection, all_timesteps: bool):
+        """Exactly one loss kernel on formed scores: cpc_nce_loss_all, or by ``selection`` (select_negatives) cpc_nce_loss,
+        cpc_nce_loss_sampled or cpc_nce_loss_grouped — same buffers and layouts; the workspaces of the last two are allocated on
+        first use.  Leaves the loss values in nce_out and the coefficients g = d loss / d score in dS and, transposed, dST."""
+        B, K, code, P, U = self.B, self.K, self.code, _hip.ptr, C.c_ulonglong
+        out, reg = P(self.nce_out), C.c_float(regularization)
+        if all_timesteps:
+            _hip.call("cpc_nce_loss_all", P(S), P(ST), P(dS), P(dST), out, P(self.nce_all_ws), B, K, self.ldS_all, softplus, reg, code)
+        elif selection is None:
+            _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), out, P(self.nce_ws), B, K, self.ldS, softplus, reg, code)
+        elif selection[0] == "sampled":
+            if getattr(self, "nce_sampled_ws", None) is None:
+                self.nce_sampled_ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(B, K)), device=self.device,
+                                                  dtype=torch.float32)
+            _, n_neg, seed, draw = selection
+            _hip.call("cpc_nce_loss_sampled", P(S), P(dS), P(dST), out, P(self.nce_sampled_ws), B, K, self.ldS, softplus, reg,
+                      n_neg, U(seed), U(draw), code)
+        else:
+            if getattr(self, "nce_grouped_ws", None) is None:
+                self.nce_grouped_ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(B, K)), device=self.device,
+                                                  dtype=torch.float32)
+            _, groups, mode, n_neg, seed, draw = selection
+            _hip.call("cpc_nce_loss_grouped", P(S), P(dS), P(dST), out, P(self.nce_grouped_ws), B, K, self.ldS, softplus, reg,
+                      P(groups), mode, n_neg, U(seed), U(draw), code)
 
     def _score_grads(self, W, WT, pred, top, out_pred, out_top):
         """The two contractions behind d loss / d (predicted_z, targets) of the default branch, for any coefficients W[k][b][b']
@@ -854,6 +941,24 @@ class CPCEngine:
         _hip.gemm_tn(_hip.ptr(W), _hip.ptr(pred), _hip.ptr(out_top, (T - K) * E), B, B, E, ld, K * E, Ltop * E, code,
                      a_batch=B * ld, b_batch=E, c_batch=E, batch=K)
 
+    def _score_grads_all(self, W, WT, pred, top, out_pred, out_top):
+        """The same for the all-timesteps branch: W [(b,k)][(b',k')] and its transpose.
+        d predicted_z[(b,k)][:] = sum_c dS[(b,k)][c] * targets[c][:]  and  d targets[c][:] = sum_r dS[r][c] * predicted_z[r][:]
+        (the latter into rows T-K+k' of item b' of the top-layer gradient).  As NT GEMMs over the long axis — the reduction
+        form would put a 3072-row reduction on 24 workgroups — with the small right-hand operands transposed once (3 MB each)."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T = self.geo.alloc[-1], self.T
+        R, ld = B * K, self.ldS_all
+        tg = (T - K) * E
+        if getattr(self, "targT", None) is None:
+            self.targT = torch.zeros(E, ld, device=self.device, dtype=self.dt)
+            self.predT = torch.zeros(E, ld, device=self.device, dtype=self.dt)
+        self.targT[:, :R].copy_(top.view(B, Ltop, E)[:, T - K:T, :].reshape(R, E).t())
+        self.predT[:, :R].copy_(pred.view(R, E).t())
+        _hip.gemm_nt(_hip.ptr(W), _hip.ptr(self.targT), _hip.ptr(out_pred), R, E, ld, ld, ld, E, code)
+        _hip.gemm_nt(_hip.ptr(WT), _hip.ptr(self.predT), _hip.ptr(out_top, tg), R, E, ld, ld, ld, E, code,
+                     c_rpi=K, c_item=Ltop * E, c_valid=K)
+
     # ---- score_over_all_timesteps=True with the column pass fused into the score GEMM (bf16; include/cpc_hip.h, cpc_score_lse) ----
     def fused_scores_ok(self, rows=None, cols=None):
         """The fused path needs bf16 storage, 256-row / 256-column tiles, E a multiple of 64 and an even K <= 24
@@ -866,7 +971,7 @@ class CPCEngine:
     def _nce_all_fused(self, softplus: bool, regularization: float, pred=None, top=None):
         """One persistent MFMA launch forms the (B K) x (B K) scores tile by tile and leaves the f32 scores + per-tile column
         (max, sum-exp) pairs + the diagonal; a merge, one gradient pass (dS and its transpose) and the loss scalars follow.  Replaces: the second (transposed) score GEMM, two f32 score matrices, the 16-way split column pass and the
-        two element-wise gradient passes of nce_all_forward_backward.  ``pred`` / ``top``: the score operands in the layouts of
+        two element-wise gradient passes of the unfused route.  ``pred`` / ``top``: the score operands in the layouts of
         self.pred / the top-layer buffer (None: those two)."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
@@ -894,68 +999,6 @@ class CPCEngine:
                   C.c_float(B), K, C.c_float(regularization), 1 if softplus else 0, P(self.nce_out))
         self._score_grads_all(f.dS, f.dST, pred, top, self.dpred, dtop)
 
-    def _all_buffers(self):
-        """Score, gradient and workspace buffers of the unfused all-timesteps loss (allocated on first use)."""
-        B, K = self.B, self.K
-        R = B * K
-        ld = _ceil_div(R, 8) * 8
-        if getattr(self, "ST_all", None) is None:
-            f32 = torch.float32
-            if getattr(self, "S_all", None) is None:
-                self.S_all = torch.zeros(R * ld, device=self.device, dtype=f32)
-            self.ST_all = torch.zeros(R * ld, device=self.device, dtype=f32)
-            self.dS_all = torch.zeros(R * ld, device=self.device, dtype=self.dt)
-            self.dST_all = torch.zeros(R * ld, device=self.device, dtype=self.dt)
-            self.nce_all_ws = torch.empty(int(_hip.lib().cpc_nce_all_workspace_floats(B, K)), device=self.device, dtype=f32)
-        return ld
-
-    def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, temperature=None):
-        """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
-        matrix (and its transpose, as a second tiny GEMM, so that both gradient layouts are written coalesced), the
-        log-sum-exp over ALL predictions for every (target item, step), and d loss / d (predicted_z, targets).
-        bf16 storage and tile-sized problems take the fused route (_nce_all_fused) instead; difference scores never do
-        (cpc_score_lse is a dot-product kernel): they run _diff_forward_backward.  "normalized" scores (with their ``temperature``)
-        run _norm_forward_backward, which takes either route on the normalised operands."""
-        kind = score_kind(softplus, score)
-        temperature = check_temperature(temperature, kind)
-        if kind == "difference":
-            return self._diff_forward_backward(True, regularization)
-        if kind == "normalized":
-            return self._norm_forward_backward(True, regularization, temperature)
-        if self.fused_scores_ok():
-            return self._nce_all_fused(softplus, regularization)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        top, dtop = self.act[-1], self.dact[-1]
-        R = B * K
-        ld = self._all_buffers()
-        tg = (T - K) * E
-        self.score_gemm_all()
-        _hip.gemm_nt(_hip.ptr(top, tg), _hip.ptr(self.pred), _hip.ptr(self.ST_all), R, R, E, E, E, ld, code,
-                     a_rpi=K, a_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
-        _hip.call("cpc_nce_loss_all", _hip.ptr(self.S_all), _hip.ptr(self.ST_all), _hip.ptr(self.dS_all), _hip.ptr(self.dST_all),
-                  _hip.ptr(self.nce_out), _hip.ptr(self.nce_all_ws), B, K, ld, 1 if softplus else 0, C.c_float(regularization), code)
-        # d predicted_z[(b,k)][:] = sum_c dS[(b,k)][c] * targets[c][:]  and  d targets[c][:] = sum_r dS[r][c] * predicted_z[r][:]
-        # (the latter into rows T-K+k' of item b' of the top-layer gradient).  As NT GEMMs over the long axis — the reduction
-        # form would put a 3072-row reduction on 24 workgroups — with the small right-hand operands transposed once (3 MB each).
-        self._score_grads_all(self.dS_all, self.dST_all, self.pred, top, self.dpred, dtop)
-
-    def _score_grads_all(self, W, WT, pred, top, out_pred, out_top):
-        """The same for the all-timesteps branch: W [(b,k)][(b',k')] and its transpose."""
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        R = B * K
-        ld = _ceil_div(R, 8) * 8
-        tg = (T - K) * E
-        if getattr(self, "targT", None) is None:
-            self.targT = torch.zeros(E, ld, device=self.device, dtype=self.dt)
-            self.predT = torch.zeros(E, ld, device=self.device, dtype=self.dt)
-        self.targT[:, :R].copy_(top.view(B, Ltop, E)[:, T - K:T, :].reshape(R, E).t())
-        self.predT[:, :R].copy_(pred.view(R, E).t())
-        _hip.gemm_nt(_hip.ptr(W), _hip.ptr(self.targT), _hip.ptr(out_pred), R, E, ld, ld, ld, E, code)
-        _hip.gemm_nt(_hip.ptr(WT), _hip.ptr(self.predT), _hip.ptr(out_top, tg), R, E, ld, ld, ld, E, code,
-                     c_rpi=K, c_item=Ltop * E, c_valid=K)
-
     def nce_eval(self, softplus: bool, all_timesteps: bool, sums, workspace, score: Optional[str] = None, temperature=None):
         """Adds this batch's validation quantities (per-step losses, per-step accuracies, mean score: include/cpc_hip.h,
         cpc_nce_eval) to ``sums`` (2 K + 1 floats) — from the score matrices of the train step (forward() must have run).
@@ -963,99 +1006,61 @@ class CPCEngine:
         operands cpc_norm_rows leaves for ``temperature``; both are then read as linear scores)."""
         kind = score_kind(softplus, score)
         temperature = check_temperature(temperature, kind)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        diff = kind == "difference"
-        pn, tn = self._norm_operands(temperature) if kind == "normalized" else (None, None)
-        if all_timesteps:
-            ld = _ceil_div(B * K, 8) * 8
-            if diff:
-                if getattr(self, "S_all", None) is None:
-                    self.S_all = torch.zeros(B * K * ld, device=self.device, dtype=torch.float32)
-                self.diff_scores_all(self.S_all, None)
-            else:
-                self.score_gemm_all(pn, tn)
-            S = self.S_all
-        else:
-            ld = self.ldS
-            if diff:
-                self.diff_scores(self.S, None)
-            else:
-                self.score_gemm(pn, tn)
-            S = self.S
-        _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), B, K, ld, 1 if kind == "softplus" else 0,
+        pred, top = self._norm_operands(temperature) if kind == "normalized" else (self.pred, self.act[-1])
+        S, ld = (self._all_scores(), self.ldS_all) if all_timesteps else (self.S, self.ldS)
+        self._scores(kind, all_timesteps, pred, top, S)
+        _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), self.B, self.K, ld, 1 if kind == "softplus" else 0,
                   1 if all_timesteps else 0, 1)
 
     # ---- difference scores (contrastive_estimation_training.py:25-33; include/cpc_hip.h, cpc_diff_scores) ----
-    def diff_scores(self, S, ST):
-        """Default branch: S[k][b][b'] = 1 / |predicted_z[b, k] - targets[b', :, k]|^2 (and ST[k][b'][b], unless None) from the
-        engine's own layouts.  Returns the launch's algorithmic FLOPs (one sub + one fma per feature and pair)."""
+    # The loss kernels take them as linear scores; with d = |p - t|^2 and s = 1 / d, d loss / d d = -g s^2 for g = d loss / d s, so the
+    # gradient is the linear score's two contractions with G = 2 g s^2 minus the rank-1 terms (row / column sums of G) * (p / t).
+    def diff_scores(self, S, ST, pred=None, top=None):
+        """Default branch: S[k][b][b'] = 1 / |predicted_z[b, k] - targets[b', :, k]|^2 (and ST[k][b'][b], unless None) from operands
+        in the engine's own layouts (None: self.pred / the top layer).  Returns the launch's algorithmic FLOPs (one sub + one fma per
+        feature and pair)."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
+        pred = self.pred if pred is None else pred
+        top = self.act[-1] if top is None else top
         work = 2.0 * K * B * B * E
-        _hip.call("cpc_diff_scores", _hip.ptr(self.pred), _hip.ptr(self.act[-1], (T - K) * E), _hip.ptr(S), _hip.ptr(ST), B, B, E,
+        _hip.call("cpc_diff_scores", _hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(S), _hip.ptr(ST), B, B, E,
                   C.c_longlong(K * E), C.c_longlong(Ltop * E), 0, C.c_longlong(0), C.c_longlong(E), C.c_longlong(E),
                   C.c_longlong(B * ld), K, ld, code, work=work)
         return work
 
-    def diff_scores_all(self, S, ST):
+    def diff_scores_all(self, S, ST, pred=None, top=None):
         """score_over_all_timesteps=True: the (B K) x (B K) difference scores S (and ST, unless None) from one pass."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T = self.geo.alloc[-1], self.T
+        pred = self.pred if pred is None else pred
+        top = self.act[-1] if top is None else top
         R = B * K
-        ld = _ceil_div(R, 8) * 8
         work = 2.0 * R * R * E
-        _hip.call("cpc_diff_scores", _hip.ptr(self.pred), _hip.ptr(self.act[-1], (T - K) * E), _hip.ptr(S), _hip.ptr(ST), R, R, E,
-                  C.c_longlong(E), C.c_longlong(E), K, C.c_longlong(Ltop * E), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), 1, ld,
-                  code, work=work)
+        _hip.call("cpc_diff_scores", _hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(S), _hip.ptr(ST), R, R, E,
+                  C.c_longlong(E), C.c_longlong(E), K, C.c_longlong(Ltop * E), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), 1,
+                  self.ldS_all, code, work=work)
         return work
 
-    def _diff_forward_backward(self, all_timesteps: bool, regularization: float, negatives=None, negative_groups=None):
-        """InfoNCE loss + regulariser on difference scores and d loss / d (predicted_z, targets).  The loss kernels take the scores
-        as linear scores (softplus = 0, as contrastive_estimation_training._InfoNCE does); with d = |p - t|^2 and s = 1 / d,
-        d loss / d d = -g s^2 for g = d loss / d s, so the gradient is the linear score's two contractions with G = 2 g s^2
-        minus the rank-1 terms (row / column sums of G) * (p / t): cpc_diff_scores_bwd, _score_grads(_all), cpc_diff_scores_rank1.
-        In bf16 storage G is rounded to bf16 (the operand type of the contractions) and its sums are taken of the rounded values."""
-        grouped = None
-        if negative_groups is not None:
-            check_negatives_supported(negatives, all_timesteps, negative_groups=negative_groups)
-            grouped = normalize_negative_groups(negative_groups, self.B, negatives)
-        elif negatives is not None:
-            check_negatives_supported(negatives, all_timesteps)
-            negatives = normalize_negatives(negatives, self.B)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        top, dtop = self.act[-1], self.dact[-1]
+    def _diff_coefficients(self, S, ST, dS, dST, all_timesteps: bool):
+        """cpc_diff_scores_bwd: G = 2 g s^2 in place of g in dS / dST, and its row / column sums in _diff_mu (allocated on first use;
+        indexed like predicted_z's and the targets' (b, k) rows in both branches).  In bf16 storage G is rounded to bf16 (the operand
+        type of the contractions) and its sums are taken of the rounded values."""
+        B, K, P = self.B, self.K, _hip.ptr
         R = B * K
         if getattr(self, "_diff_mu", None) is None:
             self._diff_mu = torch.empty(2, R, device=self.device, dtype=torch.float32)
         mu, nu = self._diff_mu[0], self._diff_mu[1]
-        P = _hip.ptr
-        if all_timesteps:
-            ld = self._all_buffers()
-            S, ST, dS, dST = self.S_all, self.ST_all, self.dS_all, self.dST_all
-            self.diff_scores_all(S, ST)
-            _hip.call("cpc_nce_loss_all", P(S), P(ST), P(dS), P(dST), P(self.nce_out), P(self.nce_all_ws), B, K, ld, 0,
-                      C.c_float(regularization), code)
-            _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), R, R, ld, C.c_longlong(0), 1, code)
-            self._score_grads_all(dS, dST, self.pred, top, self.dpred, dtop)
-        else:
-            ld = self.ldS
-            if getattr(self, "ST", None) is None:
-                self.ST = torch.zeros_like(self.S)
-            S, ST, dS, dST = self.S, self.ST, self.dS, self.dST
-            self.diff_scores(S, ST)
-            if grouped is not None:
-                self._nce_grouped(S, dS, dST, 0, regularization, grouped)
-            elif negatives is None:
-                _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), P(self.nce_out), P(self.nce_ws), B, K, ld, 0, C.c_float(regularization), code)
-            else:
-                self._nce_sampled(S, dS, dST, 0, regularization, negatives)
-            _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), B, B, ld, C.c_longlong(B * ld), K, code)
-            self._score_grads(dS, dST, self.pred, top, self.dpred, dtop)
-        # mu / nu are indexed like predicted_z's and the targets' (b, k) rows in both branches
-        _hip.call("cpc_diff_scores_rank1", P(mu), P(self.pred), P(self.dpred), R, E, 0, C.c_longlong(0), C.c_longlong(E), code)
-        tg = (T - K) * E
-        _hip.call("cpc_diff_scores_rank1", P(nu), P(top, tg), P(dtop, tg), R, E, K, C.c_longlong(Ltop * E), C.c_longlong(E), code)
+        n, ld, stride, batch = (R, self.ldS_all, 0, 1) if all_timesteps else (B, self.ldS, B * self.ldS, K)
+        _hip.call("cpc_diff_scores_bwd", P(dS), P(S), P(mu), P(dST), P(ST), P(nu), n, n, ld, C.c_longlong(stride), batch, self.code)
+
+    def _diff_rank1(self, pred, top, dpred, dtop):
+        """cpc_diff_scores_rank1: dpred -= mu * predicted_z and the K target rows of dtop -= nu * targets (_diff_coefficients' sums)."""
+        code, E, K, P, L = self.code, self.E, self.K, _hip.ptr, C.c_longlong
+        Ltop, R, tg = self.geo.alloc[-1], self.B * K, (self.T - K) * E
+        mu, nu = self._diff_mu[0], self._diff_mu[1]
+        _hip.call("cpc_diff_scores_rank1", P(mu), P(pred), P(dpred), R, E, 0, L(0), L(E), code)
+        _hip.call("cpc_diff_scores_rank1", P(nu), P(top, tg), P(dtop, tg), R, E, K, L(Ltop * E), L(E), code)
 
     # ---- cosine similarity / temperature ("normalized"; include/cpc_hip.h, cpc_norm_rows) ----
     def _norm_scratch(self):
@@ -1101,60 +1106,20 @@ class CPCEngine:
                   C.c_float(NORM_EPS), code, work=nbytes)
         return n.pn, n.tn
 
-    def _norm_forward_backward(self, all_timesteps: bool, regularization: float, temperature, negatives=None,
-                               negative_groups=None):
-        """InfoNCE loss + regulariser on cosine-similarity scores over a temperature and d loss / d (predicted_z, targets): the rows
-        are normalised (cpc_norm_rows; predictions also divided by the temperature), the linear score's own chain — score GEMM, loss
-        kernels with softplus = 0 (dense, sampled or grouped; the fused all-timesteps route where fused_scores_ok() holds) and the two
-        contractions — runs on the normalised operands, and cpc_norm_rows_bwd turns the gradients with respect to the normalised rows
-        into those with respect to the rows, in place in dpred and in rows [T-K, T) of the top-layer gradient.  All on the current
-        stream: the target-row lane of backward() starts from those rows behind the event it records there.
-        ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward).  A DeviceTemperature takes
-        the _dev kernels for the prediction rows: the scale comes from its tstate (set first in scheduled mode), and the backward leaves
-        dots[row] = <pn[row], d loss / d pn[row]> in the scratch, whose sum is d loss / d log(1 / tau) for every loss chain above —
-        FusedAdam(temperature=...) adds them up (cpc_temperature_step)."""
-        grouped = None
-        if negative_groups is not None:
-            check_negatives_supported(negatives, all_timesteps, negative_groups=negative_groups)
-            grouped = normalize_negative_groups(negative_groups, self.B, negatives)
-        elif negatives is not None:
-            check_negatives_supported(negatives, all_timesteps)
-            negatives = normalize_negatives(negatives, self.B)
-        code, B, E, K = self.code, self.B, self.E, self.K
-        Ltop, T = self.geo.alloc[-1], self.T
-        dtop = self.dact[-1]
-        R = B * K
-        P, L, tg = _hip.ptr, C.c_longlong, (T - K) * E
-        on_device = isinstance(temperature, DeviceTemperature)
-        if on_device:
-            temperature.dots = self._norm_dots()
-        pn, tn = self._norm_operands(temperature, tick=True)
-        if all_timesteps and self.fused_scores_ok():
-            self._nce_all_fused(False, regularization, pn, tn)
-        elif all_timesteps:
-            ld = self._all_buffers()
-            self.score_gemm_all(pn, tn)
-            _hip.gemm_nt(P(tn, tg), P(pn), P(self.ST_all), R, R, E, E, E, ld, code, a_rpi=K, a_item=Ltop * E, flags=_hip.GEMM_OUT_F32)
-            _hip.call("cpc_nce_loss_all", P(self.S_all), P(self.ST_all), P(self.dS_all), P(self.dST_all), P(self.nce_out),
-                      P(self.nce_all_ws), B, K, ld, 0, C.c_float(regularization), code)
-            self._score_grads_all(self.dS_all, self.dST_all, pn, tn, self.dpred, dtop)
-        else:
-            self.score_gemm(pn, tn)
-            if grouped is not None:
-                self._nce_grouped(self.S, self.dS, self.dST, 0, regularization, grouped)
-            elif negatives is None:
-                _hip.call("cpc_nce_loss", P(self.S), P(self.dS), P(self.dST), P(self.nce_out), P(self.nce_ws), B, K, self.ldS, 0,
-                          C.c_float(regularization), code)
-            else:
-                self._nce_sampled(self.S, self.dS, self.dST, 0, regularization, negatives)
-            self._score_grads(self.dS, self.dST, pn, tn, self.dpred, dtop)
-        n = self._norm
+    def _norm_backward(self, temperature, pn, tn, dpred, dtop):
+        """cpc_norm_rows_bwd turns the gradients with respect to the normalised rows (_norm_operands' pn / tn) into those with respect
+        to the rows, in place in dpred and in rows [T-K, T) of dtop.  A DeviceTemperature takes the _dev kernel for the prediction rows:
+        the scale comes from its tstate, and dots[row] = <pn[row], d loss / d pn[row]> is left in the scratch, whose sum is
+        d loss / d log(1 / tau) for every loss kernel of the chain — FusedAdam(temperature=...) adds them up (cpc_temperature_step)."""
+        code, E, K = self.code, self.E, self.K
+        Ltop, R, n = self.geo.alloc[-1], self.B * K, self._norm
+        P, L, tg = _hip.ptr, C.c_longlong, (self.T - K) * E
         nbytes = 3.0 * R * E * self.pred.element_size()
-        if on_device:
-            _hip.call("cpc_norm_rows_bwd_dev", P(pn), P(n.inv_p), P(self.dpred), P(n.dots), R, E, 0, L(0), L(E), temperature.scale_ptr(),
+        if isinstance(temperature, DeviceTemperature):
+            _hip.call("cpc_norm_rows_bwd_dev", P(pn), P(n.inv_p), P(dpred), P(n.dots), R, E, 0, L(0), L(E), temperature.scale_ptr(),
                       C.c_float(NORM_EPS), code, work=nbytes)
         else:
-            _hip.call("cpc_norm_rows_bwd", P(pn), P(n.inv_p), P(self.dpred), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
+            _hip.call("cpc_norm_rows_bwd", P(pn), P(n.inv_p), P(dpred), R, E, 0, L(0), L(E), C.c_float(1.0 / temperature),
                       C.c_float(NORM_EPS), code, work=nbytes)
         _hip.call("cpc_norm_rows_bwd", P(tn, tg), P(n.inv_t), P(dtop, tg), R, E, K, L(Ltop * E), L(E), C.c_float(1.0),
                   C.c_float(NORM_EPS), code, work=nbytes)
@@ -1426,12 +1391,7 @@ class CPCEngine:
         ``negative_groups``: None, or (groups, mode): candidates by group id (nce_forward_backward); default branch only."""
         kind = score_kind(softplus, score)
         temperature = check_temperature(temperature, kind)
-        if negative_groups is not None:
-            check_negatives_supported(negatives, all_timesteps, global_negatives, negative_groups=negative_groups)
-            normalize_negative_groups(negative_groups, self.B, negatives)
-        elif negatives is not None:
-            check_negatives_supported(negatives, all_timesteps, global_negatives)
-            negatives = normalize_negatives(negatives, self.B)
+        select_negatives(self.B, negatives, negative_groups, all_timesteps, global_negatives)          # refused before forward() runs
         if kind == "difference" and global_negatives is not None:
             raise NotImplementedError("difference scores under global negatives are not on the HIP path: the trainer takes the generic "
                                       "route there (contrastive_estimation_training.difference_score_function)")
@@ -2405,8 +2365,8 @@ class GlobalNegatives:
         self.ws = torch.empty(int(_hip.lib().cpc_nce_workspace_floats(GB, K)), device=dev, dtype=f32)
 
     def _all_timesteps(self, softplus: bool, regularization: float):
-        """The full (GB K) x (GB K) score matrix over the gathered predictions / targets (engine.nce_all_forward_backward on
-        the global batch)."""
+        """The full (GB K) x (GB K) score matrix over the gathered predictions / targets: the unfused all-timesteps
+        stages of CPCEngine._loss_chain (scores, cpc_nce_loss_all, the two contractions) restated on the global batch."""
         e = self.eng
         code, E, K, GB = e.code, e.E, e.K, self.GB
         R = GB * K

@@ -294,8 +294,9 @@ def test_engine_refusals_need_no_device():
         CPCEngine.loss_and_grads(stub, None, True, 1.0, negative_groups=ng, negatives=(8, 0, 0))
     with pytest.raises(NotImplementedError):
         ScalogramCPCEngine.loss_and_grads(stub, None, True, 1.0, gradient_penalty=10.0, negative_groups=ng)
-    with pytest.raises(NotImplementedError):
-        CPCEngine._diff_forward_backward(stub, True, 1.0, None, ng)
+    for kind, temperature in (("difference", None), ("linear", None), ("normalized", 0.1)):      # one selection check for every kind
+        with pytest.raises(NotImplementedError):
+            CPCEngine._loss_chain(stub, kind, True, 1.0, temperature, None, ng)
     with pytest.raises(NotImplementedError, match="graph"):
         GraphedStep(None, None, True, 1.0, negative_groups=ng)
 

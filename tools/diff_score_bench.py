@@ -64,7 +64,7 @@ def kernel_times(args, device):
     eng.nce_forward_backward(False, 1.0, score="difference")
     eng.nce_all_forward_backward(False, 1.0, score="difference")
     torch.cuda.synchronize()
-    ld, ld_all = eng.ldS, eng._all_buffers()
+    ld, ld_all = eng.ldS, eng.ldS_all
     G, GT = eng.dS.clone(), eng.dST.clone()
     Ga, GTa = eng.dS_all.clone(), eng.dST_all.clone()
     sums = torch.empty(2, R, device=device)

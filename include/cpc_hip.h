@@ -295,13 +295,16 @@ int cpc_attn128_fwd(const void* qkv, void* out, void* P, int B, int S, int C, in
 int cpc_attn128_bwd(const void* qkv, const void* P, const void* dout, void* dqkv, int B, int S, int C, int heads, float drop_p,
                     unsigned long long seed, unsigned site, int dtype, void* stream);
 /* r = a + dropout(b) (b may be NULL; r_out may be NULL), y = LayerNorm(r) * w + bias (transformer.py:262-271, eps inside
- * the sqrt); stats f32 [M][2] = (mean, rstd) saved for the backward; dropout element index = m*C + c. */
+ * the sqrt); stats f32 [M][2] = (mean, rstd) saved for the backward; dropout element index = m*C + c.
+ * Any C % 4 == 0 (rows of C <= 1024 stay in registers, wider rows are read three times) — wider than cpc_ln_bwd below, which stops at
+ * C = 1024: a forward at C > 1024 has no backward here. */
 int cpc_add_ln_fwd(const void* a, const void* b, const float* w, const float* bias, void* r_out, void* y, float* stats, int M,
                    int C, float eps, float drop_p, unsigned long long seed, unsigned site, int dtype, void* stream);
 /* LayerNorm backward: dy = g1 * gscale (+ g2); with bcast > 0 row m reads g1 row m / bcast (the mean over time of
  * attention_model.py:79 folded in, gscale = 1/S).  dr = gradient of r; dr_b (may be NULL) = dr * dropout factor = gradient of
  * the summand b; slabs f32 [nblocks][2][C] hold per-block partial sums of (dw, dbias), to be summed by cpc_reduce_slabs.
- * C*32 bytes of LDS must fit 64 KB. */
+ * C % 4 == 0 and C <= 1024 (a lane keeps at most four column groups; C*32 bytes of LDS): -EINVAL above, with nothing written, although
+ * cpc_add_ln_fwd accepts such rows.  Blocks beyond ceil(M/4) write zero slabs. */
 int cpc_ln_bwd(const void* g1, const void* g2, const void* r, const float* stats, const float* w, void* dr, float* slabs, int M,
                int C, int bcast, float gscale, int nblocks, void* dr_b, float drop_p, unsigned long long seed, unsigned site,
                int dtype, void* stream);

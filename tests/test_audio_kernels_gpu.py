@@ -522,6 +522,14 @@ def _gru_ref(Gi, w, b, h0, V, H):
     return h, torch.stack(hs, 1)
 
 
+def per_step_err(got, ref):
+    """(B, V, X) -> max over the steps t of max_{b,j} |got - ref| / max_{b,j} |ref| within step t: the gradient of a recurrence decays
+    backwards through time, so a maximum over the whole tensor hides the early steps."""
+    got = torch.as_tensor(got).detach().double().cpu()
+    ref = torch.as_tensor(ref).detach().double().cpu()
+    return ((got - ref).abs().amax((0, 2)) / (ref.abs().amax((0, 2)) + 1e-30)).max().item()
+
+
 def _gru_case(dt, B, V, H, streaming, with_bwd):
     g = torch.Generator().manual_seed(B * 7 + H + streaming)
     code = _hip.dtype_code(dt)
@@ -566,7 +574,7 @@ def _gru_case(dt, B, V, H, streaming, with_bwd):
     dcd = dc.to(DEV)
     _hip.call("cpc_gru_bwd", _hip.ptr(dcd), _hip.ptr(tf), _hip.ptr(wTfrag), _hip.ptr(dG), B, V, H, code)
     t_b = 5e-5 if dt == torch.float32 else 4e-2
-    assert rel_err(dG[:, :, :3 * H], gir0.grad) < t_b
+    assert per_step_err(dG[:, :, :3 * H], gir0.grad) < t_b
     dGh = torch.cat([dG[:, :, :2 * H], dG[:, :, 3 * H:]], dim=2)
     dWhh = torch.einsum("bvg,bvh->gh", dGh.double().cpu(), Hf[:, :V].double().cpu())
     assert rel_err(dWhh, wr0.grad) < t_b

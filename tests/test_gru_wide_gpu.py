@@ -32,6 +32,14 @@ def rel_err(got, ref):
     return ((got - ref).abs().max() / (ref.abs().max() + 1e-30)).item()
 
 
+def per_step_err(got, ref):
+    """(B, V, X) -> max over the steps t of max_{b,j} |got - ref| / max_{b,j} |ref| within step t: the gradient of a recurrence decays
+    backwards through time, so a maximum over the whole tensor hides the early steps."""
+    got = torch.as_tensor(got).detach().double().cpu()
+    ref = torch.as_tensor(ref).detach().double().cpu()
+    return ((got - ref).abs().amax((0, 2)) / (ref.abs().amax((0, 2)) + 1e-30)).max().item()
+
+
 def _rel(got, ref):
     got = torch.as_tensor(got).detach().double().cpu()
     ref = torch.as_tensor(ref).detach().double().cpu()
@@ -107,7 +115,7 @@ def test_wide_gru_fwd_bwd(dt, H, B, V):
     assert guard_intact(gb, B * V * 4 * H)
     dG = dG.view(B, V, 4 * H)
     t_b = 5e-5 if dt == torch.float32 else 4e-2
-    assert rel_err(dG[:, :, :3 * H], gig.grad) < t_b
+    assert per_step_err(dG[:, :, :3 * H], gig.grad) < t_b
     dGh = torch.cat([dG[:, :, :2 * H], dG[:, :, 3 * H:]], dim=2).double().cpu()
     assert rel_err(dGh.sum((0, 1)), bg.grad) < t_b
     dWhh = torch.einsum("bvg,bvh->gh", dGh, Hall.view(B, V + 1, H)[:, :V].double().cpu())

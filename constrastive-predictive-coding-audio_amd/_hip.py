@@ -13,6 +13,8 @@ import torch
 F32, BF16 = 0, 1
 GEMM_RELU, GEMM_OUT_F32, GEMM_TN_NO_TR, GEMM_FORCE_GENERIC, GEMM_SMALL_TILE, GEMM_NARROW_EPI, GEMM_NO_DMA, GEMM_SKIP_PAD_ROWS = 1, 2, 4, 8, 16, 32, 64, 128
 GEMM_BIG_TILE = 0x100000          # CPC_GEMM_BIG_TILE: the 256 x 256 tile also where fewer than 200 of them exist
+GEMM_GENERIC_EPI = 0x200000       # CPC_GEMM_GENERIC_EPI: the generic epilogue body for launches that have a compile-time form (A/B check)
+GEMM_QUERY_EPI = 0x800000         # CPC_GEMM_QUERY_EPI: no launch; the call returns 100 + the epilogue form its launch would run
 GEMM_LINEAR_K, GEMM_NO_PERS, GEMM_DIRECT_MASK, GEMM_KRANGE_EXACT = 256, 512, 1024, 2048
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -76,6 +78,8 @@ _P, _I, _L, _F, _D, _U64, _U32 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C
 _SIGNATURES = {
     "cpc_abi_version": ([], _I),
     "cpc_gemm_nt": ([C.POINTER(GemmNTArgs), _P], _I),
+    "cpc_gemm_nt_bits": ([C.POINTER(GemmNTArgs), _P, _P, _P], _I),
+    "cpc_gemm_nt_debug_flags": ([_I], _I),
     "cpc_gemm_tn": ([C.POINTER(GemmTNArgs), _P], _I),
     "cpc_reduce_slabs": ([_P, _P, _I, _I, _I, _L, _I, _L, _L, _L, _P], _I),
     "cpc_colsum": ([_P, _P, _I, _I, _L, _I, _I, _P], _I),

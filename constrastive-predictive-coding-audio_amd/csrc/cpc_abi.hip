@@ -11,6 +11,7 @@ static_assert(CPC_GEMM_FORCE_GENERIC == GEMM_FORCE_GENERIC && CPC_GEMM_SMALL_TIL
 static_assert(CPC_GEMM_SKIP_PAD_ROWS == GEMM_SKIP_PAD_ROWS && CPC_GEMM_NO_DMA == GEMM_NO_DMA, "flag mismatch");
 static_assert(CPC_GEMM_RELU == GEMM_RELU && CPC_GEMM_OUT_F32 == GEMM_OUT_F32 && CPC_GEMM_TN_NO_TR == GEMM_TN_NO_TR, "flag mismatch");
 static_assert(CPC_GEMM_LINEAR_K == GEMM_LINEAR_K && CPC_GEMM_NO_PERS == GEMM_NO_PERS && CPC_GEMM_DIRECT_MASK == GEMM_DIRECT_MASK, "flag mismatch");
+static_assert(CPC_GEMM_BIG_TILE == GEMM_BIG_TILE && CPC_GEMM_GENERIC_EPI == GEMM_GENERIC_EPI && CPC_GEMM_QUERY_EPI == GEMM_QUERY_EPI, "flag mismatch");
 static_assert(CPC_F32 == CPC_DTYPE_F32 && CPC_BF16 == CPC_DTYPE_BF16, "dtype mismatch");
 
 static inline int esize(int dtype) { return dtype == CPC_DTYPE_BF16 ? 2 : 4; }
@@ -19,10 +20,11 @@ extern "C" {
 
 int cpc_abi_version(void) { return 9; }
 
-int cpc_gemm_nt(const cpc_gemm_nt_args* a, void* stream) {
+static int gemm_nt_from_args(const cpc_gemm_nt_args* a, const void* mask_bits, float* colsum_slabs, void* stream) {
     if (!a || !a->A || !a->Bt || !a->C) return CPC_EINVAL;
     GemmNT p = {};
     p.A = a->A; p.Bt = a->Bt; p.C = a->C; p.bias = a->bias; p.mask = a->mask;
+    p.mask_bits = (const unsigned char*)mask_bits; p.colsum_slabs = colsum_slabs;
     p.M = a->M; p.N = a->N; p.K = a->K;
     p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc;
     p.a_rpi = a->a_rpi; p.a_item = a->a_item;
@@ -51,6 +53,15 @@ int cpc_gemm_nt(const cpc_gemm_nt_args* a, void* stream) {
     }
     return launch_gemm_nt(p, a->dtype, nb, (hipStream_t)stream);
 }
+
+int cpc_gemm_nt(const cpc_gemm_nt_args* a, void* stream) { return gemm_nt_from_args(a, nullptr, nullptr, stream); }
+
+int cpc_gemm_nt_bits(const cpc_gemm_nt_args* a, const void* mask_bits, float* colsum_slabs, void* stream) {
+    if (!mask_bits && !(a && a->mask)) return CPC_EINVAL;
+    return gemm_nt_from_args(a, mask_bits, colsum_slabs, stream);
+}
+
+int cpc_gemm_nt_debug_flags(int flags) { return gemm_nt_debug_flags(flags); }
 
 int cpc_gemm_tn(const cpc_gemm_tn_args* a, void* stream) {
     if (!a || !a->A || !a->B || !a->C) return CPC_EINVAL;

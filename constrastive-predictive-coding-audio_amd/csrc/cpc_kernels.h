@@ -19,6 +19,9 @@
 #define GEMM_LINEAR_K 256       // NT fast path: visit K in storage order even for overlapped-row operands (A-B check, see GemmNT::k_taps)
 #define GEMM_BIG_TILE 0x100000  // internal: the 256x256 tile also where fewer than 200 of them exist (a row-range launch that needs the per-tile column sums)
 #define GEMM_WT_SYSTEM 0x80000  // internal: set by the launcher: output stores of the NT fast kernels write through at system scope (sc0 sc1)
+#define GEMM_GENERIC_EPI 0x200000 // internal, NT 256x256 bf16: the generic epilogue body also where a launch matches a compile-time epilogue form (A-B
+                                  // check and the bit-identity tests; see EPI_DGRAD in gemm.hip).  gemm_nt_debug_flags sets it for every launch.
+#define GEMM_QUERY_EPI 0x800000   // internal: launch nothing; a launch that passes every check returns 100 + the epilogue form it would run (EPI_* in gemm.hip)
 #define GEMM_FORCE_GENERIC 8   // use the register-staged generic kernel even when the LDS-DMA fast path applies (A-B check)
 
 struct GemmNT {
@@ -104,6 +107,9 @@ struct GemmTN {
 };
 
 int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream);
+// Tests and A/B timing only (one relaxed atomic load per launch otherwise).  Flags OR-ed into every launch_gemm_nt call of the process from now on (GEMM_GENERIC_EPI and GEMM_QUERY_EPI; anything else is refused); returns the
+// previous value, or -1.  For A-B timing and tests of launches that reach the launcher through the domain-level entry points.
+int gemm_nt_debug_flags(int flags);
 int launch_score_lse(const void* P, const void* Tg, void* Sb, float* pm, float* ps, float* valid, int M, int N, int E, long long ldp,
                      long long ldt, long long lds_, int diag_off, hipStream_t stream);
 int launch_gemm_tn(const GemmTN& p, int dtype, int nsplit, int batch, hipStream_t stream);

@@ -14,6 +14,7 @@
 // Storage type T is bf16 (v_mfma_f32_16x16x32_bf16) or f32 (v_mfma_f32_16x16x4_f32, exact-f32 parity mode);
 // accumulation is always f32.  128x128 output tile per 256-thread workgroup (4 waves, 64x64 each).
 #include <algorithm>
+#include <atomic>
 #include "cpc_common.h"
 #include "cpc_kernels.h"
 #include <cstdlib>
@@ -355,13 +356,79 @@ __device__ __forceinline__ int direct_b_col(int r) {
 __device__ __forceinline__ void store_out16(uint4* dst, uint4 v, int flags) {
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const v4u d = {v.x, v.y, v.z, v.w};
-    if (flags & GEMM_WT_SYSTEM) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(d) : "memory");
+    // (s_nop: a store of more than 8 bytes must not be followed at once by a VALU write of its data registers, and the compiler's hazard
+    // check does not see into the asm — it may reuse the dead data registers in the very next instruction.)
+    if (flags & GEMM_WT_SYSTEM) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(d) : "memory");
     else *dst = v;
 }
 
-template <typename T, typename TO, int WM, int WN, int TI, int TJ, bool DMA, bool C1 = false, bool DIRECT = false>
+// GemmNT::colsum_slabs: the tile's 256 column sums — 16 row groups per column chunk through LDS, fixed order — to slabs[mt][n]: the bias
+// gradient of the layer below without another pass over this kernel's 0.06-0.24 GB output.  cs: the thread's sums over its rows of the
+// 8 columns of its chunk (thread tid holds chunk tid % (TBN / 8) of row group tid / (TBN / 8)).
+template <int TBN, int NTHR>
+__device__ __forceinline__ void nt_colsum_reduce(float* red, const float (&cs)[8], int tid, int mt, int n0, const GemmNT& p) {
+    constexpr int CPR = TBN / 8, RPP = NTHR / CPR;
+    *(f32x4*)(red + tid * 8) = (f32x4){cs[0], cs[1], cs[2], cs[3]};
+    *(f32x4*)(red + tid * 8 + 4) = (f32x4){cs[4], cs[5], cs[6], cs[7]};
+    __syncthreads();
+    if (tid < TBN && n0 + tid < p.N) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < RPP; ++g) t += red[(g * CPR + (tid >> 3)) * 8 + (tid & 7)];
+        p.colsum_slabs[(long long)mt * p.N + n0 + tid] = t;
+    }
+}
+
+// Fused layer-1 weight gradient, from the masked tile image at lds and the window image behind it (the caller's barrier stands between
+// their last writes and this): slab[j][c] = sum over the tile's rows of xw[row][j] * G[row][c], a (16 x TBM) x (TBM x TBN) product on the
+// matrix pipe with both operands read transposed from their LDS images (the TN kernel's fragment reads); wave w owns the column
+// blocks 2w and 2w+1, so no sums cross waves.  x = hi + lo keeps ~16 mantissa bits.
+template <int TBM, int TBN, int EPI_RS>
+__device__ __forceinline__ void nt_conv1_slabs(const unsigned char* lds, int lane, int wave, int mt, int nt, int numN, const GemmNT& p) {
+    const unsigned char* xw = lds + TBM * EPI_RS;
+    f32x4 d0 = (f32x4){0.f, 0.f, 0.f, 0.f}, d1 = d0;
+#pragma unroll
+    for (int ks = 0; ks < TBM / 32; ++ks) {
+        const uint4 fh = tn_frag_rb(xw, 32, 0, ks, lane);
+        const uint4 fl = tn_frag_rb(xw + TBM * 32, 32, 0, ks, lane);
+        const uint4 g0 = tn_frag_rb(lds, EPI_RS, (wave * 2) * 16, ks, lane);
+        const uint4 g1 = tn_frag_rb(lds, EPI_RS, (wave * 2 + 1) * 16, ks, lane);
+        mfma_chunk<bf16_t>(d0, g0, fh);
+        mfma_chunk<bf16_t>(d0, g0, fl);
+        mfma_chunk<bf16_t>(d1, g1, fh);
+        mfma_chunk<bf16_t>(d1, g1, fl);
+    }
+    const int slot = lane & 15, c4 = (lane >> 4) * 4;
+    if (slot <= p.c1_kw) {
+        float* sl = p.c1_slabs + ((long long)mt * numN + nt) * (p.c1_kw + 1) * TBN + (long long)slot * TBN;
+        // (written through like the tile stores: 82 MB of slabs per launch, read by the reduction right behind this kernel)
+        store_out16((uint4*)(sl + (wave * 2) * 16 + c4), __builtin_bit_cast(uint4, d0), p.flags);
+        store_out16((uint4*)(sl + (wave * 2 + 1) * 16 + c4), __builtin_bit_cast(uint4, d1), p.flags);
+    }
+}
+
+// Compile-time epilogue forms of the 256x256 bf16 LDS-DMA kernel (template parameter EPI).  The generic body serves every runtime
+// combination of bias, ReLU, the two masks, pad-row policy, store kind, column sums and the fused layer-1 gradient, and finds every row's
+// address by division; the launch kinds that close the train step get bodies of their own that hold none of those choices:
+//   EPI_DGRAD     the masked data gradient as cpc_conv_dgrad / cpc_conv_dgrad_rows launch it: sign-bit mask in LDS, applied while the
+//                 accumulators go to the tile image; no bias, no ReLU; bf16 rows written through; pad rows zeroed or skipped; column sums
+//                 present or not (one uniform branch around the store passes);
+//   EPI_DGRAD_C1  the same tile kept in LDS and contracted with the waveform windows (GEMM_EPI_CONV1);
+//   EPI_DGRAD_MASK  EPI_DGRAD with the full-size mask (the activation itself) where no sign bits exist — layers 5 - 3 of the train step:
+//                 a thread's 16 mask chunks are requested before the accumulators go to the tile image and applied in the store passes.
+// All three find (item, position in item) of a thread's first row by ONE division and step from row to row by compare-and-wrap, and the
+// two that store (EPI_DGRAD, EPI_DGRAD_MASK) issue the LDS reads of all 16 store passes before the first store.  Every sum is taken in the
+// generic body's order: the results are bit-identical.  launch_gemm_nt picks a form only where a launch matches it exactly.
+// (Requesting K stage 1 before the first barrier — both stage buffers are free then — with a counted vmcnt and a raw barrier was measured
+// too: fixed cost per tile 7.23 against 6.97 us masked, 4.22 against 4.34 us fused, no difference beyond the spread; not kept.)
+constexpr int EPI_GENERIC = 0, EPI_DGRAD = 1, EPI_DGRAD_C1 = 2, EPI_DGRAD_MASK = 3;
+
+template <typename T, typename TO, int WM, int WN, int TI, int TJ, bool DMA, bool C1 = false, bool DIRECT = false, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
     static_assert(!DIRECT || (DMA && !C1 && sizeof(T) == 2 && sizeof(TO) == 2 && TJ == 4), "direct epilogue: bf16 LDS-DMA variants");
+    static_assert(EPI == EPI_GENERIC || (DMA && !DIRECT && sizeof(T) == 2 && sizeof(TO) == 2 && WM == 2 && WN == 4 && TI == 8 && TJ == 4 &&
+                                         C1 == (EPI == EPI_DGRAD_C1) && EPI <= EPI_DGRAD_MASK),
+                  "compile-time epilogue forms: the 256x256 bf16 LDS-DMA kernel");
     constexpr int CH = Elem<T>::CH;
     constexpr int BK = 8 * CH;
     constexpr int TBM = WM * TI * 16, TBN = WN * TJ * 16, NTHR = 64 * WM * WN;
@@ -529,10 +596,37 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
         // 8j + (lane>>3), LDS chunk lane&7, SOURCE chunk (lane&7) ^ (row&7) = (lane&7) ^ (lane>>3)  (swizzle on the source)
         const int srow = lane >> 3, sch = (lane & 7) ^ (lane >> 3);
         const int r0 = (wave_u * 4) * 8 + srow;
-        const T* ga0 = Ab + row_off2(min(m0 + r0, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
-        const T* ga1 = Ab + row_off2(min(m0 + r0 + 8, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
-        const T* ga2 = Ab + row_off2(min(m0 + r0 + 16, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
-        const T* ga3 = Ab + row_off2(min(m0 + r0 + 24, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
+        const T *ga0, *ga1, *ga2, *ga3;
+        [[maybe_unused]] long long cro0 = 0, cro1 = 0, cro2 = 0, cro3 = 0;   // EPI forms: C element offsets of the same four rows (mask bits)
+        if constexpr (EPI != EPI_GENERIC) {
+            // One division per thread: (item, position in item) of its first row; the rows 8, 16 and 24 further on follow by compare-and-wrap
+            // (a_rpi == c_rpi, 0 or >= 32, one row level: the launcher's conditions for these forms).  A row beyond M keeps the last row
+            // below M that the thread met (the generic body clamps to row M - 1): it feeds only outputs that are never stored.
+            const int mb = m0 + r0, mc = min(mb, p.M - 1);
+            const unsigned rpi = p.a_rpi ? (unsigned)p.a_rpi : 0xffffffffu;
+            const long long awrap = p.a_item - (long long)p.a_rpi * p.lda, cwrap = p.c_item - (long long)p.a_rpi * p.ldc;
+            const int q = p.a_rpi ? mc / p.a_rpi : 0;
+            unsigned pos = (unsigned)(mc - q * p.a_rpi);
+            long long ao = (long long)q * p.a_item + (long long)pos * p.lda, co = (long long)q * p.c_item + (long long)pos * p.ldc;
+#define NT_ROW_STEP8(k)                                                                \
+            if (mb + 8 * (k) < p.M) {                                                  \
+                pos += 8; ao += 8 * p.lda; co += 8 * p.ldc;                            \
+                if (pos >= rpi) { pos -= rpi; ao += awrap; co += cwrap; }              \
+            }
+            ga0 = Ab + ao + sch * CH; cro0 = co;
+            NT_ROW_STEP8(1);
+            ga1 = Ab + ao + sch * CH; cro1 = co;
+            NT_ROW_STEP8(2);
+            ga2 = Ab + ao + sch * CH; cro2 = co;
+            NT_ROW_STEP8(3);
+            ga3 = Ab + ao + sch * CH; cro3 = co;
+#undef NT_ROW_STEP8
+        } else {
+            ga0 = Ab + row_off2(min(m0 + r0, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
+            ga1 = Ab + row_off2(min(m0 + r0 + 8, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
+            ga2 = Ab + row_off2(min(m0 + r0 + 16, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
+            ga3 = Ab + row_off2(min(m0 + r0 + 24, p.M - 1), p.a_rpi, p.a_item, p.lda, p.a_rpi2, p.a_item2) + sch * CH;
+        }
         const int br0 = DIRECT ? direct_b_col(r0) : r0, br1 = DIRECT ? direct_b_col(r0 + 8) : r0 + 8;
         const int br2 = DIRECT ? direct_b_col(r0 + 16) : r0 + 16, br3 = DIRECT ? direct_b_col(r0 + 24) : r0 + 24;
         const T* gb0 = Bb + row_off(min(n0 + br0, p.N - 1), p.b_rpi, p.b_item, p.ldb) + sch * CH;
@@ -655,7 +749,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
         if (DO_READ) NT_WAIT_SET(fa0, fb0);                                                                      \
     } while (0)
         static_assert(TI * TJ >= 8 + NFRAG, "block 1 must have room for 8 DMA pieces and one fragment set");
-        if constexpr (BITS_IN_LDS) {
+        if constexpr (EPI == EPI_DGRAD_MASK) {
+        } else if constexpr (EPI != EPI_GENERIC) {
+            // the same DMA as below from the row offsets found above (mask_bits is set, one GEMM per launch)
+            const unsigned char* mbase = p.mask_bits + (lane & 7) * 4;
+#define NT_BITS_DMA(k, cro)                                                                                                      \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mbase + (((cro) + n0) >> 3)),       \
+                                             (__attribute__((address_space(3))) void*)(lds3 + BITS_OFF + (wave_u * 4 + (k)) * 256), 4, 0, 0)
+            NT_BITS_DMA(0, cro0); NT_BITS_DMA(1, cro1); NT_BITS_DMA(2, cro2); NT_BITS_DMA(3, cro3);
+#undef NT_BITS_DMA
+        } else if constexpr (BITS_IN_LDS) {
             if (p.mask_bits) {
                 // tile rows r, 32 bytes each: one DMA instruction = 8 rows x (8 lanes x 4 B); wave w fetches rows 32 w .. 32 w + 31.
                 // Older than every stage request of this tile, so the first vmcnt(0) of the K loop covers it.
@@ -723,6 +826,120 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
     }
 
 
+    if constexpr (EPI != EPI_GENERIC) {
+        constexpr int CPR = TBN / 8, RPP = NTHR / CPR, NPASS = TBM / RPP;       // 16-byte chunks per tile row, rows per pass, passes
+        // Store passes: thread -> chunk cc of tile rows rr + RPP q, q = 0 .. NPASS - 1.  (item, position in item) of the first row by one
+        // division; NT_ROW_NEXT steps to the next pass's row.  A pass has a row while RPP q < nrow; the row is a pad row from c_valid on.
+        // (Found where it is first needed — in front of the mask loads, else behind the tile image: not live beside the accumulators.)
+        const int cc = tid % CPR, rr = tid / CPR;
+        int nrow;
+        unsigned rpi, valid, pos0;
+        long long coff0, rstep, cwrap;
+#define NT_FIRST_ROW()                                                                                          \
+        do {                                                                                                    \
+            const int mf = m0 + rr, q0 = p.c_rpi ? mf / p.c_rpi : 0;                                            \
+            nrow = p.M - mf;                                                                                    \
+            rpi = p.c_rpi ? (unsigned)p.c_rpi : 0xffffffffu;                                                    \
+            valid = p.c_rpi ? (unsigned)p.c_valid : 0xffffffffu;                                                \
+            pos0 = (unsigned)(mf - q0 * p.c_rpi);                                                               \
+            coff0 = (long long)q0 * p.c_item + (long long)pos0 * p.ldc + n0 + cc * 8;                           \
+            rstep = (long long)RPP * p.ldc;                                                                     \
+            cwrap = p.c_item - (long long)p.c_rpi * p.ldc;                                                      \
+        } while (0)
+#define NT_ROW_NEXT(pos, coff)                                          \
+        do {                                                            \
+            pos += RPP; coff += rstep;                                  \
+            if (pos >= rpi) { pos -= rpi; coff += cwrap; }              \
+        } while (0)
+        [[maybe_unused]] uint4 mk[NPASS];
+        if constexpr (EPI == EPI_DGRAD_MASK) {
+            // all of the thread's mask chunks are requested here, so the tile pays the memory latency once and under the LDS writes
+            NT_FIRST_ROW();
+            const T* Mb = (const T*)p.mask;
+            unsigned pos = pos0;
+            long long coff = coff0;
+#pragma unroll
+            for (int q = 0; q < NPASS; ++q) {
+                mk[q] = q * RPP < nrow ? *(const uint4*)(Mb + coff) : make_uint4(0, 0, 0, 0);
+                NT_ROW_NEXT(pos, coff);
+            }
+        }
+        // accumulators -> bf16 tile image (the K loop ended on a barrier), with the sign bits applied where the mask came as bits
+#pragma unroll
+        for (int i = 0; i < TI; ++i) {
+            const int ml = (wm * TI + i) * 16 + frow;
+            unsigned mlo = 0, mhi = 0;
+            if constexpr (EPI != EPI_DGRAD_MASK) {
+                const uint2 mb8 = *(const uint2*)(lds + BITS_OFF + ml * (TBN / 8) + wn * 8);
+                mlo = mb8.x >> (4 * fg); mhi = mb8.y >> (4 * fg);
+            }
+#pragma unroll
+            for (int j = 0; j < TJ; ++j) {
+                const int nl = (wn * TJ + j) * 16 + fg * 4;
+                bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (bf16_t)acc[i][j][e];
+                uint2 w = __builtin_bit_cast(uint2, o);
+                if constexpr (EPI != EPI_DGRAD_MASK) {
+                    const unsigned nib = ((j < 2 ? mlo : mhi) >> ((j & 1) * 16)) & 0xfu;
+                    w.x &= (nib & 1u ? 0xffffu : 0u) | (nib & 2u ? 0xffff0000u : 0u);
+                    w.y &= (nib & 4u ? 0xffffu : 0u) | (nib & 8u ? 0xffff0000u : 0u);
+                }
+                *(uint2*)((TO*)(lds + ml * EPI_RS) + nl) = w;
+            }
+        }
+        __syncthreads();
+        if constexpr (EPI == EPI_DGRAD_C1) {
+            nt_conv1_slabs<TBM, TBN, EPI_RS>(lds, lane, wave, mt, nt, numN, p);
+        } else {
+            // The accumulators are dead, so the LDS reads of all passes are issued before the first wait and the stores leave as the
+            // data arrives.
+            uint4 v[NPASS];
+#pragma unroll
+            for (int q = 0; q < NPASS; ++q) v[q] = *(const uint4*)(lds + (rr + q * RPP) * EPI_RS + cc * 16);
+            if constexpr (EPI != EPI_DGRAD_MASK) NT_FIRST_ROW();
+            unsigned pos = pos0;
+            long long coff = coff0;
+            TO* const Cb = (TO*)p.C;
+            const bool skip = p.flags & GEMM_SKIP_PAD_ROWS;
+            float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#define NT_STORE_PASSES(WANT_CS)                                                                                                     \
+            _Pragma("unroll") for (int q = 0; q < NPASS; ++q) {                                                                      \
+                const bool pad = pos >= valid;                                                                                       \
+                uint4 w = pad ? make_uint4(0, 0, 0, 0) : v[q];                                                                       \
+                if constexpr (EPI == EPI_DGRAD_MASK) {      /* bf16 > 0  <=>  sign bit clear and not zero */                         \
+                    const unsigned mw[4] = {mk[q].x, mk[q].y, mk[q].z, mk[q].w};                                                     \
+                    unsigned vw[4] = {w.x, w.y, w.z, w.w};                                                                           \
+                    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                                  \
+                        const unsigned lo = mw[e] & 0xffffu, hi = mw[e] >> 16;                                                       \
+                        vw[e] &= ((lo != 0u && lo < 0x8000u) ? 0xffffu : 0u) | ((hi != 0u && hi < 0x8000u) ? 0xffff0000u : 0u);      \
+                    }                                                                                                                \
+                    w = make_uint4(vw[0], vw[1], vw[2], vw[3]);                                                                      \
+                }                                                                                                                    \
+                if (q * RPP < nrow && !(pad && skip)) {                                                                              \
+                    store_out16((uint4*)(Cb + coff), w, GEMM_WT_SYSTEM);                                                             \
+                    if (WANT_CS) {      /* column sums of what was just stored, in ascending pass order */                           \
+                        const unsigned u4[4] = {w.x, w.y, w.z, w.w};                                                                 \
+                        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                              \
+                            cs[2 * e] += __builtin_bit_cast(float, u4[e] << 16);                                                     \
+                            cs[2 * e + 1] += __builtin_bit_cast(float, u4[e] & 0xffff0000u);                                         \
+                        }                                                                                                            \
+                    }                                                                                                                \
+                }                                                                                                                    \
+                NT_ROW_NEXT(pos, coff);                                                                                              \
+            }
+            if (p.colsum_slabs) {
+                NT_STORE_PASSES(true)
+                nt_colsum_reduce<TBN, NTHR>((float*)(lds + CS_OFF), cs, tid, mt, n0, p);
+            } else {
+                NT_STORE_PASSES(false)
+            }
+#undef NT_STORE_PASSES
+        }
+#undef NT_ROW_NEXT
+#undef NT_FIRST_ROW
+        return;
+    }
     TO* Cb = (TO*)p.C + (long long)blockIdx.z * p.c_batch;
     const T* Mb = (const T*)p.mask;
     const bool relu = p.flags & GEMM_RELU;
@@ -942,47 +1159,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
                 }
             }
             if constexpr (CS_IN_LDS) {
-                // GemmNT::colsum_slabs: the tile's 256 column sums — 16 row groups per column chunk through LDS, fixed order — to
-                // slabs[mt][n]: the bias gradient of the layer below without another pass over this kernel's 0.06-0.24 GB output
-                if (want_cs) {
-                    float* red = (float*)(lds + CS_OFF);
-                    *(f32x4*)(red + (rr * CPR + cc) * 8) = (f32x4){cs[0], cs[1], cs[2], cs[3]};
-                    *(f32x4*)(red + (rr * CPR + cc) * 8 + 4) = (f32x4){cs[4], cs[5], cs[6], cs[7]};
-                    __syncthreads();
-                    if (tid < TBN && n0 + tid < p.N) {
-                        float t = 0.f;
-#pragma unroll
-                        for (int g = 0; g < RPP; ++g) t += red[(g * CPR + (tid >> 3)) * 8 + (tid & 7)];
-                        p.colsum_slabs[(long long)mt * p.N + n0 + tid] = t;
-                    }
-                }
+                if (want_cs) nt_colsum_reduce<TBN, NTHR>((float*)(lds + CS_OFF), cs, tid, mt, n0, p);
             }
             if constexpr (C1) {
-                // slab[j][c] = sum over the tile's rows of xw[row][j] * G[row][c]: a (16 x TBM) x (TBM x TBN) product on the
-                // matrix pipe with both operands read transposed from their LDS images (the TN kernel's fragment reads);
-                // wave w owns the column blocks 2w and 2w+1, so no sums cross waves.  x = hi + lo keeps ~16 mantissa bits.
                 static_assert(TBN / 16 == 2 * WM * WN, "two 16-column blocks per wave");
                 __syncthreads();
-                const unsigned char* xw = lds + TBM * EPI_RS;
-                f32x4 d0 = (f32x4){0.f, 0.f, 0.f, 0.f}, d1 = d0;
-#pragma unroll
-                for (int ks = 0; ks < TBM / 32; ++ks) {
-                    const uint4 fh = tn_frag_rb(xw, 32, 0, ks, lane);
-                    const uint4 fl = tn_frag_rb(xw + TBM * 32, 32, 0, ks, lane);
-                    const uint4 g0 = tn_frag_rb(lds, EPI_RS, (wave * 2) * 16, ks, lane);
-                    const uint4 g1 = tn_frag_rb(lds, EPI_RS, (wave * 2 + 1) * 16, ks, lane);
-                    mfma_chunk<bf16_t>(d0, g0, fh);
-                    mfma_chunk<bf16_t>(d0, g0, fl);
-                    mfma_chunk<bf16_t>(d1, g1, fh);
-                    mfma_chunk<bf16_t>(d1, g1, fl);
-                }
-                const int slot = lane & 15, c4 = (lane >> 4) * 4;
-                if (slot <= p.c1_kw) {
-                    float* sl = p.c1_slabs + ((long long)mt * numN + nt) * (p.c1_kw + 1) * TBN + (long long)slot * TBN;
-                    // (written through like the tile stores: 82 MB of slabs per launch, read by the reduction right behind this kernel)
-                    store_out16((uint4*)(sl + (wave * 2) * 16 + c4), __builtin_bit_cast(uint4, d0), p.flags);
-                    store_out16((uint4*)(sl + (wave * 2 + 1) * 16 + c4), __builtin_bit_cast(uint4, d1), p.flags);
-                }
+                nt_conv1_slabs<TBM, TBN, EPI_RS>(lds, lane, wave, mt, nt, numN, p);
             }
             return;
         }
@@ -1973,7 +2155,15 @@ constexpr int NT_STAGGER64 = 32;
 // start stagger of the persistent kernel's first round of tiles, in the same unit
 constexpr int NT_PERSIST_STAGGER64 = 64;
 
-int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
+static std::atomic<int> g_nt_debug_flags{0};
+int gemm_nt_debug_flags(int flags) {
+    if (flags & ~(GEMM_GENERIC_EPI | GEMM_QUERY_EPI)) return -1;
+    return g_nt_debug_flags.exchange(flags);
+}
+
+int launch_gemm_nt(const GemmNT& p_in, int dtype, int batch, hipStream_t stream) {
+    GemmNT p = p_in;
+    p.flags |= g_nt_debug_flags.load(std::memory_order_relaxed);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || batch <= 0) return CPC_EINVAL;
     const int ch = dtype == CPC_DTYPE_BF16 ? 8 : 4;
     if (p.K % ch || p.lda % ch || p.ldb % ch || p.ldc % 4) return CPC_EINVAL;
@@ -1986,6 +2176,7 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
     if (dtype == CPC_DTYPE_F32 && batch == 1 && (p.N == 8 || p.N == 16 || p.N == 32) && p.K <= 32 && p.K % 4 == 0 && !p.mask &&
         p.a_rpi == 0 && p.b_rpi == 0 && p.M >= 4096 && p.ldc % 4 == 0 && (p.c_rpi == 0 || p.c_item % 4 == 0) &&
         !(p.flags & GEMM_FORCE_GENERIC) && p.m_off == 0 && ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.C % 16 == 0)) {
+        if (p.flags & GEMM_QUERY_EPI) return 100 + EPI_GENERIC;
         const long long rows_pp = 256 / (p.N / 8);
         const int blocks = (int)std::min<long long>(256 * 8, (p.M + rows_pp - 1) / rows_pp);
         hipLaunchKernelGGL(gemm_nt_skinny_f32_kernel, dim3(blocks), dim3(256), 0, stream, p);
@@ -2037,12 +2228,23 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
         if (dma) hipLaunchKernelGGL((gemm_nt_fast_kernel<TT, TOO, WMM, WNN, TII, TJJ, true>), grid, dim3(NTH), 0, stream, ARG);  \
         else hipLaunchKernelGGL((gemm_nt_fast_kernel<TT, TOO, WMM, WNN, TII, TJJ, false>), grid, dim3(NTH), 0, stream, ARG);     \
     } while (0)
+    // Compile-time epilogue forms (EPI_DGRAD / EPI_DGRAD_C1 above): only for a launch that is exactly what cpc_conv_dgrad(_rows) and
+    // cpc_conv_dgrad_conv1(_rows) build — one 256x256 bf16 LDS-DMA GEMM with the sign-bit mask (which replaces `mask` wherever both are given)
+    // or the full-size mask and the LDS-staged epilogue, no bias, no ReLU, plain B rows, A and C rows in items of the same >= 32 rows or not in items at all.
+    // The checks below still apply to it; everything else keeps the generic body.
+    const bool epi_form = big && dma && batch == 1 && !of32 && (q.flags & GEMM_WIDE_EPI) && (p.mask_bits || p.mask) && !p.bias &&
+                          !(p.flags & (GEMM_RELU | GEMM_GENERIC_EPI | GEMM_NARROW_EPI)) && !banded && p.m_off == 0 && p.b_rpi == 0 &&
+                          p.a_rpi == p.c_rpi && (p.c_rpi == 0 || (p.c_rpi >= 32 && p.c_valid >= 0)) && p.N % 256 == 0 &&
+                          (p.M - 1) / 256 * 256LL + 512 < 0x7fffffffLL;
     if (p.flags & GEMM_EPI_CONV1) {
         // fused layer-1 weight gradient: only the 256x256 LDS-DMA kernel with the LDS-staged epilogue has that variant
         if (!(big && dma && (q.flags & GEMM_WIDE_EPI) && (p.mask || p.mask_bits) && batch == 1 && p.c1_x && p.c1_slabs && p.c1_sub > 0 &&
               p.N % p.c1_sub == 0 && (p.N / p.c1_sub) % 256 == 0 && p.c1_kw >= 1 && p.c1_kw <= 15 && p.c1_rpi > 0))
             return CPC_EINVAL;
-        hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, true>), grid, dim3(512), 0, stream, q);
+        const bool c1_form = epi_form && p.mask_bits;           // (the fused launch has a form for the sign-bit mask only)
+        if (p.flags & GEMM_QUERY_EPI) return 100 + (c1_form ? EPI_DGRAD_C1 : EPI_GENERIC);
+        if (c1_form) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, true, false, EPI_DGRAD_C1>), grid, dim3(512), 0, stream, q);
+        else hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, true>), grid, dim3(512), 0, stream, q);
         CPC_CHECK_LAUNCH();
         return CPC_OK;
     }
@@ -2059,6 +2261,9 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
     if (p.mask_bits && !(big && dma && dtype == CPC_DTYPE_BF16 && !of32 && (q.flags & GEMM_WIDE_EPI) && p.N % 256 == 0 && p.ldc % 32 == 0 &&
                          p.c_item % 32 == 0 && p.c_batch % 32 == 0 && (uintptr_t)p.mask_bits % 4 == 0))
         return CPC_EINVAL;
+    if (dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) return CPC_EINVAL;
+    const int form = !epi_form || direct ? EPI_GENERIC : p.mask_bits ? EPI_DGRAD : EPI_DGRAD_MASK;
+    if (p.flags & GEMM_QUERY_EPI) return 100 + form;
     if (dtype == CPC_DTYPE_BF16) {
         if (big) {
             if (of32) NT_LAUNCH(bf16_t, float, 2, 4, 8, 4, 512, q);
@@ -2072,6 +2277,8 @@ int launch_gemm_nt(const GemmNT& p, int dtype, int batch, hipStream_t stream) {
                 hipLaunchKernelGGL((gemm_nt_persist_kernel<>), dim3(256), dim3(512), 0, stream, q);      // one workgroup per CU walks the tiles
             }
             else if (direct) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, true>), grid, dim3(512), 0, stream, q);
+            else if (form == EPI_DGRAD) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, false, EPI_DGRAD>), grid, dim3(512), 0, stream, q);
+            else if (form == EPI_DGRAD_MASK) hipLaunchKernelGGL((gemm_nt_fast_kernel<bf16_t, bf16_t, 2, 4, 8, 4, true, false, false, EPI_DGRAD_MASK>), grid, dim3(512), 0, stream, q);
             else NT_LAUNCH(bf16_t, bf16_t, 2, 4, 8, 4, 512, q);
         } else if (fast) {
             if (of32) NT_LAUNCH(bf16_t, float, 2, 2, 4, 4, 256, q);

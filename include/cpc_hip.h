@@ -40,6 +40,11 @@ extern "C" {
 #define CPC_GEMM_SMALL_TILE 16   /* keep the 128x128 tile where the 256x256 one would be chosen (A/B check) */
 #define CPC_GEMM_BIG_TILE 0x100000 /* NT/bf16: the 256x256 tile also where fewer than 200 of them exist (M >= 256): a launch that is ONE nearly
                                     * full round of such tiles (layer 2's target rows at the headline size: 196) runs 0.11 instead of 0.135 ms */
+#define CPC_GEMM_GENERIC_EPI 0x200000 /* NT/bf16 256x256: the generic epilogue body also for the masked data-gradient launches that have a
+                                       * compile-time epilogue form (A/B check: bit-identical results) */
+#define CPC_GEMM_QUERY_EPI 0x800000   /* NT: launch nothing; a call that passes every argument check returns 100 + the epilogue form its launch would
+                                       * run (0 generic, 1 masked data gradient with the sign-bit mask, 2 the same fused with layer 1's weight gradient, 3 masked data gradient
+                                       * with the full-size mask) instead of 0.  For tests only. */
 
 /* 9: the tuning-knob entry point (stagger, store policy, timing probes of the NT GEMM) is gone; cpc_gru_set_streaming is on / off only.
  *    Added later under 9 (backward compatible, no entry point changed): the difference scores cpc_diff_scores, cpc_diff_scores_bwd,
@@ -57,6 +62,7 @@ extern "C" {
  *    cpc_norm_rows, cpc_norm_rows_bwd.
  *    Added later under 9 (backward compatible, no entry point changed): the exponential moving average of the weights cpc_ema,
  *    cpc_ema_swap; the temperature in device memory cpc_norm_rows_dev, cpc_norm_rows_bwd_dev, cpc_temperature_step, cpc_temperature_set.
+ *    Added later under 9 (backward compatible, no entry point changed): cpc_gemm_nt_bits, cpc_gemm_nt_debug_flags.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -111,6 +117,15 @@ typedef struct cpc_gemm_nt_args {
     int k_taps; long long k_tap_stride; long long k_tap_stride_a;
 } cpc_gemm_nt_args;
 int cpc_gemm_nt(const cpc_gemm_nt_args* args, void* stream);
+/* FOR TESTS AND A/B TIMING ONLY (this entry point and cpc_gemm_nt_debug_flags below; no production caller, not part of the supported
+ * interface).  The same launch with the ReLU-backward mask as sign bits (cpc_sign_bits of the array `mask` would name; one byte per 8 elements, addressed
+ * by the C element offset / 8; NULL only where args->mask is given) and, optionally, the per-tile column sums of what it stores (colsum_slabs[ceil(M / 256)][N] f32 or
+ * NULL): what cpc_conv_dgrad builds, with every field of the argument block in the caller's hands.  bf16 launches that take the 256 x 256
+ * tile with the LDS-staged epilogue only (N % 256 == 0, ldc % 32 == 0, c_item % 32 == 0); CPC_EINVAL otherwise. */
+int cpc_gemm_nt_bits(const cpc_gemm_nt_args* args, const void* mask_bits, float* colsum_slabs, void* stream);
+/* Tests and A/B timing only: flags OR-ed into every NT launch of the process from now on, whichever entry point builds it: CPC_GEMM_GENERIC_EPI,
+ * CPC_GEMM_QUERY_EPI or 0; returns the previous value, -1 for anything else.  Not for use while another thread launches. */
+int cpc_gemm_nt_debug_flags(int flags);
 
 /* C[i][j] = sum_m A[m][i] * B[m][j]  (reduction over the row index of both operands), optionally split over m into
  * nsplit f32 slabs C + s*slab_stride that cpc_reduce_slabs sums deterministically.

@@ -212,6 +212,10 @@ int cpc_conv1_fused_reduce(const float* slabs, float* tmp, float* dw, float* db,
  * gradient reads (ceil(kw / stride) - 1) * Cout elements BEFORE dy.  The caller states how many elements are readable there
  * (x_tail after the end of x, dy_head in front of dy; zeros expected in dy_head, values in x_tail only ever meet pad rows);
  * CPC_EINVAL when that is less than the call needs.
+ * The data gradient also requires every item of dy to END in at least D - 1 = ceil(kw / stride) - 1 zero pad rows (Lout_alloc >=
+ * Lout_valid + D - 1): row 0 of item b reads the last D - 1 rows of item b - 1 as its preceding rows, exactly as row 0 of item 0 reads
+ * dy_head.  Lin_valid is not used to zero anything: dx is zero beyond it, and at valid positions no window covers, only because those
+ * pad rows (and dy_head) are zero.
  * x_act_bits: the sign-bit mask cpc_sign_bits makes of x_act (NULL: the mask is read from x_act).  Only the bf16 256 x 256-tile
  * kernel knows the format (>= 200 such tiles, stride * Cin a multiple of 256): CPC_EINVAL where the launch would take another
  * kernel, never a silent fall-back.  With x_act_bits, x_act may be NULL. */

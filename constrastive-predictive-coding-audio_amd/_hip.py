@@ -177,6 +177,8 @@ _SIGNATURES = {
     "cpc_nce_grouped_workspace_floats": ([_I, _I], _L),
     "cpc_nce_loss_grouped": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _I, _U64, _U64, _I, _P], _I),
     "cpc_nce_group_mask": ([_P, _P, _I, _I, _I, _I, _U64, _U64, _P], _I),
+    "cpc_nce_banked_workspace_floats": ([_I, _I, _I], _L),
+    "cpc_nce_loss_banked": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _U64, _I, _F, _I, _P], _I),
     "cpc_nce_all_workspace_floats": ([_I, _I], _L),
     "cpc_nce_loss_all": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P], _I),
     "cpc_score_lse": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P], _I),

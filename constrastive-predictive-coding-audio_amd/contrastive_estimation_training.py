@@ -488,6 +488,17 @@ class ContrastiveEstimationTrainer:
         self.negative_groups = None
         self.negative_group_ids = None
         self.last_empty_negative_sets = None
+        # Not in the reference's signature: a cross-batch memory of negatives ("Negative bank").  negative_bank: None, or
+        # M in 1 .. 63 — every target is also contrasted against the predictions of the M latest steps, kept as constants
+        # (engine.NegativeBank; the candidate count grows from B to (M + 1) B at the cost of one skinny score GEMM and one longer
+        # contraction per step, no encoder work).  The first step after an empty bank is the in-batch step bit for bit;
+        # negative_bank_filled tells how many earlier steps the bank holds, reset_negative_bank() empties it.  The trainer owns the
+        # bank across train() calls with the same batch shape.  It is not checkpointed: a resumed run starts with an empty bank.  Engine
+        # route only (Adam with linear_score_function, softplus_score_function or a NormalizedScoreFunction of constant temperature),
+        # default loss branch, no use_graph, not combined with num_negatives / negative_groups / global_negatives / the gradient
+        # penalty; validate() stays in-batch.  Under data parallelism every rank keeps a bank of its own shard (permitted, unverified).
+        self.negative_bank = None
+        self._bank = None
         # Not in the reference's signature: clip the gradient to this global L2 norm before the update, as
         # torch.nn.utils.clip_grad_norm_ in front of optimizer.step() (None: no clipping, the reference's step).  On the fused routes
         # the norm and the clipped Adam are HIP kernels (engine.FusedAdam(max_grad_norm=...)); under data parallelism it is the norm of
@@ -648,6 +659,61 @@ class ContrastiveEstimationTrainer:
         gid = np.ascontiguousarray(ids[np.asarray(idx, dtype=np.int64)], dtype=np.int32)
         self.last_empty_negative_sets = empty_negative_sets(gid, mode)
         return {"negative_groups": (torch.from_numpy(gid).to(device), mode)}
+
+    def _check_negative_bank(self):
+        """Up-front checks of negative_bank (before any GPU work): ValueError unless None or an integer in 1 .. 63,
+        NotImplementedError for what the banked loss does not cover.  Returns None or M."""
+        if self.negative_bank is None:
+            return None
+        from .engine import check_slots_back
+        slots_back = check_slots_back(self.negative_bank)
+        if self.score_over_all_timesteps:
+            raise NotImplementedError("negative_bank: defined for score_over_all_timesteps=False only (its rows are the predictions of "
+                                      "one step k each, not the (item, step) pairs of the all-timesteps branch)")
+        if self.wasserstein_gradient_penalty:
+            raise NotImplementedError("negative_bank: wasserstein_gradient_penalty runs the dense loss kernels in its tangent passes; "
+                                      "a bank is not carried through them")
+        if self.use_graph:
+            raise NotImplementedError("negative_bank: use_graph replays one captured step, but the bank's cursor and its mask of filled "
+                                      "slots live on the host and change every step")
+        if self.global_negatives:
+            raise NotImplementedError("negative_bank: global_negatives contrasts against the gathered batches of all ranks; the bank "
+                                      "holds the rank's own earlier predictions only")
+        if self.num_negatives is not None or self.negative_groups is not None:
+            raise NotImplementedError("negative_bank together with num_negatives or negative_groups: no selection over the rows of "
+                                      "earlier steps exists")
+        sf = self.score_function
+        if sf is difference_score_function:
+            raise NotImplementedError("negative_bank: difference scores are formed by cpc_diff_scores, which takes no ring of earlier "
+                                      "predictions")
+        if isinstance(sf, NormalizedScoreFunction) and (sf.learnable or sf.schedule is not None):
+            raise NotImplementedError("negative_bank: a learnable or scheduled temperature — the rows of earlier steps carry the "
+                                      "1 / temperature of their own step")
+        if not (self._fused() or self._engine_normalized()):
+            raise NotImplementedError("negative_bank runs on the engine route only: optimizer=torch.optim.Adam with "
+                                      "linear_score_function, softplus_score_function or a NormalizedScoreFunction of constant "
+                                      f"temperature, not {self.optimizer!r} with {sf!r}")
+        return slots_back
+
+    def reset_negative_bank(self):
+        """Empties the bank: the next step is the in-batch step again, the ones after it fill the bank anew."""
+        if self._bank is not None:
+            self._bank.reset()
+
+    @property
+    def negative_bank_filled(self):
+        """How many earlier steps the bank holds at present (0 without a bank)."""
+        return 0 if self._bank is None else self._bank.filled
+
+    def _bank_kw(self, slots_back):
+        """{} without negative_bank; else the step's negative_bank = the trainer's engine.NegativeBank, made anew when M changed."""
+        if slots_back is None:
+            self._bank = None
+            return {}
+        if self._bank is None or self._bank.slots != slots_back + 1:
+            from .engine import NegativeBank
+            self._bank = NegativeBank(slots_back)
+        return {"negative_bank": self._bank}
 
     def _check_grad_clip(self):
         """Up-front checks of max_grad_norm (before any GPU work): ValueError unless None or finite and > 0, NotImplementedError
@@ -836,6 +902,7 @@ class ContrastiveEstimationTrainer:
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
         self._check_negatives(batch_size)
         grouping = self._check_negative_groups()
+        bank_kw = self._bank_kw(self._check_negative_bank())
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
         trust_ratio, trust_clip = self._check_trust()
@@ -1027,6 +1094,7 @@ class ContrastiveEstimationTrainer:
             if here is not None and here[1] is not None and hasattr(optimizer, "t"):
                 optimizer.t = here[1]                               # no update has happened since the start of the NaN step
             self.training_step = step          # the reference leaves train() inside step `step`, before its update (:124-133)
+            self.reset_negative_bank()         # (its latest rows come from the NaN step and the ones launched behind it)
             if bad_grad_norm[0]:
                 print("gradient norm not finite at step", step, "(max_grad_norm): no update was applied")
             print("nan loss")
@@ -1127,7 +1195,7 @@ class ContrastiveEstimationTrainer:
                                                      all_timesteps=bool(self.score_over_all_timesteps),
                                                      grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
                                                      global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
-                                                     **score_kw, **self._negatives_kw(), **groups_kw)
+                                                     **score_kw, **self._negatives_kw(), **groups_kw, **bank_kw)
                         if sync is not None:
                             sync.finish()
                         # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up

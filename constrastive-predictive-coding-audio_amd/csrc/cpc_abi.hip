@@ -711,6 +711,15 @@ int cpc_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int
     return launch_nce_group_mask(mask, groups, B, K, mode, n_neg, seed, draw, (hipStream_t)stream);
 }
 
+long long cpc_nce_banked_workspace_floats(int B, int K, int slots) { return nce_banked_workspace_floats(B, K, slots); }
+
+int cpc_nce_loss_banked(const float* S, void* dS, void* dST_cur, float* out, float* workspace, int B, int K, int ld, int slots, int cur,
+                        unsigned long long valid_mask, int softplus, float regularization, int dtype, void* stream) {
+    if (!S || !dS || !dST_cur || !out || !workspace) return CPC_EINVAL;
+    return launch_nce_banked(S, dS, dST_cur, out, workspace, B, K, ld, slots, cur, valid_mask, softplus, regularization, dtype,
+                             (hipStream_t)stream);
+}
+
 int cpc_gp_score_coeff(const float* S, const float* St1, const float* St2, float* W, float* WT, int nmat, int rows, int cols, int ld,
                        int ldT, int mode, void* stream) {
     if (!S || !W || !WT) return CPC_EINVAL;

@@ -162,6 +162,9 @@ int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* w
                        int n_neg, unsigned long long seed, unsigned long long draw, int dtype, hipStream_t stream);
 int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw,
                            hipStream_t stream);
+long long nce_banked_workspace_floats(int B, int K, int slots);
+int launch_nce_banked(const float* S, void* dS, void* dST_cur, float* out, float* workspace, int B, int K, int ld, int slots, int cur,
+                      unsigned long long valid, int softplus, float reg, int dtype, hipStream_t stream);
 long long nce_grouped_workspace_floats(int B, int K);
 int launch_nce_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
                        const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw, int dtype,

@@ -123,9 +123,10 @@ __global__ __launch_bounds__(256) void nce_col_merge_kernel(const float* __restr
 // m[b][b'] = mean_k sp[k][b][b'] (the regulariser's mean over the prediction steps, contrastive_estimation_training.py:141)
 // for every pair once, plus per-block partials {sum of the valid scores sp[k][b][b], sum m^2, max sp}.  (The gradient kernel
 // used to recompute this mean in each of its K blocks per tile: 12 x the softplus work, 42 of the loss's 65 us.)
+// ks: floats between the blocks of two steps k (B ld; the banked loss reads one slot of [K][slots B][ld]).
 template <int KT>
 __device__ __forceinline__ void nce_mean_body(const float* __restrict__ S, float* __restrict__ mean, float* __restrict__ partial, int B,
-                                              int K_rt, int ld, int softplus, int bx) {
+                                              int K_rt, int ld, int softplus, int bx, long long ks) {
     __shared__ float red[3][256];
     const int K = KT > 0 ? KT : K_rt;
     const long long idx = (long long)bx * 256 + threadIdx.x;
@@ -137,7 +138,7 @@ __device__ __forceinline__ void nce_mean_body(const float* __restrict__ S, float
         if (KT > 0) {
             float raw[KT > 0 ? KT : 1];
 #pragma unroll
-            for (int k = 0; k < KT; ++k) raw[k] = sp0[(long long)k * B * ld];
+            for (int k = 0; k < KT; ++k) raw[k] = sp0[k * ks];
 #pragma unroll
             for (int k = 0; k < KT; ++k) {
                 const float sp = score_tf(raw[k], softplus);
@@ -147,7 +148,7 @@ __device__ __forceinline__ void nce_mean_body(const float* __restrict__ S, float
             }
         } else {
             for (int k = 0; k < K; ++k) {
-                const float sp = score_tf(sp0[(long long)k * B * ld], softplus);
+                const float sp = score_tf(sp0[k * ks], softplus);
                 m += sp;
                 mx = fmaxf(mx, sp);
                 if (b == bp) valid += sp;
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(256) void nce_col_mean_kernel(const float* __restri
     if ((int)blockIdx.x < ncol)
         nce_col_body<NCE_CW>(S, lse, colp, B, K, ld, softplus, B, nullptr, nullptr, blockIdx.x % ncb, blockIdx.x / ncb, 0, ncb, 1);
     else
-        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncol);
+        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncol, (long long)B * ld);
 }
 
 // out[0] = loss, out[1] = max score, out[2] = -mean valid, out[3] = mean lse, out[4] = reg term (already scaled)
@@ -784,7 +785,7 @@ __global__ __launch_bounds__(256) void nce_sampled_col_mean_kernel(const float* 
         const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
         if (col < K * B) nsm_col_body<H>(S, thr, lse, B, ld, softplus, n_neg, seed, draw, col);          // (wave-uniform)
     } else {
-        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb);
+        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb, (long long)B * ld);
     }
 }
 
@@ -932,7 +933,7 @@ __global__ __launch_bounds__(256) void nce_grouped_col_mean_kernel(const float* 
         const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
         if (col < K * B) nsg_col_body<H>(S, thr, lse, B, ld, softplus, groups, mode, n_neg, seed, draw, col);     // (wave-uniform)
     } else {
-        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb);
+        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb, (long long)B * ld);
     }
 }
 
@@ -997,6 +998,133 @@ __global__ __launch_bounds__(256) void nce_group_mask_kernel(unsigned char* __re
         const int row = lane + 64 * h;
         if (row < B) mask[((long long)k * B + row) * B + bp] = nsg_in<H>(row, h, bp, B, ok, t, key) ? 1 : 0;
     }
+}
+
+// ---- negative bank: the equal-step loss with the predictions of earlier steps as further candidates (include/cpc_hip.h, cpc_nce_loss_banked) ----
+// S[k][r][b'], r = slot B + b over `slots` ring slots of B rows; a column's log-sum-exp runs over the rows of the valid slots (up to
+// 64 B of them), everything else of the loss over slot `cur` alone.  Three launches: partial pass + pair means, merge, gradients.
+// Partial pass: a wave takes NBK_CHUNK rows of one slot and 64 columns, lanes along b' (every row read is one coalesced 256-byte
+// line), each lane an online (max, sum exp) pair in f32 over the chunk's rows in row order; a chunk never spans two slots, and the
+// chunks of invalid slots are neither read nor written.  Merge: one thread per column over the chunks of the valid slots in chunk
+// order.  Neither depends on the grid: the chunk constant alone fixes the summation order.
+constexpr int NBK_CHUNK = 32;       // rows per (max, sum) pair
+constexpr int NBK_WAVES = 4;        // chunks (waves) per workgroup of the partial pass
+
+__host__ __device__ __forceinline__ bool nbk_valid(unsigned long long valid, int slot) { return (valid >> slot) & 1ull; }
+
+// grid: npart = K x ceil(slots cps / NBK_WAVES) x ceil(B / 64) workgroups for the chunks (cps = ceil(B / NBK_CHUNK) chunks per slot),
+// then the pair means of slot cur (nce_mean_body), in one launch as nce_col_mean_kernel.  part[chunk][k][b'] = (max, sum).
+template <int KT>
+__global__ __launch_bounds__(256) void nce_bank_partial_mean_kernel(const float* __restrict__ S, float2* __restrict__ part,
+                                                                    float* __restrict__ mean, float* __restrict__ pairp, int B, int K,
+                                                                    int ld, int slots, int cur, unsigned long long valid, int softplus,
+                                                                    int cps, int ncb, int npart) {
+    if ((int)blockIdx.x >= npart) {
+        nce_mean_body<KT>(S + (long long)cur * B * ld, mean, pairp, B, K, ld, softplus, blockIdx.x - npart, (long long)slots * B * ld);
+        return;
+    }
+    const int ngrp = (slots * cps + NBK_WAVES - 1) / NBK_WAVES;
+    const int cb = blockIdx.x % ncb, grp = (blockIdx.x / ncb) % ngrp, k = blockIdx.x / (ncb * ngrp);
+    const int chunk = grp * NBK_WAVES + (threadIdx.x >> 6), bp = cb * 64 + (threadIdx.x & 63);
+    if (chunk >= slots * cps || bp >= B) return;
+    const int slot = chunk / cps;
+    if (!nbk_valid(valid, slot)) return;                       // (wave-uniform)
+    const int r0 = (chunk % cps) * NBK_CHUNK, r1 = min(B, r0 + NBK_CHUNK);
+    const float* col = S + ((long long)k * slots + slot) * B * ld + bp;
+    float mx = -INFINITY, sum = 0.f;
+    for (int base = r0; base < r1; base += 8) {                // eight rows per trip, their loads in flight together
+        float vv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vv[u] = (base + u < r1) ? col[(long long)(base + u) * ld] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (base + u < r1) {
+                const float v = score_tf(vv[u], softplus);
+                if (v > mx) { sum = sum * expf(mx - v) + 1.f; mx = v; }
+                else sum += (v == mx) ? 1.f : expf(v - mx);    // (a NaN score stays in the sum; +inf twice counts twice)
+            }
+        }
+    }
+    part[((long long)chunk * K + k) * B + bp] = make_float2(mx, sum);
+}
+
+// lse[c] for column c = k B + b' from the chunks of the valid slots, in chunk order, and one partial sum of lse per 256 columns.
+// A chunk whose scores are all NaN has max = -inf and sum = NaN: it is weighed like any other, so that the NaN reaches the loss.
+__global__ __launch_bounds__(256) void nce_bank_merge_kernel(const float2* __restrict__ part, int nchunk, int cps,
+                                                             unsigned long long valid, int ncols, float* __restrict__ lse,
+                                                             float* __restrict__ colp) {
+    __shared__ float red[256];
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    float l = 0.f;
+    if (c < ncols) {
+        float m = -INFINITY;
+        for (int z = 0; z < nchunk; ++z)
+            if (nbk_valid(valid, z / cps)) m = fmaxf(m, part[(long long)z * ncols + c].x);
+        float tot = 0.f;
+        for (int z = 0; z < nchunk; ++z) {
+            if (!nbk_valid(valid, z / cps)) continue;
+            const float2 p = part[(long long)z * ncols + c];
+            tot += (p.x == m) ? p.y : p.y * expf(p.x - m);      // (p.x == m: as in nce_col_body, m = +inf included)
+        }
+        l = m + logf(tot);
+        lse[c] = l;
+    }
+    red[threadIdx.x] = l;
+    __syncthreads();
+    for (int s2 = 128; s2 > 0; s2 >>= 1) {
+        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) colp[blockIdx.x] = red[0];
+}
+
+// nce_grad_kernel over the ring's rows: grid (column tiles, slots x row tiles, K), a 32 x 32 tile inside ONE slot.  A row of an
+// invalid slot gets zero coefficients (written every launch), a row of a stale slot the softmax term alone, a row of slot cur also
+// the diagonal and the regulariser, and its tile goes through LDS into dST_cur[k][b'][b] as in nce_grad_kernel.  A slot has
+// ceil(ld / 32) row tiles, as nce_grad_kernel's grid: where ld reaches into a tile of its own (B = 32, ld = 39) that tile holds
+// no row of dS, but its transposed store is what writes the zeros of dST_cur's pad columns [B, ld).
+template <typename T>
+__global__ __launch_bounds__(256) void nce_bank_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
+                                                            const float* __restrict__ mean, T* __restrict__ dS, T* __restrict__ dST,
+                                                            int B, int K, int ld, int slots, int cur, unsigned long long valid,
+                                                            int softplus, float reg, const float* __restrict__ colp, int ncol,
+                                                            const float* __restrict__ pairp, int npair, float* __restrict__ out) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
+    const int nrt = (ld + 31) / 32;
+    const int slot = blockIdx.y / nrt;
+    const int bp0 = blockIdx.x * 32, b0 = (blockIdx.y % nrt) * 32;
+    const float inv_bk = 1.f / ((float)B * (float)K);
+    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
+    const int k = blockIdx.z;
+    const bool live = nbk_valid(valid, slot), own = slot == cur;          // (workgroup-uniform)
+    const long long row0 = ((long long)k * slots + slot) * B;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = b0 + ty + 8 * r, bp = bp0 + tx;
+        float g = 0.f;
+        if (live && b < B && bp < B) {
+            const float x = S[(row0 + b) * ld + bp];
+            const float sp = score_tf(x, softplus);
+            float dsp = expf(sp - lse[k * B + bp]) * inv_bk;
+            if (own) {
+                dsp += reg_c * mean[(long long)b * ld + bp];
+                if (b == bp) dsp -= inv_bk;
+            }
+            g = dsp * score_grad(x, softplus);
+        }
+        if (b < B && bp < ld) dS[(row0 + b) * ld + bp] = from_f32<T>(g);
+        tile[ty + 8 * r][tx] = g;
+    }
+    if (own) {
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int bp = bp0 + ty + 8 * r, b = b0 + tx;
+            if (b < ld && bp < B) dST[((long long)k * B + bp) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
+        }
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(colp, ncol, pairp, npair, out, B, K, reg);
 }
 
 }  // namespace
@@ -1164,6 +1292,51 @@ int launch_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, 
     const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
     if (B <= 256) hipLaunchKernelGGL(nce_group_mask_kernel<4>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
     else hipLaunchKernelGGL(nce_group_mask_kernel<16>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+// ---- negative bank ----
+// workspace: chunk pairs (max, sum) [slots * ceil(B / NBK_CHUNK)][K][B] (8 bytes each, first: the workspace must be 8-byte aligned)
+// + lse [K][B] + column partials [ceil(K B / 256)] + pair partials [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7]
+long long nce_banked_workspace_floats(int B, int K, int slots) {
+    if (B <= 0 || K <= 0 || slots <= 0) return 0;
+    const long long nmb = ((long long)B * B + 255) / 256, cps = (B + NBK_CHUNK - 1) / NBK_CHUNK;
+    return 2LL * slots * cps * K * B + (long long)K * B + ((long long)K * B + 255) / 256 + 3 * nmb + (long long)B * (B + 8);
+}
+
+// (K <= NBK_MAXK keeps K B, the chunk count and every grid dimension far inside an int; one CPC_CHECK_LAUNCH behind the last launch,
+// as the siblings: a launch that fails leaves its error for it)
+constexpr int NBK_MAXK = 1024;
+
+int launch_nce_banked(const float* S, void* dS, void* dST_cur, float* out, float* workspace, int B, int K, int ld, int slots, int cur,
+                      unsigned long long valid, int softplus, float reg, int dtype, hipStream_t stream) {
+    if (B <= 1 || B > NSM_MAXB || K <= 0 || K > NBK_MAXK || ld < B || ld > B + 7 || slots < 2 || slots > 64 || cur < 0 || cur >= slots) return CPC_EINVAL;
+    if (!nbk_valid(valid, cur) || (slots < 64 && (valid >> slots) != 0)) return CPC_EINVAL;
+    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+    const int cps = (B + NBK_CHUNK - 1) / NBK_CHUNK, nchunk = slots * cps;
+    const int nmb = (int)(((long long)B * B + 255) / 256), ncolp = (K * B + 255) / 256;
+    float2* part = (float2*)workspace;
+    float* lse = workspace + 2LL * nchunk * K * B;
+    float* colp = lse + (long long)K * B;
+    float* pairp = colp + ncolp;
+    float* mean = pairp + 3LL * nmb;
+    const int ncb = (B + 63) / 64;
+    const int npart = K * ((nchunk + NBK_WAVES - 1) / NBK_WAVES) * ncb;
+    const dim3 g1(npart + nmb);
+#define NBK_PART(KT) \
+    hipLaunchKernelGGL(nce_bank_partial_mean_kernel<KT>, g1, dim3(256), 0, stream, S, part, mean, pairp, B, K, ld, slots, cur, valid, softplus, \
+                       cps, ncb, npart)
+    if (K == 12) NBK_PART(12); else if (K == 16) NBK_PART(16); else NBK_PART(0);
+#undef NBK_PART
+    hipLaunchKernelGGL(nce_bank_merge_kernel, dim3(ncolp), dim3(256), 0, stream, part, nchunk, cps, valid, K * B, lse, colp);
+    const dim3 g3((ld + 31) / 32, slots * ((ld + 31) / 32), K);
+    if (dtype == CPC_DTYPE_BF16)
+        hipLaunchKernelGGL((nce_bank_grad_kernel<bf16_t>), g3, dim3(256), 0, stream, S, lse, mean, (bf16_t*)dS, (bf16_t*)dST_cur, B, K, ld,
+                           slots, cur, valid, softplus, reg, colp, ncolp, pairp, nmb, out);
+    else
+        hipLaunchKernelGGL((nce_bank_grad_kernel<float>), g3, dim3(256), 0, stream, S, lse, mean, (float*)dS, (float*)dST_cur, B, K, ld,
+                           slots, cur, valid, softplus, reg, colp, ncolp, pairp, nmb, out);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }

@@ -279,9 +279,102 @@ def normalize_negative_groups(negative_groups, B, negatives=None):
     return groups, mode, check_group_negatives(B, n_neg), seed, draw
 
 
-def select_negatives(B, negatives, negative_groups, all_timesteps=False, global_negatives=None):
-    """The negative selection of a loss call, checked (check_negatives_supported) and normalised once for every score kind, as the
-    loss-kernel stage takes it: None (the whole batch), ("sampled", n_neg, seed, draw) or ("grouped", groups, mode, n_neg, seed, draw)."""
+MAX_BANK_SLOTS = 64          # the valid mask of cpc_nce_loss_banked is one 64-bit word
+
+
+def check_slots_back(slots_back):
+    """M, the number of earlier steps a negative bank keeps, as an int; ValueError unless it is an integer in [1, MAX_BANK_SLOTS - 1]."""
+    if isinstance(slots_back, bool) or not isinstance(slots_back, int) or not 1 <= slots_back <= MAX_BANK_SLOTS - 1:
+        raise ValueError(f"a negative bank keeps 1 .. {MAX_BANK_SLOTS - 1} earlier steps, got {slots_back!r}")
+    return slots_back
+
+
+class NegativeBank:
+    """Cross-batch memory of the InfoNCE loss ("Negative bank"): a ring of ``slots_back`` + 1 slots of B prediction rows,
+    ring[slot B + b][k][:] in the engine's storage dtype.  Every banked loss call copies its score operands (predicted_z; the
+    normalised, 1 / temperature-scaled rows of "normalized" scores) into slot ``cur``, contrasts the targets against the rows of all
+    slots whose bit is set in ``valid`` — the earlier steps' rows as constants — and then moves ``cur`` on.  The ring is allocated by
+    the first call from that engine's (B, K, E, dtype, device); host state only (cur, valid), so not for a captured step."""
+
+    def __init__(self, slots_back):
+        self.slots = check_slots_back(slots_back) + 1
+        self.cur, self.valid = 0, 1
+        self.ring = self.sizes = None
+
+    @property
+    def filled(self):
+        """How many slots hold an earlier step's rows."""
+        return bin(self.valid).count("1") - 1
+
+    def reset(self):
+        """Forgets the earlier steps: the next banked call is the in-batch loss again.  The rows are zeroed, so that the score GEMM
+        over the whole ring never meets what an abandoned run left (0 x NaN in the target contraction)."""
+        self.valid = 1 << self.cur
+        if self.ring is not None:
+            self.ring.zero_()
+
+    def bind(self, B, K, E, dtype, device):
+        """Allocates the ring on first use; ValueError (naming both) when a later caller has other sizes."""
+        sizes = (int(B), int(K), int(E), dtype, torch.device(device))
+        if self.ring is None:
+            self.sizes = sizes
+            self.ring = torch.zeros(self.slots * sizes[0], sizes[1], sizes[2], dtype=dtype, device=device)
+        elif sizes != self.sizes:
+            raise ValueError(f"this negative bank holds rows of (B, K, E, dtype, device) = {self.sizes}, the call has {sizes}: "
+                             "a bank belongs to one engine (reset() does not change its sizes; make a new NegativeBank)")
+
+    def slot(self, i):
+        """The [B][K][E] rows of slot i (a view)."""
+        B = self.sizes[0]
+        return self.ring[i * B:(i + 1) * B]
+
+    def advance(self):
+        """After a step: the slot just written becomes an earlier step's, the next one (whose bit is set at once: it is filled before
+        any score is formed) takes the coming step's rows."""
+        self.cur = (self.cur + 1) % self.slots
+        self.valid |= 1 << self.cur
+
+
+def check_negative_bank_supported(negative_bank, all_timesteps=False, global_negatives=None, gradient_penalty=None, negatives=None,
+                                  negative_groups=None, kind=None, temperature=None, graphed=False):
+    """A negative bank exists for the default loss branch of one process's own step with dot-product scores and a constant
+    temperature; what it does not cover is refused here, before any launch."""
+    if negative_bank is None:
+        return
+    if not isinstance(negative_bank, NegativeBank):
+        raise TypeError(f"negative_bank must be None or a NegativeBank, got {negative_bank!r}")
+    if all_timesteps:
+        raise NotImplementedError("a negative bank is defined for score_over_all_timesteps=False only: its rows are the predictions "
+                                  "of one step k each, and the all-timesteps branch contrasts every (item, step) pair")
+    if global_negatives is not None:
+        raise NotImplementedError("a negative bank holds the process's own earlier predictions; with a global_negatives object the "
+                                  "candidates span the gathered batches of all ranks, whose loss kernels know no bank")
+    if gradient_penalty is not None:
+        raise NotImplementedError("the gradient penalty's tangent passes run the dense loss kernels; a negative bank is not carried "
+                                  "through them")
+    if graphed:
+        raise NotImplementedError("a negative bank keeps its cursor and its mask of filled slots on the host and changes them every "
+                                  "step, which a captured graph cannot replay")
+    if negatives is not None or negative_groups is not None:
+        raise NotImplementedError("a negative bank together with sampled or grouped negatives: no selection over the rows of earlier "
+                                  "steps exists (their group ids and draws are gone)")
+    if kind == "difference":
+        raise NotImplementedError("a negative bank with difference scores: the banked scores come from the score GEMM, and "
+                                  "cpc_diff_scores takes no ring of earlier predictions")
+    if isinstance(temperature, DeviceTemperature):
+        raise NotImplementedError("a negative bank with a learnable or scheduled temperature: the rows of earlier steps carry the "
+                                  "1 / temperature of their own step and are constants, so neither the scale nor its gradient "
+                                  "would be the current one")
+
+
+def select_negatives(B, negatives, negative_groups, all_timesteps=False, global_negatives=None, negative_bank=None, kind=None,
+                     temperature=None):
+    """The negative selection of a loss call, checked (check_negatives_supported, check_negative_bank_supported) and normalised once
+    for every score kind, as the loss-kernel stage takes it: None (the whole batch), ("sampled", n_neg, seed, draw),
+    ("grouped", groups, mode, n_neg, seed, draw) or ("banked", bank)."""
+    if negative_bank is not None:
+        check_negative_bank_supported(negative_bank, all_timesteps, global_negatives, None, negatives, negative_groups, kind, temperature)
+        return ("banked", negative_bank)
     if negative_groups is not None:
         check_negatives_supported(negatives, all_timesteps, global_negatives, negative_groups=negative_groups)
         return ("grouped",) + normalize_negative_groups(negative_groups, B, negatives)
@@ -829,7 +922,7 @@ class CPCEngine:
         return 2.0 * R * R * E
 
     def nce_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, negatives=None,
-                             negative_groups=None, temperature=None):
+                             negative_groups=None, temperature=None, negative_bank=None):
         """Equal-step scores, InfoNCE loss + regulariser, and d loss / d (predicted_z, targets).
 
         contrastive_estimation_training.py:106-122,141 with score_over_all_timesteps=False.  Only the K diagonal
@@ -839,9 +932,11 @@ class CPCEngine:
         whole batch (cpc_nce_loss_sampled behind the same dense score GEMM; sampled_negatives.sampled_negative_mask).
         ``negative_groups``: None, or (groups, mode) — groups an int32 device tensor [B], mode "same" / "other": a target's candidates
         are the rows of its own group / of the other groups, all of them or, with ``negatives``, n_neg seeded ones
-        (cpc_nce_loss_grouped; sampled_negatives.grouped_negative_mask)."""
+        (cpc_nce_loss_grouped; sampled_negatives.grouped_negative_mask).
+        ``negative_bank``: None, or a NegativeBank — the predictions of the steps it remembers are further candidates of every target
+        (cpc_nce_loss_banked); the call writes this step's into it and moves its cursor on."""
         kind = score_kind(softplus, score)
-        self._loss_chain(kind, False, regularization, check_temperature(temperature, kind), negatives, negative_groups)
+        self._loss_chain(kind, False, regularization, check_temperature(temperature, kind), negatives, negative_groups, negative_bank)
 
     def nce_all_forward_backward(self, softplus: bool, regularization: float, score: Optional[str] = None, temperature=None):
         """score_over_all_timesteps=True (contrastive_estimation_training.py:108-114, :141): the full (B K) x (B K) score
@@ -853,30 +948,45 @@ class CPCEngine:
         self._loss_chain(kind, True, regularization, check_temperature(temperature, kind))
 
     def _loss_chain(self, kind: str, all_timesteps: bool, regularization: float, temperature=None, negatives=None,
-                    negative_groups=None):
+                    negative_groups=None, negative_bank=None):
         """InfoNCE loss + regulariser on the scores of ``kind`` and d loss / d (predicted_z, targets), into dpred and rows [T-K, T) of
         the top-layer gradient.  The stages, in order:
           selection   select_negatives: checked and normalised before anything of the engine but B is read
           operands    as they are; "normalized": the rows over their norms, predictions also over the temperature (_norm_operands)
-          scores      _scores: score GEMM(s) or cpc_diff_scores
-          loss        _nce_loss: dense, sampled, grouped or all-timesteps kernel ("linear" scores for every kind but "softplus", as
+          bank        ("banked") the operands go into the bank's slot cur (_bank_store); a bank without earlier steps is then the
+                      whole-batch selection: that step runs the very launches of a call without a bank
+          scores      _scores: score GEMM(s) or cpc_diff_scores; "banked": one score GEMM over the ring's rows (_bank_scores)
+          loss        _nce_loss: dense, sampled, grouped, banked or all-timesteps kernel ("linear" scores for every kind but "softplus", as
                       contrastive_estimation_training._InfoNCE does); or scores and loss in one, _nce_all_fused, where
                       fused_scores_ok() holds
           fix-up      "difference": _diff_coefficients
-          gradients   the linear score's two contractions, _score_grads / _score_grads_all
+          gradients   the linear score's two contractions, _score_grads / _score_grads_all ("banked": the second one reduces over the
+                      ring's rows, and nothing flows into the bank)
           operands'   "difference": the rank-1 terms (_diff_rank1); "normalized": cpc_norm_rows_bwd, in place (_norm_backward)
           backward
         All on the current stream: the target-row lane of backward() starts from those rows behind the event it records there.
         ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward)."""
-        selection = select_negatives(self.B, negatives, negative_groups, all_timesteps)
+        selection = select_negatives(self.B, negatives, negative_groups, all_timesteps, None, negative_bank, kind, temperature)
         pred, top, dpred, dtop = self.pred, self.act[-1], self.dpred, self.dact[-1]
         if kind == "normalized":
             if isinstance(temperature, DeviceTemperature):
                 temperature.dots = self._norm_dots()
             pred, top = self._norm_operands(temperature, tick=True)
         softplus = 1 if kind == "softplus" else 0
+        bank = None
+        if selection is not None and selection[0] == "banked":
+            bank = selection[1]
+            self._bank_store(bank, pred)
+            if bank.filled == 0:
+                selection = None
         if all_timesteps and kind != "difference" and self.fused_scores_ok():
             self._nce_all_fused(softplus, regularization, pred, top)
+        elif selection is not None and selection[0] == "banked":
+            S, dS = self._bank_buffers(bank)
+            self._bank_scores(bank, top, S)
+            self._nce_loss(S, None, dS, self.dST, softplus, regularization, selection, False)
+            rows = bank.slots * self.B
+            self._score_grads(dS, self.dST, bank.ring, top, dpred, dtop, rows=rows, nsplit=self._bank_nsplit(rows))
         else:
             S, ST, dS, dST = self._loss_buffers(all_timesteps, transposed=kind == "difference")
             self._scores(kind, all_timesteps, pred, top, S, ST)
@@ -888,6 +998,48 @@ class CPCEngine:
             self._diff_rank1(pred, top, dpred, dtop)
         elif kind == "normalized":
             self._norm_backward(temperature, pred, top, dpred, dtop)
+        if bank is not None:
+            bank.advance()
+
+    # ---- negative bank (NegativeBank; include/cpc_hip.h, cpc_nce_loss_banked) ----
+    def _bank_store(self, bank, pred):
+        """This step's score operands (shaped like self.pred) into slot cur of the bank, which is allocated here on first use."""
+        bank.bind(self.B, self.K, self.E, self.dt, self.device)
+        bank.slot(bank.cur).view(-1).copy_(pred.view(-1))
+
+    def _bank_buffers(self, bank):
+        """(S, dS) [K][slots B][ldS] of the banked loss and its workspace nce_banked_ws, allocated on first use per ring size."""
+        b = getattr(self, "_bank_bufs", None)
+        if b is None or b.slots != bank.slots:
+            n = self.K * bank.slots * self.B * self.ldS
+            b = self._bank_bufs = SimpleNamespace(
+                slots=bank.slots, S=torch.zeros(n, device=self.device, dtype=torch.float32),
+                dS=torch.zeros(n, device=self.device, dtype=self.dt))
+            self.nce_banked_ws = torch.empty(int(_hip.lib().cpc_nce_banked_workspace_floats(self.B, self.K, bank.slots)),
+                                             device=self.device, dtype=torch.float32)
+        return b.S, b.dS
+
+    def _bank_nsplit(self, rows):
+        """Slabs of the target contraction over the ring's ``rows``: its output is B x E per step k (96 tiles at the headline size),
+        so a reduction of thousands of rows sits on few workgroups.  Measured on an MI355X at B = 256, K = 12, E = 512 (DESIGN.md,
+        "Negative bank"): bf16 storage gains from 1280 rows on with slabs of about 512 rows (direct 35.8 / 95.8 us at 1280 / 4352 rows,
+        slabs 20.0 / 37.9 us + the cast) and loses at 512 rows; f32 storage gains from 512 rows on, most with eight slabs.  No slab
+        is ever empty: _chunk rounds a slab's rows up, so the count comes down until the last slab still starts inside the rows."""
+        if self.dt == torch.bfloat16:
+            n = rows // 512 if rows >= 1024 else 1
+        else:
+            n = rows // 64 if rows >= 512 else 1
+        n = max(1, min(8, n))
+        while n > 1 and (n - 1) * self._chunk(rows, n) >= rows:
+            n -= 1
+        return n
+
+    def _bank_scores(self, bank, top, S):
+        """score_gemm with the ring as the left operand: S[k][slot B + b][b'] = <ring[slot B + b][k], targets[b'][:, k]>."""
+        code, B, E, K = self.code, self.B, self.E, self.K
+        Ltop, T, ld, N = self.geo.alloc[-1], self.T, self.ldS, bank.slots * self.B
+        _hip.gemm_nt(_hip.ptr(bank.ring), _hip.ptr(top, (T - K) * E), _hip.ptr(S), N, B, E, K * E, Ltop * E, ld, code,
+                     a_batch=E, b_batch=E, c_batch=N * ld, batch=K, flags=_hip.GEMM_OUT_F32)
 
     def _scores(self, kind: str, all_timesteps: bool, pred, top, S, ST=None):
         """The scores of a kind and a branch into S and, unless None, their transpose into ST, from operands in the layouts of
@@ -906,8 +1058,9 @@ class CPCEngine:
 
     def _nce_loss(self, S, ST, dS, dST, softplus: int, regularization: float, selection, all_timesteps: bool):
         """Exactly one loss kernel on formed scores: cpc_nce_loss_all, or by ``selection`` (select_negatives) cpc_nce_loss,
-        cpc_nce_loss_sampled or cpc_nce_loss_grouped — same buffers and layouts; the workspaces of the last two are allocated on
-        first use.  Leaves the loss values in nce_out and the coefficients g = d loss / d score in dS and, transposed, dST."""
+        cpc_nce_loss_sampled, cpc_nce_loss_grouped — same buffers and layouts; the workspaces of the last two are allocated on
+        first use — or cpc_nce_loss_banked (S, dS over the ring's rows from _bank_buffers, dST the current slot's).  Leaves the loss
+        values in nce_out and the coefficients g = d loss / d score in dS and, transposed, dST."""
         B, K, code, P, U = self.B, self.K, self.code, _hip.ptr, C.c_ulonglong
         out, reg = P(self.nce_out), C.c_float(regularization)
         if all_timesteps:
@@ -921,6 +1074,10 @@ class CPCEngine:
             _, n_neg, seed, draw = selection
             _hip.call("cpc_nce_loss_sampled", P(S), P(dS), P(dST), out, P(self.nce_sampled_ws), B, K, self.ldS, softplus, reg,
                       n_neg, U(seed), U(draw), code)
+        elif selection[0] == "banked":
+            bank = selection[1]
+            _hip.call("cpc_nce_loss_banked", P(S), P(dS), P(dST), out, P(self.nce_banked_ws), B, K, self.ldS, bank.slots, bank.cur,
+                      U(bank.valid), softplus, reg, code)
         else:
             if getattr(self, "nce_grouped_ws", None) is None:
                 self.nce_grouped_ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(B, K)), device=self.device,
@@ -929,17 +1086,34 @@ class CPCEngine:
             _hip.call("cpc_nce_loss_grouped", P(S), P(dS), P(dST), out, P(self.nce_grouped_ws), B, K, self.ldS, softplus, reg,
                       P(groups), mode, n_neg, U(seed), U(draw), code)
 
-    def _score_grads(self, W, WT, pred, top, out_pred, out_top):
+    def _score_grads(self, W, WT, pred, top, out_pred, out_top, rows=None, nsplit=1):
         """The two contractions behind d loss / d (predicted_z, targets) of the default branch, for any coefficients W[k][b][b']
-        (WT: its transpose per k) and operands in the layouts of ``self.pred`` / the top-layer buffer."""
+        (WT: its transpose per k) and operands in the layouts of ``self.pred`` / the top-layer buffer.  ``rows``: the prediction rows
+        of W and ``pred`` where they are more than B (the banked loss: W [k][rows][b'], ``pred`` the ring, WT of the current slot);
+        ``nsplit`` > 1 (_bank_nsplit) splits that long reduction into f32 slabs [nsplit][B][K][E], summed in slab order by one
+        cpc_reduce_slabs — straight into the target rows in f32 storage, through an f32 [B][K][E] sum and one strided cast in bf16."""
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
+        rows = B if rows is None else rows
         # out_pred[b][k][:] = sum_b' W[k][b][b'] * targets[b'][k][:]
         _hip.gemm_tn(_hip.ptr(WT), _hip.ptr(top, (T - K) * E), _hip.ptr(out_pred), B, B, E, ld, Ltop * E, K * E, code,
                      a_batch=B * ld, b_batch=E, c_batch=E, batch=K)
         # out_top rows T-K+k of item b' = sum_b W[k][b][b'] * predicted_z[b][k][:]
-        _hip.gemm_tn(_hip.ptr(W), _hip.ptr(pred), _hip.ptr(out_top, (T - K) * E), B, B, E, ld, K * E, Ltop * E, code,
-                     a_batch=B * ld, b_batch=E, c_batch=E, batch=K)
+        if nsplit == 1:
+            _hip.gemm_tn(_hip.ptr(W), _hip.ptr(pred), _hip.ptr(out_top, (T - K) * E), rows, B, E, ld, K * E, Ltop * E, code,
+                         a_batch=rows * ld, b_batch=E, c_batch=E, batch=K)
+            return
+        n = B * K * E
+        if getattr(self, "_tn_slabs", None) is None or self._tn_slabs.numel() < (nsplit + 1) * n:
+            self._tn_slabs = torch.empty((nsplit + 1) * n, device=self.device, dtype=torch.float32)          # slabs + their sum
+        slabs, L = self._tn_slabs, C.c_longlong
+        _hip.gemm_tn(_hip.ptr(W), _hip.ptr(pred), _hip.ptr(slabs), rows, B, E, ld, K * E, K * E, code, a_batch=rows * ld, b_batch=E,
+                     c_batch=E, batch=K, nsplit=nsplit, m_chunk=self._chunk(rows, nsplit), slab_stride=n, flags=_hip.GEMM_OUT_F32)
+        if self.dt == torch.float32:
+            _hip.call("cpc_reduce_slabs", _hip.ptr(slabs), _hip.ptr(out_top, (T - K) * E), B, K * E, nsplit, L(n), 1, L(1), L(Ltop * E), L(0))
+        else:
+            _hip.call("cpc_reduce_slabs", _hip.ptr(slabs), _hip.ptr(slabs, nsplit * n), B, K * E, nsplit, L(n), 1, L(1), L(K * E), L(0))
+            out_top[:B * Ltop * E].view(B, Ltop, E)[:, T - K:T, :].copy_(slabs[nsplit * n:(nsplit + 1) * n].view(B, K, E))
 
     def _score_grads_all(self, W, WT, pred, top, out_pred, out_top):
         """The same for the all-timesteps branch: W [(b,k)][(b',k')] and its transpose.
@@ -1379,7 +1553,7 @@ class CPCEngine:
     # ------------------------------------------------------------------------------------------ whole step
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
                        global_negatives=None, after_loss=None, score: Optional[str] = None, negatives=None, negative_groups=None,
-                       temperature=None):
+                       temperature=None, negative_bank=None):
         """Forward + loss + backward; returns the device tensor [loss, max_score, -mean valid, mean lse, reg, NaN indicator of
         this step, sticky NaN flag, -] (no sync; include/cpc_hip.h, cpc_nce_loss).
         ``global_negatives``: a GlobalNegatives object — the loss is then taken over the batches of ALL ranks.
@@ -1388,10 +1562,13 @@ class CPCEngine:
         ``score``: "softplus" | "linear" | "difference" | "normalized" (score_kind; None: the ``softplus`` flag decides).
         ``temperature``: the temperature of "normalized" scores (finite and > 0; required there, a ValueError with any other kind).
         ``negatives``: None, or (n_neg, seed, draw): n_neg seeded negatives per target (nce_forward_backward); default branch only.
-        ``negative_groups``: None, or (groups, mode): candidates by group id (nce_forward_backward); default branch only."""
+        ``negative_groups``: None, or (groups, mode): candidates by group id (nce_forward_backward); default branch only.
+        ``negative_bank``: None, or a NegativeBank: earlier steps' predictions as further candidates (nce_forward_backward); default
+        branch only."""
         kind = score_kind(softplus, score)
         temperature = check_temperature(temperature, kind)
-        select_negatives(self.B, negatives, negative_groups, all_timesteps, global_negatives)          # refused before forward() runs
+        select_negatives(self.B, negatives, negative_groups, all_timesteps, global_negatives, negative_bank, kind,
+                         temperature)          # refused before forward() runs
         if kind == "difference" and global_negatives is not None:
             raise NotImplementedError("difference scores under global negatives are not on the HIP path: the trainer takes the generic "
                                       "route there (contrastive_estimation_training.difference_score_function)")
@@ -1405,6 +1582,8 @@ class CPCEngine:
         elif all_timesteps:
             self.nce_all_forward_backward(softplus, regularization, score=kind, **tkw)
         else:
+            if negative_bank is not None:          # (without one nce_forward_backward is called as before the keyword existed)
+                tkw["negative_bank"] = negative_bank
             self.nce_forward_backward(softplus, regularization, score=kind, negatives=negatives, negative_groups=negative_groups, **tkw)
         if after_loss is not None:
             after_loss(self.nce_out)
@@ -3299,8 +3478,11 @@ class GraphedStep:
     (dropout seeds)."""
 
     def __init__(self, eng, opt, softplus: bool, regularization: float, all_timesteps: bool = False, score: Optional[str] = None,
-                 negatives=None, negative_groups=None, temperature=None):
+                 negatives=None, negative_groups=None, temperature=None, negative_bank=None):
         temperature = check_temperature(temperature, score_kind(softplus, score))
+        # (the trainer refuses use_graph with a bank before it gets here: the keyword exists for direct callers, so that they get the
+        # reason instead of a TypeError)
+        check_negative_bank_supported(negative_bank, graphed=True)
         if negative_groups is not None:
             raise NotImplementedError("grouped negatives take the group ids of each step's batch from the host, which a captured graph "
                                       "cannot replay")

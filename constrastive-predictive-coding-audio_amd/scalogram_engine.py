@@ -16,8 +16,8 @@ from typing import List, Optional
 import torch
 
 from . import _hip, switches
-from .engine import (CPCEngine, Float32Context, _ceil_div, check_negatives_supported, check_temperature, make_context, score_kind,
-                     side_stream)
+from .engine import (CPCEngine, Float32Context, _ceil_div, check_negative_bank_supported, check_negatives_supported, check_temperature,
+                     make_context, score_kind, side_stream)
 
 
 class Grid:
@@ -1425,11 +1425,13 @@ class ScalogramCPCEngine(CPCEngine):
     # ------------------------------------------------------------------ Wasserstein gradient penalty
     def loss_and_grads(self, x, softplus: bool, regularization: float, all_timesteps: bool = False, grad_ready_hook=None,
                        global_negatives=None, after_loss=None, gradient_penalty=None, score: Optional[str] = None, negatives=None,
-                       negative_groups=None, temperature=None):
+                       negative_groups=None, temperature=None, negative_bank=None):
         check_negatives_supported(negatives, all_timesteps, global_negatives, gradient_penalty, negative_groups=negative_groups)
+        check_negative_bank_supported(negative_bank, all_timesteps, global_negatives, gradient_penalty, negatives, negative_groups)
         if gradient_penalty is None:
             return super().loss_and_grads(x, softplus, regularization, all_timesteps, grad_ready_hook, global_negatives, after_loss,
-                                          score=score, negatives=negatives, negative_groups=negative_groups, temperature=temperature)
+                                          score=score, negatives=negatives, negative_groups=negative_groups, temperature=temperature,
+                                          negative_bank=negative_bank)
         check_temperature(temperature, score_kind(softplus, score))
         if score_kind(softplus, score) in ("difference", "normalized"):
             raise NotImplementedError("the gradient penalty covers linear_score_function / softplus_score_function; see DESIGN.md section 8")

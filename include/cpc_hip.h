@@ -63,6 +63,8 @@ extern "C" {
  *    Added later under 9 (backward compatible, no entry point changed): the exponential moving average of the weights cpc_ema,
  *    cpc_ema_swap; the temperature in device memory cpc_norm_rows_dev, cpc_norm_rows_bwd_dev, cpc_temperature_step, cpc_temperature_set.
  *    Added later under 9 (backward compatible, no entry point changed): cpc_gemm_nt_bits, cpc_gemm_nt_debug_flags.
+ *    Added later under 9 (backward compatible, no entry point changed): the loss over a bank of earlier predictions
+ *    cpc_nce_banked_workspace_floats, cpc_nce_loss_banked.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -650,6 +652,27 @@ int cpc_nce_loss_grouped(const float* S, void* dS, void* dST, float* out, float*
                          int dtype, void* stream);
 int cpc_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
                        unsigned long long draw, void* stream);
+
+/* cpc_nce_loss with the predictions of earlier steps as further candidates (not in the reference; DESIGN.md, "Negative bank").
+ * 2 <= slots <= 64 ring slots of B prediction rows each, N = slots B; sp = f(S), f the identity or softplus; V the rows of the slots
+ * whose bit is set in valid_mask (bit cur always; no bit at or above slots):
+ *   S[k][r][b'] = < R[r][k][:], targets[b'][:, k] >,  r in [0, N)          (f32, [K][N][ld], B <= ld <= B + 7, formed by the caller)
+ *   loss = -mean_{b',k} sp[k][cur B + b'][b'] + mean_{k,b'} logsumexp_{r in V} sp[k][r][b']
+ *          + reg mean_{b,b'} (mean_k sp[k][cur B + b][b'])^2                                         (current slot only, as cpc_nce_loss)
+ *   dsp[k][r][b'] = [r in V] exp(sp - lse[k][b']) / (B K) - [r == cur B + b'] / (B K) + [r in slot cur] 2 reg / (B^2 K) mean_k sp[k][r][b']
+ *   dS[k][r][b'] = dsp f'(S)  (T, [K][N][ld]);  dST_cur[k][b'][b] = dS[k][cur B + b][b']  (T, [K][B][ld], cpc_nce_loss's dST)
+ * The rows of invalid slots are WRITTEN as zero coefficients by every call, and the pad columns [B, ld) of dS and dST_cur get zeros, so
+ * that GEMMs may run over all N rows and ld columns; the scores of invalid slots are never read.  out[8] as cpc_nce_loss: the max
+ * score, the valid scores and the pair means run over slot cur; a NaN among the scores of any valid slot reaches out[0] and raises
+ * out[5] / out[6].  With valid_mask == 1 << cur the loss, out[] and the coefficients of slot cur are cpc_nce_loss's (other summation
+ * order of the log-sum-exp).  No atomics; the summation order is fixed by B and slots alone.
+ * workspace: cpc_nce_banked_workspace_floats(B, K, slots) f32, 8-byte aligned (it starts with 8-byte pairs).
+ * Limits: 2 <= B <= 1024, 1 <= K <= 1024; CPC_EINVAL otherwise and for slots outside [2, 64], cur outside [0, slots), a valid_mask without
+ * bit cur or with a bit at or above slots, ld outside [B, B + 7], a null pointer, a dtype other than f32 / bf16 and a workspace that
+ * is not 8-byte aligned — before any launch: a refused call writes nothing. */
+long long cpc_nce_banked_workspace_floats(int B, int K, int slots);
+int cpc_nce_loss_banked(const float* S, void* dS, void* dST_cur, float* out, float* workspace, int B, int K, int ld, int slots, int cur,
+                        unsigned long long valid_mask, int softplus, float regularization, int dtype, void* stream);
 
 /* Wasserstein gradient penalty with softplus_score_function (contrastive_estimation_training.py:12-16 under :144-158): the
  * coefficients the penalty's seeds carry.  S (and the tangent scores St1 + St2, St2 may be NULL): nmat f32 matrices [rows][ld].

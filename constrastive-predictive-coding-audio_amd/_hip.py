@@ -74,6 +74,14 @@ class GemmTNArgs(C.Structure):
                 ("flags", C.c_int), ("dtype", C.c_int), ("c_rpi", C.c_int), ("c_item", C.c_longlong), ("a_rpi2", C.c_int), ("a_item2", C.c_longlong)]
 
 
+class CpcWaveAugment(C.Structure):
+    """cpc_wave_augment's configuration (include/cpc_hip.h, cpc_wave_augment_cfg)."""
+    _fields_ = [("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("clip_offset", C.c_ulonglong), ("protect_from", C.c_int),
+                ("q_lo", C.c_int), ("q_hi", C.c_int), ("drop_count", C.c_int), ("drop_max_len", C.c_int),
+                ("noise_on", C.c_int), ("snr_lo", C.c_float), ("snr_hi", C.c_float),
+                ("gain_on", C.c_int), ("gain_lo_db", C.c_float), ("gain_hi_db", C.c_float), ("polarity_threshold", C.c_ulonglong)]
+
+
 _P, _I, _L, _F, _D, _U64, _U32 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_uint
 _SIGNATURES = {
     "cpc_abi_version": ([], _I),
@@ -210,6 +218,9 @@ _SIGNATURES = {
     "cpc_lamb": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _P, _L, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
     "cpc_ema": ([_P, _P, _L, _F, _I, _I, _P, _P, _P], _I),
     "cpc_ema_swap": ([_P, _P, _L, _P], _I),
+    "cpc_wave_power_chunks": ([_I], _I),
+    "cpc_wave_power": ([_P, _P, _I, _I, _L, _I, _P], _I),
+    "cpc_wave_augment": ([_P, _P, _P, _P, _I, _I, _L, _L, C.POINTER(CpcWaveAugment), _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

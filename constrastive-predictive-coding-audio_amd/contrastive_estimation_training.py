@@ -550,6 +550,16 @@ class ContrastiveEstimationTrainer:
         # value behind the latest step read back; every step's value goes to logger.temperature_meter where the logger has one.
         self._temperature = None
         self.last_temperature = None
+        # Not in the reference's signature: waveform augmentation in the time domain ("Waveform augmentation").
+        # augmentation: None, or an augmentation.WaveAugmentation — batch i of a train() call reaches the model, the engine or the
+        #   preprocessing module as aug(batch, step = continue_training_at_step + i, clip_offset = rank * batch_size), so that a
+        #   resumed run and every rank of a data-parallel run draw what one uninterrupted single-process run draws;
+        # augment_targets: False leaves bit for bit every sample the prediction_steps target frames depend on (the augmentation
+        #   then acts on the past only); it needs AudioEncoder's geometry, so not a preprocessing module in front of the encoder.
+        # Not with use_graph (the step number is a host-side launch argument).  validate(), calc_test_task_data() and test_task
+        # never augment.
+        self.augmentation = None
+        self.augment_targets = True
         self._ema = None          # the shadow: a flat f32 tensor shaped like model._flat_param
         self._ema_owner = None    # who updates it at present: the latest train() call's FusedAdam or TorchEma
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
@@ -833,6 +843,46 @@ class ContrastiveEstimationTrainer:
             sf.device_temperature = kept
         return kept
 
+    def _check_augmentation(self):
+        """None without augmentation; else (the WaveAugmentation, protect(L) -> the first protected sample of clips of L samples).
+        TypeError for anything but a WaveAugmentation, NotImplementedError with use_graph, ValueError for augment_targets=False
+        on a model whose encoder does not give the frame geometry of the waveform."""
+        aug = self.augmentation
+        if aug is None:
+            return None
+        from .augmentation import WaveAugmentation
+        if not isinstance(aug, WaveAugmentation):
+            raise TypeError(f"augmentation must be None or an augmentation.WaveAugmentation, got {type(aug).__name__}")
+        if self.use_graph:
+            raise NotImplementedError("augmentation: use_graph replays one captured step, but the augmentation's step number is a "
+                                      "host-side launch argument that changes every step")
+        if self.augment_targets:
+            return aug, lambda L: None
+        from .audio_model import AudioEncoder
+        enc = getattr(self.model, "encoder", None)
+        if self.preprocessing is not None or not isinstance(enc, AudioEncoder):
+            raise ValueError("augment_targets=False needs the frame geometry of the waveform (AudioEncoder's receptive_field and "
+                             "downsampling_factor): not available for a scalogram encoder behind a preprocessing module")
+        field, hop, K = int(enc.receptive_field), int(enc.downsampling_factor), int(self.model.prediction_steps)
+
+        def protect(L):
+            T = (int(L) - field) // hop + 1
+            if L < field or T <= K:
+                raise ValueError(f"augment_targets=False: clips of {int(L)} samples give {max(T, 0)} frames, not more than the "
+                                 f"{K} target frames")
+            return hop * (T - K)          # the first sample of frame T - K: everything the K target frames read
+        return aug, protect
+
+    @staticmethod
+    def _augmented(batches, aug, protect, counter, clip_offset, with_indices):
+        """The batches of ``batches`` augmented: batch i of the run (counter[0], which goes on over the epochs) at step i.  Every
+        output is a fresh tensor, so the one in hand stays valid while the following batch is prepared."""
+        for item in batches:
+            batch = item[0] if with_indices else item
+            out = aug(batch, counter[0], clip_offset=clip_offset, protect_from=protect(batch.shape[1]))
+            counter[0] += 1
+            yield (out, item[1]) if with_indices else out
+
     @staticmethod
     def _world():
         import torch.distributed as dist
@@ -903,6 +953,8 @@ class ContrastiveEstimationTrainer:
         self._check_negatives(batch_size)
         grouping = self._check_negative_groups()
         bank_kw = self._bank_kw(self._check_negative_bank())
+        augmenting = self._check_augmentation()
+        aug_counter = [int(continue_training_at_step)]          # the step of the next batch the augmentation sees
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
         trust_ratio, trust_clip = self._check_trust()
@@ -1120,6 +1172,9 @@ class ContrastiveEstimationTrainer:
                     ahead = InputAhead(self._model_input, device)
                 batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world,
                                         with_indices=grouping is not None)
+                if augmenting is not None:          # in front of everything that sees a batch, the one preprocessed ahead included
+                    batches = self._augmented(batches, augmenting[0], augmenting[1], aug_counter, rank * int(batch_size),
+                                              grouping is not None)
                 # (the sampler is read one batch ahead only where that batch is preprocessed ahead)
                 for batch, next_batch in (_with_next(batches) if ahead is not None else ((b_, None) for b_ in batches)):
                     groups_kw = {}

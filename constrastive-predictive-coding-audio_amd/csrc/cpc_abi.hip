@@ -892,4 +892,28 @@ int cpc_ema(const float* p, float* ema, long long n, float decay, int warmup, in
 
 int cpc_ema_swap(float* p, float* ema, long long n, void* stream) { return launch_ema_swap(p, ema, n, (hipStream_t)stream); }
 
+int cpc_wave_power_chunks(int n) { return wave_power_chunks(n); }
+
+// (the shape checks shared by cpc_wave_power and cpc_wave_augment; blockIdx.y carries the clip, f32 carries sample indices)
+static bool wave_shape_ok(int B, int L, long long ld) { return B >= 1 && B <= 65535 && L >= 1 && L <= (1 << 24) && ld >= L; }
+
+int cpc_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, void* stream) {
+    if (!x || !partial || !wave_shape_ok(B, L, ldx) || n < 1 || n > L) return CPC_EINVAL;
+    return launch_wave_power(x, partial, B, L, ldx, n, (hipStream_t)stream);
+}
+
+int cpc_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
+                     const CpcWaveAugment* cfg, void* stream) {
+    if (!x || !y || !cfg || !wave_shape_ok(B, L, ldx) || ldy < L) return CPC_EINVAL;
+    if (cfg->protect_from < 0 || cfg->protect_from > L) return CPC_EINVAL;
+    if (cfg->q_lo < 32768 || cfg->q_lo > cfg->q_hi || cfg->q_hi > 131072) return CPC_EINVAL;
+    if (cfg->drop_count < 0 || cfg->drop_count > 8 || (cfg->drop_count > 0 && cfg->drop_max_len < 1)) return CPC_EINVAL;
+    if (cfg->noise_on && (!partial || !std::isfinite(cfg->snr_lo) || !std::isfinite(cfg->snr_hi) || cfg->snr_lo > cfg->snr_hi))
+        return CPC_EINVAL;
+    if (cfg->gain_on && (!std::isfinite(cfg->gain_lo_db) || !std::isfinite(cfg->gain_hi_db) || cfg->gain_lo_db > cfg->gain_hi_db))
+        return CPC_EINVAL;
+    if (cfg->polarity_threshold > (1ull << 32)) return CPC_EINVAL;
+    return launch_wave_augment(x, y, partial, params_out, B, L, ldx, ldy, cfg, (hipStream_t)stream);
+}
+
 }  // extern "C"

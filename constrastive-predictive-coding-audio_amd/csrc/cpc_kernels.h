@@ -225,6 +225,12 @@ int launch_lamb(const AdamArgs& a, int step, const LambTables& t, hipStream_t st
 int launch_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
                hipStream_t stream);
 int launch_ema_swap(float* p, float* ema, long long n, hipStream_t stream);
+// Waveform augmentation (augment.hip): the per-chunk sums of squares and the apply pass; arguments checked by the entry points.
+struct cpc_wave_augment_cfg;
+int wave_power_chunks(int n);
+int launch_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, hipStream_t stream);
+int launch_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
+                        const cpc_wave_augment_cfg* cfg, hipStream_t stream);
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
                       hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);

@@ -65,6 +65,8 @@ extern "C" {
  *    Added later under 9 (backward compatible, no entry point changed): cpc_gemm_nt_bits, cpc_gemm_nt_debug_flags.
  *    Added later under 9 (backward compatible, no entry point changed): the loss over a bank of earlier predictions
  *    cpc_nce_banked_workspace_floats, cpc_nce_loss_banked.
+ *    Added later under 9 (backward compatible, no entry point changed): waveform augmentation cpc_wave_power_chunks, cpc_wave_power,
+ *    cpc_wave_augment.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -949,6 +951,62 @@ int cpc_lamb(float* p, const float* g, float* m, float* v, long long n, float lr
 int cpc_ema(const float* p, float* ema, long long n, float decay, int warmup, int step, const float* state, const float* skip,
             void* stream);
 int cpc_ema_swap(float* p, float* ema, long long n, void* stream);
+
+
+/* Waveform augmentation in the time domain (not in the reference; DESIGN.md, "Waveform augmentation"): speed change, time drop,
+ * additive noise, gain and polarity on the first protect_from samples of every clip of an f32 batch x[B][ldx] (L valid samples per
+ * row), written to a separate buffer y[B][ldy]; x and y must not overlap.
+ *
+ * Randomness is counter-based, with the arithmetic of the sampled negatives (modulo 2^64):
+ *   mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *   kb   = mix(seed + 0x632BE59BD9B4E019 * step + 0x9E3779B97F4A7C15 * (clip + 1)),  clip = clip_offset + b
+ *   u_f  = mix(kb + 0xD1B54A32D192ED03 * f) >> 32                        field f of a clip, a u32
+ *   integer draw in [lo, hi]:  lo + ((u_f * (hi - lo + 1)) >> 32)        (64-bit product)
+ *   real draw in [lo, hi]:     fma(hi - lo, float(u_f) * 2^-32, lo)      (f32)
+ * a = protect_from.  Samples n >= a are copied bit for bit; every stage acts on n < a, in this order, and a stage that is off
+ * performs no arithmetic on the samples (all off: y == x bitwise).  With a == 0 nothing is drawn: q = 65536, no span, sigma = 0.
+ *   speed     (field 1)  q in [q_lo, q_hi], Q16; q_lo == q_hi == 65536 is off.  pos = a * 65536 - (a - n) * q (64-bit integers),
+ *             i = pos >> 16 (floor), t = (pos & 0xFFFF) * 2^-16, v = sum_j w_j(t) x[i + j], j = -1 .. 2, x = 0 outside [0, L), with
+ *             the Catmull-Rom weights w_-1 = ((-t + 2) t - 1) t / 2, w_0 = ((3 t - 5) t^2 + 2) / 2, w_1 = ((-3 t + 4) t + 1) t / 2,
+ *             w_2 = (t - 1) t^2 / 2, evaluated in the factored forms -t u^2 / 2, u (2 + t (2 - 3 t)) / 2, t (1 + t (4 - 3 t)) / 2,
+ *             -u t^2 / 2 with u = 1 - t (no cancellation: every weight carries at most two roundings), and summed as one
+ *             multiply and three fmas, j ascending.  No low-pass filter in front of a speed-up: meant for |q / 65536 - 1| <= 0.25.
+ *   time drop (fields 8 + 2 d and 9 + 2 d, d < drop_count <= 8)  len_d in [1, min(drop_max_len, a)] from field 8 + 2 d, start_d in
+ *             [0, a - len_d] from field 9 + 2 d; v = 0.0f for n in [start_d, start_d + len_d).  Spans may overlap.
+ *   noise     (field 2)  snr_db in [snr_lo, snr_hi], sigma = sqrtf(P) * exp2f(-snr_db * (log2(10) / 20)), P = (sum of partial[b][.]
+ *             in index order) / float(a): the mean square of the ORIGINAL x[b][0 .. a) as cpc_wave_power left it.
+ *             v = fma(sigma, g(n), v), g(n) = float(s - 131070) * float(sqrt(3) / 65536), s = the sum of the four 16-bit fields of
+ *             mix(kb + 0xD1B54A32D192ED03 * (32 + n)): mean 0, variance 1, |g| <= 3.47.  Dropped spans hold noise only.
+ *   gain      (field 3)  db in [gain_lo_db, gain_hi_db], gain = exp2f(db * (log2(10) / 20)); v = v * gain.
+ *   polarity  (field 4)  the sign flips when u_4 < polarity_threshold (probability * 2^32; 0 = off, 2^32 = always): with the gain
+ *             on, v = v * (-gain); with it off, v = -v.
+ * cpc_wave_power: partial[b][c] = the sum of squares of x[b][4096 c .. min(4096 (c + 1), n)), c < cpc_wave_power_chunks(n) =
+ *   ceil(n / 4096) (0 for n < 1), rows of partial that many floats apart.  One workgroup per (b, c); thread t of 256 runs one fma
+ *   chain over elements 4 (256 p + t) + j, p = 0 .. 3 outer, j = 0 .. 3 inner, then an xor-shuffle butterfly over the wave and
+ *   (w0 + w1) + (w2 + w3) over the four waves: one fixed order whatever the alignment of the rows, no atomics.
+ *   CPC_EINVAL: x or partial NULL, B outside [1, 65535], L outside [1, 2^24], ldx < L, n outside [1, L].
+ * cpc_wave_augment: one launch (after cpc_wave_power(x, partial, B, L, ldx, protect_from) where the noise is on and
+ *   protect_from >= 1).  params_out NULL or f32 [B][8]: per clip q, sigma, the signed gain, P, start_0, len_0, start_1, len_1 as the
+ *   device drew them (0 for what is off or not drawn, gain +-1 with the gain off; integers up to 2^24 are exact in f32).  16-byte
+ *   loads / stores where the row starts and leading dimensions allow, scalar ones otherwise; the same bits either way.
+ *   CPC_EINVAL before any launch: x, y or cfg NULL, partial NULL with noise_on, B outside [1, 65535], L outside [1, 2^24], ldx < L or
+ *   ldy < L, protect_from outside [0, L], not 32768 <= q_lo <= q_hi <= 131072, drop_count outside [0, 8], drop_max_len < 1 with
+ *   drop_count > 0, snr_lo > snr_hi or either not finite with noise_on, gain_lo_db > gain_hi_db or either not finite with gain_on,
+ *   polarity_threshold > 2^32.
+ * Neither call throws, allocates or synchronises. */
+typedef struct cpc_wave_augment_cfg {
+    unsigned long long seed, step, clip_offset;
+    int protect_from;
+    int q_lo, q_hi;
+    int drop_count, drop_max_len;
+    int noise_on; float snr_lo, snr_hi;
+    int gain_on; float gain_lo_db, gain_hi_db;
+    unsigned long long polarity_threshold;
+} CpcWaveAugment;
+int cpc_wave_power_chunks(int n);
+int cpc_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, void* stream);
+int cpc_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
+                     const CpcWaveAugment* cfg, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,28 @@ __device__ __forceinline__ float score_grad(float x, int softplus) {
     return x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
 }
 
+// The block reduction of this file: N values per thread of a 256-thread workgroup, the first NSUM of them summed and the rest
+// maximised, through red[N][256].  A fixed tree, strides 128 down to 1, the lower index taking the upper: the result depends on the
+// values alone, never on timing.  Called by all 256 threads; every thread may read the results red[i][0] afterwards, and has to pass
+// a barrier of its own before it writes red again.
+template <int N, int NSUM = N>
+__device__ __forceinline__ void block_reduce(float (&red)[N][256], const float (&v)[N]) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[i][t] = v[i];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                if (i < NSUM) red[i][t] += red[i][t + s];
+                else red[i][t] = fmaxf(red[i][t], red[i][t + s]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // logsumexp over b of every (k, b') column.  grid (ceil(B/32), K, nsplit); block 256 = 32 columns x 8 row lanes, each lane keeps
 // an online (max, sum) over its rows of the split's row range, combined through LDS.  With nsplit == 1 it writes lse[k][b'] and
 // one partial sum of lse per block; otherwise the per-split (max, sum) pairs go to pm / ps [split][k][b'] for nce_col_merge_kernel
@@ -96,7 +118,7 @@ __global__ __launch_bounds__(256) void nce_col_kernel(const float* __restrict__ 
 // Merges the per-split (max, sum) pairs of a column in split order: lse[c] and one partial sum of lse per block of 256 columns.
 __global__ __launch_bounds__(256) void nce_col_merge_kernel(const float* __restrict__ pm, const float* __restrict__ ps, int nsplit,
                                                             int ncols, float* __restrict__ lse, float* __restrict__ partial) {
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int c = blockIdx.x * 256 + threadIdx.x;
     float l = 0.f;
     if (c < ncols) {
@@ -111,13 +133,8 @@ __global__ __launch_bounds__(256) void nce_col_merge_kernel(const float* __restr
         l = m + logf(tot);
         lse[c] = l;
     }
-    red[threadIdx.x] = l;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    block_reduce<1>(red, {l});
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0][0];
 }
 
 // m[b][b'] = mean_k sp[k][b][b'] (the regulariser's mean over the prediction steps, contrastive_estimation_training.py:141)
@@ -158,18 +175,7 @@ __device__ __forceinline__ void nce_mean_body(const float* __restrict__ S, float
         msq = m * m;
         mean[(long long)b * ld + bp] = m;
     }
-    red[0][threadIdx.x] = valid;
-    red[1][threadIdx.x] = msq;
-    red[2][threadIdx.x] = mx;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-            red[2][threadIdx.x] = fmaxf(red[2][threadIdx.x], red[2][threadIdx.x + s]);
-        }
-        __syncthreads();
-    }
+    block_reduce<3, 2>(red, {valid, msq, mx});
     if (threadIdx.x == 0) {
         partial[bx * 3 + 0] = red[0][0];
         partial[bx * 3 + 1] = red[1][0];
@@ -202,17 +208,7 @@ __device__ __forceinline__ void nce_finalize_body(const float* __restrict__ col_
         msq += grad_partial[i * 3 + 1];
         mx = fmaxf(mx, grad_partial[i * 3 + 2]);
     }
-    red[0][threadIdx.x] = lse_sum; red[1][threadIdx.x] = valid; red[2][threadIdx.x] = msq; red[3][threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s2];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s2];
-            red[2][threadIdx.x] += red[2][threadIdx.x + s2];
-            red[3][threadIdx.x] = fmaxf(red[3][threadIdx.x], red[3][threadIdx.x + s2]);
-        }
-        __syncthreads();
-    }
+    block_reduce<4, 3>(red, {lse_sum, valid, msq, mx});
     if (threadIdx.x != 0) return;
     lse_sum = red[0][0]; valid = red[1][0]; msq = red[2][0]; mx = red[3][0];
     const float bk = (float)B * (float)K;
@@ -231,43 +227,83 @@ __device__ __forceinline__ void nce_finalize_body(const float* __restrict__ col_
     if (bad != 0.f) out[6] = 1.f;
 }
 
-// One thread per (b, b') pair, 32x32 pairs per block (blockDim = 32x8, 4 rows per thread).
-// Writes dS[k][b][b'] and dST[k][b'][b] (storage dtype T) and per-block partials {sum valid, sum m^2, max sp}.
-// Writes dS[k][b][b'] and dST[k][b'][b] (storage dtype T); grid (tiles, tiles, K).
-// The loss scalars (nce_finalize_body) depend on the partials of the launch before this one only, so workgroup (0, 0, 0) also
+// ---- the gradient tile of the equal-step losses (dense, sampled / grouped, banked) ----
+// What tells these losses apart is a column's candidate set, i.e. the coefficient dsp = d loss / d sp of one (b, b') pair.  A policy
+// P says that much and nce_grad_tile does the rest:
+//   P::column(k, bp)       once per thread before its rows (bp may lie past B): what the pairs of column (k, b') share
+//   P::dsp(k, b, bp, sp)   the coefficient of a pair b, bp < B with transformed score sp
+//   P::live, P::own        workgroup-uniform: the tile's rows have coefficients at all / are rows of the current batch
+// The terms every policy puts its coefficient together from:
+struct NceTerms {
+    const float* lse;           // [K][B] column log-sum-exps over the candidates
+    const float* mean;          // [B][ld] pair means (nce_mean_body)
+    int B, ld;
+    float inv_bk, reg_c;
+};
+__device__ __forceinline__ NceTerms nce_terms(const float* lse, const float* mean, int B, int K, int ld, float reg) {
+    return {lse, mean, B, ld, 1.f / ((float)B * (float)K), 2.f * reg / ((float)B * (float)B * (float)K)};
+}
+
+// every row is a candidate of every column
+struct NceDense : NceTerms {
+    static constexpr bool live = true, own = true;
+    __device__ __forceinline__ void column(int, int) {}
+    __device__ __forceinline__ float dsp(int k, int b, int bp, float sp) const {
+        float dsp = expf(sp - lse[k * B + bp]) * inv_bk + reg_c * mean[(long long)b * ld + bp];
+        if (b == bp) dsp -= inv_bk;
+        return dsp;
+    }
+};
+
+// One 32 x 32 tile of (b, b') pairs of step k = blockIdx.z per workgroup, one thread per pair and trip (blockDim = 32 x 8, 4 rows per
+// thread): rows b0 + 0..31 of the B score rows that start at row row0 of S and dS (k B, or the slot's first row in the ring of the
+// banked loss), columns 32 blockIdx.x + 0..31.  Writes dS[row0 + b][b'] and, for a tile of the current batch, dST[k][b'][b] through
+// LDS (storage dtype T).  Both stores write the zeros of the pad columns [B, ld) as well: the grids have ceil(ld / 32) tiles per
+// side and the fast index of either store is bounded by ld, not by B — where ld reaches into a tile of its own (B = 32, ld = 39)
+// that tile holds no pair at all and exists for those zeros.
+// The loss scalars (nce_finalize_body) depend on the partials of the launches before this one only, so workgroup (0, 0, 0) also
 // does that reduction: no launch of its own.
+template <typename T, typename P>
+__device__ __forceinline__ void nce_grad_tile(const float* __restrict__ S, T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld,
+                                              int softplus, float reg, long long row0, int b0, P pol, const float* __restrict__ colp,
+                                              int ncol, const float* __restrict__ pairp, int npair, float* __restrict__ out) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
+    const int bp0 = blockIdx.x * 32, bp = bp0 + tx;
+    const int k = blockIdx.z;
+    pol.column(k, bp);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = b0 + ty + 8 * r;
+        float g = 0.f;
+        if (pol.live && b < B && bp < B) {
+            const float x = S[(row0 + b) * ld + bp];
+            const float sp = score_tf(x, softplus);
+            g = pol.dsp(k, b, bp, sp) * score_grad(x, softplus);
+        }
+        if (b < B && bp < ld) dS[(row0 + b) * ld + bp] = from_f32<T>(g);
+        tile[ty + 8 * r][tx] = g;
+    }
+    if (pol.own) {
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int bq = bp0 + ty + 8 * r, b = b0 + tx;
+            if (b < ld && bq < B) dST[((long long)k * B + bq) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
+        }
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(colp, ncol, pairp, npair, out, B, K, reg);
+}
+
+// grid (ceil(ld / 32), ceil(ld / 32), K)
 template <typename T>
 __global__ __launch_bounds__(256) void nce_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
                                                        const float* __restrict__ mean, T* __restrict__ dS, T* __restrict__ dST,
                                                        int B, int K, int ld, int softplus, float reg, const float* __restrict__ colp,
                                                        int ncol, const float* __restrict__ pairp, int npair, float* __restrict__ out) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
-    const int bp0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
-    const float inv_bk = 1.f / ((float)B * (float)K);
-    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
     const int k = blockIdx.z;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + ty + 8 * r, bp = bp0 + tx;
-        float g = 0.f;
-        if (b < B && bp < B) {
-            const float x = S[((long long)k * B + b) * ld + bp];
-            const float sp = score_tf(x, softplus);
-            float dsp = expf(sp - lse[k * B + bp]) * inv_bk + reg_c * mean[(long long)b * ld + bp];
-            if (b == bp) dsp -= inv_bk;
-            g = dsp * score_grad(x, softplus);
-        }
-        if (b < B && bp < ld) dS[((long long)k * B + b) * ld + bp] = from_f32<T>(g);
-        tile[ty + 8 * r][tx] = g;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int bp = bp0 + ty + 8 * r, b = b0 + tx;
-        if (b < ld && bp < B) dST[((long long)k * B + bp) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
-    }
-    if (out != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(colp, ncol, pairp, npair, out, B, K, reg);
+    nce_grad_tile<T>(S, dS, dST, B, K, ld, softplus, reg, (long long)k * B, blockIdx.y * 32,
+                     NceDense{nce_terms(lse, mean, B, K, ld, reg)}, colp, ncol, pairp, npair, out);
 }
 
 // score_over_all_timesteps=True branch (contrastive_estimation_training.py:108-114, :141): S is the full R x R score
@@ -336,18 +372,7 @@ __global__ __launch_bounds__(256) void nce_all_grad_kernel(const float* __restri
         }
     }
     if (!want_partials) return;
-    red[0][threadIdx.x] = valid;
-    red[1][threadIdx.x] = msq;
-    red[2][threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s2];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s2];
-            red[2][threadIdx.x] = fmaxf(red[2][threadIdx.x], red[2][threadIdx.x + s2]);
-        }
-        __syncthreads();
-    }
+    block_reduce<3, 2>(red, {valid, msq, mx});
     if (threadIdx.x == 0) {
         partial[blockIdx.x * 3 + 0] = red[0][0];
         partial[blockIdx.x * 3 + 1] = red[1][0];
@@ -367,17 +392,7 @@ __global__ __launch_bounds__(256) void nce_all_finalize_kernel(const float* __re
         msq += grad_partial[i * 3 + 1];
         mx = fmaxf(mx, grad_partial[i * 3 + 2]);
     }
-    red[0][threadIdx.x] = lse_sum; red[1][threadIdx.x] = valid; red[2][threadIdx.x] = msq; red[3][threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s2];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s2];
-            red[2][threadIdx.x] += red[2][threadIdx.x + s2];
-            red[3][threadIdx.x] = fmaxf(red[3][threadIdx.x], red[3][threadIdx.x + s2]);
-        }
-        __syncthreads();
-    }
+    block_reduce<4, 3>(red, {lse_sum, valid, msq, mx});
     if (threadIdx.x != 0) return;
     lse_sum = red[0][0]; valid = red[1][0]; msq = red[2][0]; mx = red[3][0];
     const float r = (float)B * (float)K;
@@ -437,7 +452,7 @@ __global__ __launch_bounds__(256) void nce_row_eval_kernel(const float* __restri
 __global__ __launch_bounds__(256) void nce_eval_finalize_kernel(const float* __restrict__ lse, const float* __restrict__ rsum,
                                                                 const int* __restrict__ rarg, const float* __restrict__ rvalid,
                                                                 float* __restrict__ out, int B, int K, int all_t, int accumulate) {
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int R = B * K;
     for (int k = 0; k < K; ++k) {
         float dl = 0.f, hit = 0.f;
@@ -451,21 +466,11 @@ __global__ __launch_bounds__(256) void nce_eval_finalize_kernel(const float* __r
                 hit += rarg[k * B + j] == j ? 1.f : 0.f;
             }
         }
-        red[threadIdx.x] = dl;
+        block_reduce<1>(red, {dl});
+        const float loss_k = -red[0][0] / (float)B;
         __syncthreads();
-        for (int s2 = 128; s2 > 0; s2 >>= 1) {
-            if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-            __syncthreads();
-        }
-        const float loss_k = -red[0] / (float)B;
-        __syncthreads();
-        red[threadIdx.x] = hit;
-        __syncthreads();
-        for (int s2 = 128; s2 > 0; s2 >>= 1) {
-            if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-            __syncthreads();
-        }
-        const float acc_k = red[0] / (float)(all_t ? R : B);
+        block_reduce<1>(red, {hit});
+        const float acc_k = red[0][0] / (float)(all_t ? R : B);
         __syncthreads();
         if (threadIdx.x == 0) {
             out[k] = (accumulate ? out[k] : 0.f) + loss_k;
@@ -474,14 +479,9 @@ __global__ __launch_bounds__(256) void nce_eval_finalize_kernel(const float* __r
     }
     float tot = 0.f;
     for (int r = threadIdx.x; r < R; r += 256) tot += rsum[r];
-    red[threadIdx.x] = tot;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
+    block_reduce<1>(red, {tot});
     if (threadIdx.x == 0) {
-        const float mean = red[0] / ((float)R * (float)(all_t ? R : B));
+        const float mean = red[0][0] / ((float)R * (float)(all_t ? R : B));
         out[2 * K] = (accumulate ? out[2 * K] : 0.f) + mean;
     }
 }
@@ -504,16 +504,7 @@ __global__ __launch_bounds__(256) void nce_lse_merge_kernel(const float* __restr
         l = ref + logf(tot);
         lse[c] = l;
     }
-    red[0][threadIdx.x] = l;
-    red[1][threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s2];
-            red[1][threadIdx.x] = fmaxf(red[1][threadIdx.x], red[1][threadIdx.x + s2]);
-        }
-        __syncthreads();
-    }
+    block_reduce<2, 1>(red, {l, mx});
     if (threadIdx.x == 0) {
         colp[blockIdx.x * 2] = red[0][0];
         colp[blockIdx.x * 2 + 1] = red[1][0];
@@ -534,7 +525,7 @@ __global__ __launch_bounds__(256) void nce_fused_grad_kernel(const float* __rest
                                                              bf16_t* __restrict__ dST, float* __restrict__ gradp, int items, int K_rt, int ncols,
                                                              long long ld, long long ldT, int diag_off, int softplus, float inv_r, float reg_c) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tsm[];
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int K = KT > 0 ? KT : K_rt;
     const int rs = NFG_IT * K * 2 + 16;                       // LDS image row stride (bytes): one column's 16 K gradients + pad
     const int tid = threadIdx.x, cg = tid & 15, it = tid >> 4;          // thread = (item, 4 columns)
@@ -616,13 +607,8 @@ __global__ __launch_bounds__(256) void nce_fused_grad_kernel(const float* __rest
             }
         }
     }
-    red[tid] = msq;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (tid < s2) red[tid] += red[tid + s2];
-        __syncthreads();
-    }
-    if (tid == 0 && gradp != nullptr) gradp[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+    block_reduce<1>(red, {msq});
+    if (tid == 0 && gradp != nullptr) gradp[blockIdx.y * gridDim.x + blockIdx.x] = red[0][0];
 }
 
 // Loss scalars of the fused path.  mode 0: reduce the partials and write out[0..6] (single process); mode 1: reduce only ->
@@ -638,17 +624,7 @@ __global__ __launch_bounds__(256) void nce_fused_finalize_kernel(const float* __
         for (int i = threadIdx.x; i < nvalid; i += 256) sv += score_tf(valid[i], softplus);
         for (int i = threadIdx.x; i < ncolp; i += 256) { sl += colp[2 * i]; mx = fmaxf(mx, colp[2 * i + 1]); }
         for (int i = threadIdx.x; i < ngrad; i += 256) sm += gradp[i];
-        red[0][threadIdx.x] = sv; red[1][threadIdx.x] = sl; red[2][threadIdx.x] = sm; red[3][threadIdx.x] = mx;
-        __syncthreads();
-        for (int s2 = 128; s2 > 0; s2 >>= 1) {
-            if (threadIdx.x < s2) {
-                red[0][threadIdx.x] += red[0][threadIdx.x + s2];
-                red[1][threadIdx.x] += red[1][threadIdx.x + s2];
-                red[2][threadIdx.x] += red[2][threadIdx.x + s2];
-                red[3][threadIdx.x] = fmaxf(red[3][threadIdx.x], red[3][threadIdx.x + s2]);
-            }
-            __syncthreads();
-        }
+        block_reduce<4, 3>(red, {sv, sl, sm, mx});
         sv = red[0][0]; sl = red[1][0]; sm = red[2][0]; mx = red[3][0];
     } else {
         sv = sums[0]; sl = sums[1]; sm = sums[2]; mx = sums[3];
@@ -693,9 +669,6 @@ __device__ __forceinline__ unsigned nsm_key(unsigned long long col_base, int b) 
     z ^= z >> 31;
     return (unsigned)(z >> 32);
 }
-__device__ __forceinline__ bool nsm_member(unsigned long long col_base, int b, int bp, unsigned long long thr) {
-    return b == bp || (((unsigned long long)nsm_key(col_base, b) << 32) | (unsigned)b) <= thr;
-}
 
 // The search of every selection: called by all 64 lanes of a wave with key[h] of row lane + 64 h and ok bit h set where that row takes
 // part; returns the n-th smallest composite (key << 32 | row) among the rows that take part (1 <= n <= their number).
@@ -724,27 +697,64 @@ __device__ __forceinline__ unsigned long long nsm_search(unsigned ok, int lane, 
     return ((unsigned long long)tk << 32) | tb;
 }
 
-// The selection routine of the sampled entry points.  Called by all 64 lanes of a wave for column (k, b'): fills key[h] for row
-// lane + 64 h and returns the N-th smallest composite among the rows b < B, b != b' (at least n_neg of them exist: n_neg <= B - 1).
-template <int H>
-__device__ __forceinline__ unsigned long long nsm_select(unsigned long long col_base, int lane, int bp, int B, int n_neg,
-                                                         unsigned (&key)[H]) {
-    unsigned ok = 0;            // bit h: row lane + 64 h takes part in the selection
+// ---- grouped negatives: the same chain with candidates restricted by a per-item group id (include/cpc_hip.h, cpc_nce_loss_grouped) ----
+// Row b is ELIGIBLE for column (k, b') when b != b' and (groups[b] == groups[b']) == (mode == same); the column keeps its own row and
+// the n = min(n_neg, |Elig|) eligible rows with the smallest (key, b) (n_neg == 0: all of them).  A sampled draw is a grouped draw
+// with one group and mode "same", so everything below is written once, GROUPED a compile-time flag: without it every other row is
+// eligible, and no instantiation reads `groups` or `mode`.  Eligibility is one more condition on the ok bits of the selection and is
+// tested AGAIN, before the threshold, wherever membership is asked: a column whose eligible set is empty needs no sentinel threshold.
+constexpr unsigned long long NSM_ALL = ~0ull;       // threshold of a column that keeps every eligible row (no composite reaches it: row < 1024)
+
+__device__ __forceinline__ bool nsg_eligible(int g, int gp, int mode) { return (g == gp) == (mode == 0); }
+
+// The selection routine of every entry point.  Called by all 64 lanes of a wave for column (k, b').  ok bit h <- row lane + 64 h is
+// eligible; returns the column's threshold, the n-th smallest composite among the eligible rows.  |Elig| is B - 1 or comes from
+// ballots; with n == |Elig| (always when n_neg == 0, for an empty set, and for n_neg == B - 1 sampled negatives) nothing is hashed or
+// searched, the threshold is NSM_ALL and the keys are zero: the branch is wave-uniform.
+template <bool GROUPED, int H>
+__device__ __forceinline__ unsigned long long nsm_select(const int* __restrict__ groups, int mode, unsigned long long seed,
+                                                         unsigned long long draw, int k, int lane, int bp, int B, int n_neg,
+                                                         unsigned (&key)[H], unsigned& ok_out) {
+    int gp = 0;
+    if constexpr (GROUPED) gp = groups[bp];
+    unsigned ok = 0;
+    int elig = GROUPED ? 0 : B - 1;
 #pragma unroll
     for (int h = 0; h < H; ++h) {
         const int row = lane + 64 * h;
-        key[h] = nsm_key(col_base, row);
-        if (row < B && row != bp) ok |= 1u << h;
+        bool e = row < B && row != bp;
+        if constexpr (GROUPED) {
+            e = e && nsg_eligible(groups[row < B ? row : 0], gp, mode);
+            elig += __popcll(__ballot(e));
+        }
+        if (e) ok |= 1u << h;
     }
-    return nsm_search<H>(ok, lane, n_neg, key);
+    ok_out = ok;
+    const int n = (n_neg == 0 || n_neg > elig) ? elig : n_neg;
+    if (n == elig) {
+#pragma unroll
+        for (int h = 0; h < H; ++h) key[h] = 0;
+        return NSM_ALL;
+    }
+    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
+#pragma unroll
+    for (int h = 0; h < H; ++h) key[h] = nsm_key(base, lane + 64 * h);
+    return nsm_search<H>(ok, lane, n, key);
+}
+
+// The membership test of every entry point: row b < B is a candidate of column b' with threshold t when it is the column's own row,
+// or is eligible and its composite is within the threshold (NSM_ALL admits every key).  No branch in it: the four rows of a gradient
+// thread hash side by side.
+__device__ __forceinline__ bool nsm_member(int b, int bp, bool eligible, unsigned long long t, unsigned key) {
+    return b == bp || (eligible && (((unsigned long long)key << 32) | (unsigned)b) <= t);
 }
 
 // Column pass of one wave: threshold of column col = k B + b', and the log-sum-exp over its candidates.  The wave-wide max and sum
 // are xor butterflies (every lane ends with the same bits), the lane's own sum runs over h in order: nothing depends on timing.
-template <int H>
+template <bool GROUPED, int H>
 __device__ __forceinline__ void nsm_col_body(const float* __restrict__ S, unsigned long long* __restrict__ thr, float* __restrict__ lse,
-                                             int B, int ld, int softplus, int n_neg, unsigned long long seed, unsigned long long draw,
-                                             int col) {
+                                             int B, int ld, int softplus, const int* __restrict__ groups, int mode, int n_neg,
+                                             unsigned long long seed, unsigned long long draw, int col) {
     const int lane = threadIdx.x & 63;
     const int k = col / B, bp = col % B;
     const float* cp = S + (long long)k * B * ld + bp;
@@ -752,13 +762,13 @@ __device__ __forceinline__ void nsm_col_body(const float* __restrict__ S, unsign
     unsigned key[H];
 #pragma unroll
     for (int h = 0; h < H; ++h) v[h] = (lane + 64 * h < B) ? cp[(long long)(lane + 64 * h) * ld] : 0.f;      // in flight during the selection
-    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
-    const unsigned long long t = nsm_select<H>(base, lane, bp, B, n_neg, key);
+    unsigned ok;
+    const unsigned long long t = nsm_select<GROUPED, H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
     float mx = -INFINITY;
 #pragma unroll
     for (int h = 0; h < H; ++h) {
         const int row = lane + 64 * h;
-        const bool in = row < B && (row == bp || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t);
+        const bool in = row < B && nsm_member(row, bp, (ok >> h) & 1u, t, key[h]);
         v[h] = in ? score_tf(v[h], softplus) : -INFINITY;
         mx = fmaxf(mx, v[h]);
     }
@@ -776,227 +786,78 @@ __device__ __forceinline__ void nsm_col_body(const float* __restrict__ S, unsign
 
 // Column pass + pair means in ONE launch, as nce_col_mean_kernel: the first ncb workgroups take NSM_COLS columns each, the rest the
 // pairs (nce_mean_body: the regulariser, the max score and the valid scores run over ALL scores and do not know about the sampling).
-template <int KT, int H>
-__global__ __launch_bounds__(256) void nce_sampled_col_mean_kernel(const float* __restrict__ S, unsigned long long* __restrict__ thr,
-                                                                   float* __restrict__ lse, float* __restrict__ mean,
-                                                                   float* __restrict__ pairp, int B, int K, int ld, int softplus, int n_neg,
-                                                                   unsigned long long seed, unsigned long long draw, int ncb) {
+template <bool GROUPED, int KT, int H>
+__global__ __launch_bounds__(256) void nce_selected_col_mean_kernel(const float* __restrict__ S, unsigned long long* __restrict__ thr,
+                                                                    float* __restrict__ lse, float* __restrict__ mean,
+                                                                    float* __restrict__ pairp, int B, int K, int ld, int softplus,
+                                                                    const int* __restrict__ groups, int mode, int n_neg,
+                                                                    unsigned long long seed, unsigned long long draw, int ncb) {
     if ((int)blockIdx.x < ncb) {
         const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
-        if (col < K * B) nsm_col_body<H>(S, thr, lse, B, ld, softplus, n_neg, seed, draw, col);          // (wave-uniform)
+        if (col < K * B) nsm_col_body<GROUPED, H>(S, thr, lse, B, ld, softplus, groups, mode, n_neg, seed, draw, col);     // (wave-uniform)
     } else {
         nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb, (long long)B * ld);
     }
 }
 
-// nce_grad_kernel with the candidate test: exp(sp - lse) only where row b is a candidate of column (k, b'); workgroup (0, 0, 0) also
-// reduces the loss scalars (the column sums are the K B log-sum-exps themselves, in nce_finalize_body's fixed order).
-template <typename T>
-__global__ __launch_bounds__(256) void nce_sampled_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
-                                                               const unsigned long long* __restrict__ thr, const float* __restrict__ mean,
-                                                               T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld, int softplus,
-                                                               float reg, unsigned long long seed, unsigned long long draw,
-                                                               const float* __restrict__ pairp, int npair, float* __restrict__ out) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
-    const int bp0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
-    const float inv_bk = 1.f / ((float)B * (float)K);
-    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
+// exp(sp - lse) only where row b is a candidate of column (k, b'): the element's eligibility and key are computed again and compared
+// with the threshold the column pass left.
+template <bool GROUPED>
+struct NceSelected : NceTerms {
+    static constexpr bool live = true, own = true;
+    const unsigned long long* thr;
+    const int* groups;
+    int mode;
+    unsigned long long seed, draw;
+    unsigned long long base, t;         // of the thread's column, set by column(): what its keys share, its threshold,
+    float l;                            // its log-sum-exp
+    int gp;                             // and its group
+    __device__ __forceinline__ void column(int k, int bp) {
+        base = nsm_col_base(seed, draw, k, bp, B);
+        t = bp < B ? thr[k * B + bp] : 0ull;
+        l = bp < B ? lse[k * B + bp] : 0.f;
+        if constexpr (GROUPED) gp = bp < B ? groups[bp] : 0;
+    }
+    __device__ __forceinline__ float dsp(int k, int b, int bp, float sp) const {
+        float dsp = reg_c * mean[(long long)b * ld + bp];
+        bool eligible = true;
+        if constexpr (GROUPED) eligible = nsg_eligible(groups[b], gp, mode);
+        unsigned key = 0;           // (grouped: the hash is spared where the answer does not hang on it; sampled rows hash always)
+        if (!GROUPED || (eligible && t != NSM_ALL)) key = nsm_key(base, b);
+        if (nsm_member(b, bp, eligible, t, key)) dsp += expf(sp - l) * inv_bk;
+        if (b == bp) dsp -= inv_bk;
+        return dsp;
+    }
+};
+
+// grid as nce_grad_kernel's; the column sums of the loss scalars are the K B log-sum-exps themselves, in nce_finalize_body's fixed order
+template <typename T, bool GROUPED>
+__global__ __launch_bounds__(256) void nce_selected_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
+                                                                const unsigned long long* __restrict__ thr, const float* __restrict__ mean,
+                                                                T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld, int softplus,
+                                                                float reg, const int* __restrict__ groups, int mode, unsigned long long seed,
+                                                                unsigned long long draw, const float* __restrict__ pairp, int npair,
+                                                                float* __restrict__ out) {
     const int k = blockIdx.z;
-    const int bp = bp0 + tx;
-    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
-    const unsigned long long t = bp < B ? thr[k * B + bp] : 0ull;
-    const float l = bp < B ? lse[k * B + bp] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + ty + 8 * r;
-        float g = 0.f;
-        if (b < B && bp < B) {
-            const float x = S[((long long)k * B + b) * ld + bp];
-            const float sp = score_tf(x, softplus);
-            float dsp = reg_c * mean[(long long)b * ld + bp];
-            if (nsm_member(base, b, bp, t)) dsp += expf(sp - l) * inv_bk;
-            if (b == bp) dsp -= inv_bk;
-            g = dsp * score_grad(x, softplus);
-        }
-        if (b < B && bp < ld) dS[((long long)k * B + b) * ld + bp] = from_f32<T>(g);
-        tile[ty + 8 * r][tx] = g;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int bq = bp0 + ty + 8 * r, b = b0 + tx;
-        if (b < ld && bq < B) dST[((long long)k * B + bq) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(lse, K * B, pairp, npair, out, B, K, reg);
+    nce_grad_tile<T>(S, dS, dST, B, K, ld, softplus, reg, (long long)k * B, blockIdx.y * 32,
+                     NceSelected<GROUPED>{nce_terms(lse, mean, B, K, ld, reg), thr, groups, mode, seed, draw}, lse, K * B, pairp, npair, out);
 }
 
 // mask[k][b][b'] = 1 where row b is a candidate of column (k, b') (its own row included), from the same selection routine.
-template <int H>
-__global__ __launch_bounds__(256) void nce_sample_mask_kernel(unsigned char* __restrict__ mask, int B, int K, int n_neg,
-                                                              unsigned long long seed, unsigned long long draw) {
-    const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
-    if (col >= K * B) return;                   // (wave-uniform)
-    const int lane = threadIdx.x & 63;
-    const int k = col / B, bp = col % B;
-    unsigned key[H];
-    const unsigned long long t = nsm_select<H>(nsm_col_base(seed, draw, k, bp, B), lane, bp, B, n_neg, key);
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        const int row = lane + 64 * h;
-        if (row < B)
-            mask[((long long)k * B + row) * B + bp] = (row == bp || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t) ? 1 : 0;
-    }
-}
-
-// ---- grouped negatives: the sampled chain with candidates restricted by a per-item group id (include/cpc_hip.h, cpc_nce_loss_grouped) ----
-// Row b is ELIGIBLE for column (k, b') when b != b' and (groups[b] == groups[b']) == (mode == same); the column keeps its own row and
-// the n = min(n_neg, |Elig|) eligible rows with the smallest (key, b) (n_neg == 0: all of them).  Eligibility is one more condition
-// on the ok bits of the selection and is tested AGAIN, before the threshold, wherever membership is asked: a column whose eligible
-// set is empty needs no sentinel threshold.
-constexpr unsigned long long NSG_ALL = ~0ull;       // threshold of a column that keeps every eligible row (no composite reaches it: row < 1024)
-
-__device__ __forceinline__ bool nsg_eligible(int g, int gp, int mode) { return (g == gp) == (mode == 0); }
-
-// Called by all 64 lanes of a wave for column (k, b').  ok bit h <- row lane + 64 h is eligible; returns the column's threshold.
-// |Elig| comes from ballots; with n == |Elig| (always when n_neg == 0, and for an empty set) nothing is hashed or searched and key[]
-// stays unset: the branch is wave-uniform, and callers test `t == NSG_ALL ||` before they look at a key.
-template <int H>
-__device__ __forceinline__ unsigned long long nsg_select(const int* __restrict__ groups, int mode, unsigned long long seed,
-                                                         unsigned long long draw, int k, int lane, int bp, int B, int n_neg,
-                                                         unsigned (&key)[H], unsigned& ok_out) {
-    const int gp = groups[bp];
-    unsigned ok = 0;
-    int elig = 0;
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        const int row = lane + 64 * h;
-        const bool e = row < B && row != bp && nsg_eligible(groups[row < B ? row : 0], gp, mode);
-        if (e) ok |= 1u << h;
-        elig += __popcll(__ballot(e));
-    }
-    ok_out = ok;
-    const int n = (n_neg == 0 || n_neg > elig) ? elig : n_neg;
-    if (n == elig) return NSG_ALL;
-    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
-#pragma unroll
-    for (int h = 0; h < H; ++h) key[h] = nsm_key(base, lane + 64 * h);
-    return nsm_search<H>(ok, lane, n, key);
-}
-
-template <int H>
-__device__ __forceinline__ bool nsg_in(int row, int h, int bp, int B, unsigned ok, unsigned long long t, const unsigned (&key)[H]) {
-    if (row >= B) return false;
-    if (row == bp) return true;
-    if (!((ok >> h) & 1u)) return false;
-    return t == NSG_ALL || (((unsigned long long)key[h] << 32) | (unsigned)row) <= t;
-}
-
-// nsm_col_body with the grouped selection (same butterflies, same order of the lane's own sum).
-template <int H>
-__device__ __forceinline__ void nsg_col_body(const float* __restrict__ S, unsigned long long* __restrict__ thr, float* __restrict__ lse,
-                                             int B, int ld, int softplus, const int* __restrict__ groups, int mode, int n_neg,
-                                             unsigned long long seed, unsigned long long draw, int col) {
-    const int lane = threadIdx.x & 63;
-    const int k = col / B, bp = col % B;
-    const float* cp = S + (long long)k * B * ld + bp;
-    float v[H];
-    unsigned key[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) v[h] = (lane + 64 * h < B) ? cp[(long long)(lane + 64 * h) * ld] : 0.f;
-    unsigned ok;
-    const unsigned long long t = nsg_select<H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        v[h] = nsg_in<H>(lane + 64 * h, h, bp, B, ok, t, key) ? score_tf(v[h], softplus) : -INFINITY;
-        mx = fmaxf(mx, v[h]);
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int h = 0; h < H; ++h) sum += (v[h] == mx) ? 1.f : expf(v[h] - mx);          // (as nsm_col_body)
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0) {
-        thr[col] = t;
-        lse[col] = mx + logf(sum);
-    }
-}
-
-template <int KT, int H>
-__global__ __launch_bounds__(256) void nce_grouped_col_mean_kernel(const float* __restrict__ S, unsigned long long* __restrict__ thr,
-                                                                   float* __restrict__ lse, float* __restrict__ mean,
-                                                                   float* __restrict__ pairp, int B, int K, int ld, int softplus,
-                                                                   const int* __restrict__ groups, int mode, int n_neg,
-                                                                   unsigned long long seed, unsigned long long draw, int ncb) {
-    if ((int)blockIdx.x < ncb) {
-        const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
-        if (col < K * B) nsg_col_body<H>(S, thr, lse, B, ld, softplus, groups, mode, n_neg, seed, draw, col);     // (wave-uniform)
-    } else {
-        nce_mean_body<KT>(S, mean, pairp, B, K, ld, softplus, blockIdx.x - ncb, (long long)B * ld);
-    }
-}
-
-// nce_sampled_grad_kernel with the eligibility test in front of the threshold test.
-template <typename T>
-__global__ __launch_bounds__(256) void nce_grouped_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
-                                                               const unsigned long long* __restrict__ thr, const float* __restrict__ mean,
-                                                               T* __restrict__ dS, T* __restrict__ dST, int B, int K, int ld, int softplus,
-                                                               float reg, const int* __restrict__ groups, int mode, unsigned long long seed,
-                                                               unsigned long long draw, const float* __restrict__ pairp, int npair,
-                                                               float* __restrict__ out) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
-    const int bp0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
-    const float inv_bk = 1.f / ((float)B * (float)K);
-    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
-    const int k = blockIdx.z;
-    const int bp = bp0 + tx;
-    const unsigned long long base = nsm_col_base(seed, draw, k, bp, B);
-    const unsigned long long t = bp < B ? thr[k * B + bp] : 0ull;
-    const float l = bp < B ? lse[k * B + bp] : 0.f;
-    const int gp = bp < B ? groups[bp] : 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + ty + 8 * r;
-        float g = 0.f;
-        if (b < B && bp < B) {
-            const float x = S[((long long)k * B + b) * ld + bp];
-            const float sp = score_tf(x, softplus);
-            float dsp = reg_c * mean[(long long)b * ld + bp];
-            bool in = b == bp;
-            if (!in && nsg_eligible(groups[b], gp, mode))
-                in = t == NSG_ALL || (((unsigned long long)nsm_key(base, b) << 32) | (unsigned)b) <= t;
-            if (in) dsp += expf(sp - l) * inv_bk;
-            if (b == bp) dsp -= inv_bk;
-            g = dsp * score_grad(x, softplus);
-        }
-        if (b < B && bp < ld) dS[((long long)k * B + b) * ld + bp] = from_f32<T>(g);
-        tile[ty + 8 * r][tx] = g;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int bq = bp0 + ty + 8 * r, b = b0 + tx;
-        if (b < ld && bq < B) dST[((long long)k * B + bq) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(lse, K * B, pairp, npair, out, B, K, reg);
-}
-
-template <int H>
-__global__ __launch_bounds__(256) void nce_group_mask_kernel(unsigned char* __restrict__ mask, const int* __restrict__ groups, int B, int K,
-                                                             int mode, int n_neg, unsigned long long seed, unsigned long long draw) {
+template <bool GROUPED, int H>
+__global__ __launch_bounds__(256) void nce_select_mask_kernel(unsigned char* __restrict__ mask, const int* __restrict__ groups, int B, int K,
+                                                              int mode, int n_neg, unsigned long long seed, unsigned long long draw) {
     const int col = blockIdx.x * NSM_COLS + (threadIdx.x >> 6);
     if (col >= K * B) return;                   // (wave-uniform)
     const int lane = threadIdx.x & 63;
     const int k = col / B, bp = col % B;
     unsigned key[H];
     unsigned ok;
-    const unsigned long long t = nsg_select<H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
+    const unsigned long long t = nsm_select<GROUPED, H>(groups, mode, seed, draw, k, lane, bp, B, n_neg, key, ok);
 #pragma unroll
     for (int h = 0; h < H; ++h) {
         const int row = lane + 64 * h;
-        if (row < B) mask[((long long)k * B + row) * B + bp] = nsg_in<H>(row, h, bp, B, ok, t, key) ? 1 : 0;
+        if (row < B) mask[((long long)k * B + row) * B + bp] = nsm_member(row, bp, (ok >> h) & 1u, t, key[h]) ? 1 : 0;
     }
 }
 
@@ -1053,7 +914,7 @@ __global__ __launch_bounds__(256) void nce_bank_partial_mean_kernel(const float*
 __global__ __launch_bounds__(256) void nce_bank_merge_kernel(const float2* __restrict__ part, int nchunk, int cps,
                                                              unsigned long long valid, int ncols, float* __restrict__ lse,
                                                              float* __restrict__ colp) {
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int c = blockIdx.x * 256 + threadIdx.x;
     float l = 0.f;
     if (c < ncols) {
@@ -1069,62 +930,36 @@ __global__ __launch_bounds__(256) void nce_bank_merge_kernel(const float2* __res
         l = m + logf(tot);
         lse[c] = l;
     }
-    red[threadIdx.x] = l;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) colp[blockIdx.x] = red[0];
+    block_reduce<1>(red, {l});
+    if (threadIdx.x == 0) colp[blockIdx.x] = red[0][0];
 }
 
-// nce_grad_kernel over the ring's rows: grid (column tiles, slots x row tiles, K), a 32 x 32 tile inside ONE slot.  A row of an
-// invalid slot gets zero coefficients (written every launch), a row of a stale slot the softmax term alone, a row of slot cur also
-// the diagonal and the regulariser, and its tile goes through LDS into dST_cur[k][b'][b] as in nce_grad_kernel.  A slot has
-// ceil(ld / 32) row tiles, as nce_grad_kernel's grid: where ld reaches into a tile of its own (B = 32, ld = 39) that tile holds
-// no row of dS, but its transposed store is what writes the zeros of dST_cur's pad columns [B, ld).
+// The ring's rows: a row of an invalid slot gets zero coefficients (written every launch), a row of a stale slot the softmax term
+// alone, a row of slot cur also the diagonal and the regulariser, and its tile alone goes into dST_cur.
+struct NceBanked : NceTerms {
+    bool live, own;
+    __device__ __forceinline__ void column(int, int) {}
+    __device__ __forceinline__ float dsp(int k, int b, int bp, float sp) const {
+        float dsp = expf(sp - lse[k * B + bp]) * inv_bk;
+        if (own) {
+            dsp += reg_c * mean[(long long)b * ld + bp];
+            if (b == bp) dsp -= inv_bk;
+        }
+        return dsp;
+    }
+};
+
+// grid (column tiles, slots x row tiles, K), ceil(ld / 32) tiles per side and slot as nce_grad_kernel's: a tile lies inside ONE slot
 template <typename T>
 __global__ __launch_bounds__(256) void nce_bank_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse,
                                                             const float* __restrict__ mean, T* __restrict__ dS, T* __restrict__ dST,
                                                             int B, int K, int ld, int slots, int cur, unsigned long long valid,
                                                             int softplus, float reg, const float* __restrict__ colp, int ncol,
                                                             const float* __restrict__ pairp, int npair, float* __restrict__ out) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // ty 0..7
     const int nrt = (ld + 31) / 32;
-    const int slot = blockIdx.y / nrt;
-    const int bp0 = blockIdx.x * 32, b0 = (blockIdx.y % nrt) * 32;
-    const float inv_bk = 1.f / ((float)B * (float)K);
-    const float reg_c = 2.f * reg / ((float)B * (float)B * (float)K);
-    const int k = blockIdx.z;
-    const bool live = nbk_valid(valid, slot), own = slot == cur;          // (workgroup-uniform)
-    const long long row0 = ((long long)k * slots + slot) * B;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + ty + 8 * r, bp = bp0 + tx;
-        float g = 0.f;
-        if (live && b < B && bp < B) {
-            const float x = S[(row0 + b) * ld + bp];
-            const float sp = score_tf(x, softplus);
-            float dsp = expf(sp - lse[k * B + bp]) * inv_bk;
-            if (own) {
-                dsp += reg_c * mean[(long long)b * ld + bp];
-                if (b == bp) dsp -= inv_bk;
-            }
-            g = dsp * score_grad(x, softplus);
-        }
-        if (b < B && bp < ld) dS[(row0 + b) * ld + bp] = from_f32<T>(g);
-        tile[ty + 8 * r][tx] = g;
-    }
-    if (own) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int bp = bp0 + ty + 8 * r, b = b0 + tx;
-            if (b < ld && bp < B) dST[((long long)k * B + bp) * ld + b] = from_f32<T>(tile[tx][ty + 8 * r]);
-        }
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) nce_finalize_body(colp, ncol, pairp, npair, out, B, K, reg);
+    const int slot = blockIdx.y / nrt, k = blockIdx.z;
+    nce_grad_tile<T>(S, dS, dST, B, K, ld, softplus, reg, ((long long)k * slots + slot) * B, (blockIdx.y % nrt) * 32,
+                     NceBanked{nce_terms(lse, mean, B, K, ld, reg), nbk_valid(valid, slot), slot == cur}, colp, ncol, pairp, npair, out);
 }
 
 }  // namespace
@@ -1167,8 +1002,7 @@ int launch_nce_fused_finalize(const float* colp, int ncolp, const float* valid, 
     return CPC_OK;
 }
 
-// workspace: lse [K*B] + col partials [ceil(K*B/256)] + grad partials [3 * ceil(B/32)^2]   (f32)
-// workspace: lse [K][B] + column partials [K * ceil(B/32)] + pair partials [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7]
+// workspace: lse [K][B] + column partials [K * ceil(B / NCE_CW)] + pair partials [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7]
 long long nce_workspace_floats(int B, int K) {
     const long long nmb = ((long long)B * B + 255) / 256;
     return (long long)K * B + (long long)K * ((B + NCE_CW - 1) / NCE_CW) + 3 * nmb + (long long)B * (B + 8);
@@ -1201,19 +1035,22 @@ int launch_nce(const float* S, void* dS, void* dST, float* out, float* workspace
     return CPC_OK;
 }
 
-// ---- sampled negatives ----
+// ---- sampled and grouped negatives ----
 // workspace: thresholds [K][B] (64 bits each, first: the workspace must be 8-byte aligned) + lse [K][B] + pair partials
-// [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7]
+// [3 * ceil(B*B/256)] + pair means [B][ld <= B + 7].  (A threshold word is internal: a column that keeps every eligible row holds
+// NSM_ALL instead of its largest composite — sampled negatives with n_neg == B - 1 included, which are not hashed or searched either.)
 long long nce_sampled_workspace_floats(int B, int K) {
     if (B <= 0 || K <= 0) return 0;
     const long long nmb = ((long long)B * B + 255) / 256;
     return 3LL * K * B + 3 * nmb + (long long)B * (B + 8);
 }
+long long nce_grouped_workspace_floats(int B, int K) { return nce_sampled_workspace_floats(B, K); }
 
-int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
-                       int n_neg, unsigned long long seed, unsigned long long draw, int dtype, hipStream_t stream) {
-    if (B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
-    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+// The chain behind both entry points, which have checked their arguments: column pass + pair means, then gradients + loss scalars.
+template <bool GROUPED>
+static int launch_nce_selected(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus,
+                               float reg, const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw,
+                               int dtype, hipStream_t stream) {
     unsigned long long* thr = (unsigned long long*)workspace;
     float* lse = workspace + 2LL * K * B;
     float* pairp = lse + (long long)K * B;
@@ -1223,8 +1060,8 @@ int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* w
     const int nb = (ld + 31) / 32;
     const dim3 g1(ncb + nmb);
 #define NSM_COL(KT, H) \
-    hipLaunchKernelGGL((nce_sampled_col_mean_kernel<KT, H>), g1, dim3(256), 0, stream, S, thr, lse, mean, pairp, B, K, ld, softplus, n_neg, \
-                       seed, draw, ncb)
+    hipLaunchKernelGGL((nce_selected_col_mean_kernel<GROUPED, KT, H>), g1, dim3(256), 0, stream, S, thr, lse, mean, pairp, B, K, ld, softplus, \
+                       groups, mode, n_neg, seed, draw, ncb)
     if (B <= 256) {
         if (K == 12) NSM_COL(12, 4); else if (K == 16) NSM_COL(16, 4); else NSM_COL(0, 4);
     } else {
@@ -1232,68 +1069,51 @@ int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* w
     }
 #undef NSM_COL
     if (dtype == CPC_DTYPE_BF16)
-        hipLaunchKernelGGL((nce_sampled_grad_kernel<bf16_t>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (bf16_t*)dS,
-                           (bf16_t*)dST, B, K, ld, softplus, reg, seed, draw, pairp, nmb, out);
-    else
-        hipLaunchKernelGGL((nce_sampled_grad_kernel<float>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (float*)dS,
-                           (float*)dST, B, K, ld, softplus, reg, seed, draw, pairp, nmb, out);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
-}
-
-int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw,
-                           hipStream_t stream) {
-    if (!mask || B <= 1 || B > NSM_MAXB || K <= 0 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
-    const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
-    if (B <= 256) hipLaunchKernelGGL(nce_sample_mask_kernel<4>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
-    else hipLaunchKernelGGL(nce_sample_mask_kernel<16>, grid, dim3(256), 0, stream, mask, B, K, n_neg, seed, draw);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
-}
-
-// ---- grouped negatives ---- (workspace laid out as the sampled chain's)
-long long nce_grouped_workspace_floats(int B, int K) { return nce_sampled_workspace_floats(B, K); }
-
-int launch_nce_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
-                       const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw, int dtype,
-                       hipStream_t stream) {
-    if (B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 0 || n_neg > B - 1 || (mode != 0 && mode != 1)) return CPC_EINVAL;
-    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
-    unsigned long long* thr = (unsigned long long*)workspace;
-    float* lse = workspace + 2LL * K * B;
-    float* pairp = lse + (long long)K * B;
-    const int nmb = (int)(((long long)B * B + 255) / 256);
-    float* mean = pairp + 3LL * nmb;
-    const int ncb = (K * B + NSM_COLS - 1) / NSM_COLS;
-    const int nb = (ld + 31) / 32;
-    const dim3 g1(ncb + nmb);
-#define NSG_COL(KT, H) \
-    hipLaunchKernelGGL((nce_grouped_col_mean_kernel<KT, H>), g1, dim3(256), 0, stream, S, thr, lse, mean, pairp, B, K, ld, softplus, groups, \
-                       mode, n_neg, seed, draw, ncb)
-    if (B <= 256) {
-        if (K == 12) NSG_COL(12, 4); else if (K == 16) NSG_COL(16, 4); else NSG_COL(0, 4);
-    } else {
-        if (K == 12) NSG_COL(12, 16); else if (K == 16) NSG_COL(16, 16); else NSG_COL(0, 16);
-    }
-#undef NSG_COL
-    if (dtype == CPC_DTYPE_BF16)
-        hipLaunchKernelGGL((nce_grouped_grad_kernel<bf16_t>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (bf16_t*)dS,
+        hipLaunchKernelGGL((nce_selected_grad_kernel<bf16_t, GROUPED>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (bf16_t*)dS,
                            (bf16_t*)dST, B, K, ld, softplus, reg, groups, mode, seed, draw, pairp, nmb, out);
     else
-        hipLaunchKernelGGL((nce_grouped_grad_kernel<float>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (float*)dS,
+        hipLaunchKernelGGL((nce_selected_grad_kernel<float, GROUPED>), dim3(nb, nb, K), dim3(256), 0, stream, S, lse, thr, mean, (float*)dS,
                            (float*)dST, B, K, ld, softplus, reg, groups, mode, seed, draw, pairp, nmb, out);
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }
 
+template <bool GROUPED>
+static int launch_nce_select_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
+                                  unsigned long long draw, hipStream_t stream) {
+    const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
+    if (B <= 256) hipLaunchKernelGGL((nce_select_mask_kernel<GROUPED, 4>), grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
+    else hipLaunchKernelGGL((nce_select_mask_kernel<GROUPED, 16>), grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}
+
+// (the dtype and the alignment are checked before the first launch: a refused call writes nothing)
+int launch_nce_sampled(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
+                       int n_neg, unsigned long long seed, unsigned long long draw, int dtype, hipStream_t stream) {
+    if (B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
+    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+    return launch_nce_selected<false>(S, dS, dST, out, workspace, B, K, ld, softplus, reg, nullptr, 0, n_neg, seed, draw, dtype, stream);
+}
+
+int launch_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned long long seed, unsigned long long draw,
+                           hipStream_t stream) {
+    if (!mask || B <= 1 || B > NSM_MAXB || K <= 0 || n_neg < 1 || n_neg > B - 1) return CPC_EINVAL;
+    return launch_nce_select_mask<false>(mask, nullptr, B, K, 0, n_neg, seed, draw, stream);
+}
+
+int launch_nce_grouped(const float* S, void* dS, void* dST, float* out, float* workspace, int B, int K, int ld, int softplus, float reg,
+                       const int* groups, int mode, int n_neg, unsigned long long seed, unsigned long long draw, int dtype,
+                       hipStream_t stream) {
+    if (!groups || B <= 1 || B > NSM_MAXB || K <= 0 || ld < B || ld > B + 7 || n_neg < 0 || n_neg > B - 1 || (mode != 0 && mode != 1)) return CPC_EINVAL;
+    if ((dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) || (uintptr_t)workspace % 8) return CPC_EINVAL;
+    return launch_nce_selected<true>(S, dS, dST, out, workspace, B, K, ld, softplus, reg, groups, mode, n_neg, seed, draw, dtype, stream);
+}
+
 int launch_nce_group_mask(unsigned char* mask, const int* groups, int B, int K, int mode, int n_neg, unsigned long long seed,
                           unsigned long long draw, hipStream_t stream) {
     if (!mask || !groups || B <= 1 || B > NSM_MAXB || K <= 0 || n_neg < 0 || n_neg > B - 1 || (mode != 0 && mode != 1)) return CPC_EINVAL;
-    const dim3 grid((K * B + NSM_COLS - 1) / NSM_COLS);
-    if (B <= 256) hipLaunchKernelGGL(nce_group_mask_kernel<4>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
-    else hipLaunchKernelGGL(nce_group_mask_kernel<16>, grid, dim3(256), 0, stream, mask, groups, B, K, mode, n_neg, seed, draw);
-    CPC_CHECK_LAUNCH();
-    return CPC_OK;
+    return launch_nce_select_mask<true>(mask, groups, B, K, mode, n_neg, seed, draw, stream);
 }
 
 // ---- negative bank ----

@@ -623,7 +623,7 @@ int cpc_nce_loss(const float* S, void* dS, void* dST, float* out, float* workspa
  *   loss = -mean valid + mean_{k,b'} logsumexp_{b in C} sp + reg mean_{b,b'} (mean_k sp)^2        (regulariser over ALL scores)
  *   dsp[k][b][b'] = ([b in C(k,b')] exp(sp - lse[k][b']) - [b == b']) / (B K) + 2 reg / (B^2 K) mean_k sp[k][b][b']
  * S, dS, dST, out[8], ld, softplus, dtype and the pad-column zeros exactly as cpc_nce_loss (out[1] stays the max over all scores);
- * n_neg == B - 1 is cpc_nce_loss's loss.  workspace: cpc_nce_sampled_workspace_floats(B,K) f32, 8-byte aligned.
+ * n_neg == B - 1 is cpc_nce_loss's loss (its column pass skips the search).  workspace: cpc_nce_sampled_workspace_floats(B,K) f32, 8-byte aligned.
  * Limits: 2 <= B <= 1024, 1 <= n_neg <= B - 1; CPC_EINVAL otherwise, for a null pointer and for a dtype other than f32 / bf16.
  * cpc_nce_sample_mask writes the candidate sets themselves, by the same device selection routine: mask[k][b][b'] (bytes, no padding)
  * = 1 where b is in C(k,b') (the diagonal included), else 0. */
@@ -641,7 +641,8 @@ int cpc_nce_sample_mask(unsigned char* mask, int B, int K, int n_neg, unsigned l
  * Loss, dsp, out[8], the layouts, ld, softplus, dtype and the pad-column zeros are cpc_nce_loss_sampled's with this C (regulariser, max
  * score and valid scores over ALL scores).  A target whose eligible set is empty has lse = sp[k][b'][b']: it contributes 0 and stays in
  * the mean.  A column that keeps its whole eligible set (always with n_neg == 0) computes no hash.  One group for the whole batch with
- * mode 0: n_neg = N selects cpc_nce_sample_mask's sets bit for bit, n_neg = 0 is cpc_nce_loss's loss.
+ * mode 0: n_neg = N selects cpc_nce_sample_mask's sets and gives cpc_nce_loss_sampled's outputs bit for bit (both entry points run
+ * one kernel template), n_neg = 0 is cpc_nce_loss's loss.
  * workspace: cpc_nce_grouped_workspace_floats(B,K) f32, 8-byte aligned.
  * Limits: 2 <= B <= 1024, B <= ld <= B + 7, mode in {0, 1}, 0 <= n_neg <= B - 1; CPC_EINVAL otherwise, for a null pointer (groups
  * included), for a dtype other than f32 / bf16 and for a workspace that is not 8-byte aligned — before any launch: a refused call

@@ -115,10 +115,11 @@ def test_one_group_is_the_sampler_on_the_device(B, K, N, seed, draw):
 
 
 # ------------------------------------------------------------------------------------------ the loss kernels
-def _run_grouped(S, groups, K, mode, n_neg, reg, softplus, dt, seed, draw):
-    """Launches cpc_nce_loss_grouped on S [K][B][B] as test_nce_loss launches cpc_nce_loss: junk in the pad columns, NaN-prefilled
-    outputs, sentinels behind every buffer.  Returns (out, dS, dST) on the host."""
-    B = len(groups)
+def _run_loss(entry, S, K, reg, softplus, dt, *selection):
+    """Launches a loss entry point on S [K][B][B] as test_nce_loss launches cpc_nce_loss: junk in the pad columns, NaN-prefilled
+    outputs, sentinels behind every buffer.  ``selection``: the arguments between the regularisation and the dtype.  Returns
+    (out, dS, dST) on the host."""
+    B = S.shape[1]
     code = _hip.dtype_code(dt)
     ld = (B + 7) // 8 * 8
     Sp = torch.full((K, B, ld), 7.0)
@@ -127,16 +128,22 @@ def _run_grouped(S, groups, K, mode, n_neg, reg, softplus, dt, seed, draw):
     dSp, dS_w = _guarded((K, B, ld), float("nan"), dt)
     dSTp, dST_w = _guarded((K, B, ld), float("nan"), dt)
     out, out_w = _guarded((8,), float("nan"), torch.float32)
-    nws = int(_hip.lib().cpc_nce_grouped_workspace_floats(B, K))
+    nws = int(getattr(_hip.lib(), entry.replace("loss_", "") + "_workspace_floats")(B, K))
     ws, ws_w = _guarded((nws,), 0.0, torch.float32)
-    g, g_w = _groups_dev(groups)
-    _hip.call("cpc_nce_loss_grouped", _hip.ptr(S_d), _hip.ptr(dSp), _hip.ptr(dSTp), _hip.ptr(out), _hip.ptr(ws), B, K, ld, softplus,
-              C.c_float(reg), _hip.ptr(g), MODES[mode], n_neg, U64(seed), U64(draw), code)
+    _hip.call(entry, _hip.ptr(S_d), _hip.ptr(dSp), _hip.ptr(dSTp), _hip.ptr(out), _hip.ptr(ws), B, K, ld, softplus, C.c_float(reg),
+              *selection, code)
     torch.cuda.synchronize()
-    assert _tails_intact(S_w, dS_w, dST_w, out_w, ws_w, g_w)
-    assert torch.equal(S_d.cpu(), Sp) and g.tolist() == list(groups)
+    assert _tails_intact(S_w, dS_w, dST_w, out_w, ws_w)
+    assert torch.equal(S_d.cpu(), Sp)
     assert (dSp[:, :, B:] == 0).all() and (dSTp[:, :, B:] == 0).all()
     return out.cpu(), dSp[:, :, :B].cpu(), dSTp[:, :, :B].cpu()
+
+
+def _run_grouped(S, groups, K, mode, n_neg, reg, softplus, dt, seed, draw):
+    g, g_w = _groups_dev(groups)
+    got = _run_loss("cpc_nce_loss_grouped", S, K, reg, softplus, dt, _hip.ptr(g), MODES[mode], n_neg, U64(seed), U64(draw))
+    assert _tails_intact(g_w) and g.tolist() == list(groups)
+    return got
 
 
 def _scores(B, K):
@@ -171,6 +178,23 @@ def test_nce_loss_grouped_against_float64(dt, softplus, B, K, groups):
             t = 2e-5 if dt == torch.float32 else 1e-2
             assert _rel(dS, lin.grad) < t, (mode, n_neg)
             assert _rel(dST, lin.grad.transpose(1, 2)) < t, (mode, n_neg)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("softplus", [0, 1])
+@pytest.mark.parametrize("B,K,N,seed,draw", [(6, 4, 2, 1234, 5), (37, 3, 9, 99, 1000003), (40, 12, 5, 41, 3), TIES[0]])
+def test_one_group_is_the_sampled_loss_bit_for_bit(dt, softplus, B, K, N, seed, draw):
+    """Identity 1 for the loss: one group, "same", n_neg = N gives cpc_nce_loss_sampled's out[0:7], dS and dST with the same (N, seed,
+    draw), bit for bit (the NaN that stays in out[6] included) — both entry points run one template."""
+    S, reg = _scores(B, K), {6: 1.0, 37: 0.5, 40: 0.01, 257: 0.0}[B]
+    got = _run_grouped(S, [-3] * B, K, "same", N, reg, softplus, dt, seed, draw)
+    ref = _run_loss("cpc_nce_loss_sampled", S, K, reg, softplus, dt, N, U64(seed), U64(draw))
+    assert torch.equal(_bits(got[0][:7]), _bits(ref[0][:7]))
+    assert torch.equal(_bits(got[1]), _bits(ref[1])) and torch.equal(_bits(got[2]), _bits(ref[2]))
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])

@@ -174,6 +174,7 @@ _SIGNATURES = {
     "cpc_gru_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "cpc_gru_fwd_h0": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "cpc_gru_bwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+    "cpc_gru_bwd_steps": ([_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "cpc_gru_gp_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_gp_bwd": ([_P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_set_streaming": ([_I], _I),

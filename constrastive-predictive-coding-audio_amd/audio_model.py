@@ -97,12 +97,23 @@ class AudioGRUModel(nn.Module):
     """GRU context network; ``forward(input)`` takes (batch, input_size, steps) and returns the last hidden state
     (reference audio_model.py:47-77).  ``reset_hidden=False`` carries the last hidden state of one call into the next (``self.hidden``,
     as in the reference, :69 / :75): forward only -- a call that starts from a carried state cannot be differentiated (the reference's
-    autograd raises there too, the previous call's graph being gone)."""
+    autograd raises there too, the previous call's graph being gone).
 
-    def __init__(self, input_size, hidden_size, bias=True, reset_hidden=True):
+    ``num_layers`` (1 .. 4; not in the reference) stacks GRU cells: layer 0 is ``gruCell``, layer i >= 1 is ``upper_cells.{i-1}``
+    (hidden_size -> hidden_size) and reads the hidden states of the layer below, step by step; the output is the top layer's last
+    hidden state.  With ``num_layers == 1`` nothing else is registered and no random number is drawn: keys, initial values and
+    parameter count are the reference's.  A carried state is (batch, hidden) for one layer, (num_layers, batch, hidden) for a stack."""
+
+    MAX_LAYERS = 4
+
+    def __init__(self, input_size, hidden_size, bias=True, reset_hidden=True, num_layers=1):
         super().__init__()
-        self.input_size, self.hidden_size = input_size, hidden_size
+        if isinstance(num_layers, bool) or not isinstance(num_layers, int) or not 1 <= num_layers <= self.MAX_LAYERS:
+            raise ValueError(f"num_layers must be an int in 1 .. {self.MAX_LAYERS}, got {num_layers!r}")
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.gruCell = _GRUCellParams(input_size, hidden_size, bias)
+        if num_layers > 1:
+            self.upper_cells = nn.ModuleList(_GRUCellParams(hidden_size, hidden_size, bias) for _ in range(num_layers - 1))
         self.hidden = None
         self.reset_hidden = reset_hidden
 

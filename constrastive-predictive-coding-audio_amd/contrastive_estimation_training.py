@@ -574,6 +574,11 @@ class ContrastiveEstimationTrainer:
             if score_function not in (linear_score_function, softplus_score_function) or optimizer is not torch.optim.Adam:
                 raise NotImplementedError("the gradient penalty on the HIP path covers linear_score_function / softplus_score_function "
                                           "+ Adam; see DESIGN.md section 8")
+            from .audio_model import AudioGRUModel
+            ar = getattr(model, "autoregressive_model", None)
+            if isinstance(ar, AudioGRUModel) and getattr(ar, "num_layers", 1) > 1:
+                from .engine import GRUContext
+                raise NotImplementedError(GRUContext.GP_STACK_REASON)
             model.gradient_penalty_engine = True      # engines built from now on also give the gradient w.r.t. the scalogram
         if self.verbose:
             print("use score function", self.score_function)

@@ -658,6 +658,12 @@ int cpc_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG,
     return launch_gru_bwd(dc, tape, WTfrag, dG, B, V, H, dtype, (hipStream_t)stream);
 }
 
+int cpc_gru_bwd_steps(const float* dc, const void* dHs, long long ld_h, const void* tape, const void* WTfrag, void* dG, int B, int V,
+                      int H, int dtype, void* stream) {
+    if (!tape || !WTfrag || !dG || (!dc && !dHs)) return CPC_EINVAL;
+    return launch_gru_bwd(dc, tape, WTfrag, dG, B, V, H, dtype, (hipStream_t)stream, dHs, ld_h);
+}
+
 int cpc_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const float* bhh, float* tape, float* ct_out, int B,
                    int V, int H, void* stream) {
     if (!Gi || !GiT || !WT || !bhh || !tape || !ct_out) return CPC_EINVAL;

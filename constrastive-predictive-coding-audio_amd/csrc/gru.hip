@@ -156,9 +156,12 @@ __global__ __launch_bounds__(512) void gru_fwd_wide_kernel(const T* __restrict__
 }
 
 // WTfrag: fragment-ordered W_hh^T ([H][3H] logical: rows = hidden unit, k = gate column).
-template <typename T, int NW>
+// STEPS (cpc_gru_bwd_steps: a lower layer of a stack): a gradient arrives at every hidden state, dHs[(b V + t) ld_h + j] at h_{t+1},
+// and joins dh at the top of step t; dc may then be NULL (zeros).  STEPS == false is cpc_gru_bwd's code: dHs / ld_h are not read.
+template <typename T, int NW, bool STEPS>
 __device__ __forceinline__ void gru_bwd_steps(unsigned char* smem, const float* __restrict__ dc, const T* __restrict__ tape,
-                                              const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+                                              const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H,
+                                              const T* __restrict__ dHs, long long ld_h) {
     constexpr int CH = Elem<T>::CH;
     const int rowb = 3 * H * (int)sizeof(T) + 16;
     unsigned char* gcur = smem;                            // dgh tile [16][3H] (+16 B pad per row)
@@ -177,7 +180,7 @@ __device__ __forceinline__ void gru_bwd_steps(unsigned char* smem, const float* 
         const int jt = wave + NW * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[q][e] = 0.f;
-        if (jt < ntile && b_ok) {
+        if (jt < ntile && b_ok && (!STEPS || dc)) {
             const f32x4 v = *(const f32x4*)(dc + (long long)b * H + jt * 16 + fg * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dh[q][e] = v[e];
@@ -196,6 +199,13 @@ __device__ __forceinline__ void gru_bwd_steps(unsigned char* smem, const float* 
                     const T* gp = tape + (((long long)b * V + t) * 5) * H + j;
                     r4 = load4(gp); u4 = load4(gp + H); n4 = load4(gp + 2 * H); q4 = load4(gp + 3 * H);
                     hp = load4(gp + 4 * H);
+                }
+                if constexpr (STEPS) {
+                    if (b_ok) {          // rows of items >= B are not read (as the stores of dG are masked)
+                        const f32x4 ds = load4(dHs + ((long long)b * V + t) * ld_h + j);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dh[q][e] += ds[e];
+                    }
                 }
                 f32x4 dr4, du4, dn4, dnr4;
 #pragma unroll
@@ -248,14 +258,30 @@ template <typename T>
 __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
                                                       const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    gru_bwd_steps<T, 4>(smem, dc, tape, WTfrag, dG, B, V, H);
+    gru_bwd_steps<T, 4, false>(smem, dc, tape, WTfrag, dG, B, V, H, nullptr, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gru_bwd_hs_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
+                                                         const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H,
+                                                         const T* __restrict__ dHs, long long ld_h) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    gru_bwd_steps<T, 4, true>(smem, dc, tape, WTfrag, dG, B, V, H, dHs, ld_h);
 }
 
 template <typename T>
 __global__ __launch_bounds__(512) void gru_bwd_wide_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
                                                            const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[16 * (3 * GRU_WIDE_H * sizeof(T) + 16)];
-    gru_bwd_steps<T, 8>(smem, dc, tape, WTfrag, dG, B, V, H);
+    gru_bwd_steps<T, 8, false>(smem, dc, tape, WTfrag, dG, B, V, H, nullptr, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void gru_bwd_wide_hs_kernel(const float* __restrict__ dc, const T* __restrict__ tape,
+                                                              const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H,
+                                                              const T* __restrict__ dHs, long long ld_h) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[16 * (3 * GRU_WIDE_H * sizeof(T) + 16)];
+    gru_bwd_steps<T, 8, true>(smem, dc, tape, WTfrag, dG, B, V, H, dHs, ld_h);
 }
 
 // ----------------------------------------------------------------------------------------------- weight-resident bf16
@@ -488,19 +514,37 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_fwd_res_kernel(const bf16_t* 
     }
 }
 
-template <int KC>
+// STEPS (cpc_gru_bwd_steps): the gradient that arrives at h_{t+1} from outside the recurrence, dHs[(b V + t) ld_h + j], joins dh at
+// the top of step t.  Its 16 x H tile is requested together with a tape prefetch (one row-contiguous 16-byte piece per thread, the same
+// coalesced form as every other global access here), is covered by the same explicit wait in front of a step's stores, goes through an
+// LDS tile and reaches the gate pass in registers, in MFMA lane order (the pipeline is spelled out in front of the loop).  (Requested in
+// lane order straight from HBM, a lane would need 8 scattered bytes of each of its tiles' rows.)
+// STEPS == false is cpc_gru_bwd's kernel: no tile, dHs / ld_h not read (the two are kernel arguments of both forms, so that the
+// body stays the kernel itself: wrapped in an inlined function, the H = 32 and 64 instantiations came out one VGPR larger).
+template <int KC, bool STEPS> struct GruBwdRes {
+    typedef GruCfg<KC> Cfg;
+    static constexpr int ROWB = 4 * Cfg::H * 2 + 16;                   // [dr | du | dn | dn*r]
+    static constexpr int WL_BYTES = GRU_NW * Cfg::NJT * Cfg::KCL * 1024;
+    static constexpr int DROWB = Cfg::H * 2 + 16;                      // row stride of the dHs tile
+    static constexpr int SMEM = WL_BYTES + 16 * ROWB + (STEPS ? 16 * DROWB : 0);
+};
+
+template <int KC, bool STEPS>
 __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* __restrict__ dc, const bf16_t* __restrict__ tape,
                                                                   const bf16_t* __restrict__ WTfrag, bf16_t* __restrict__ dG,
-                                                                  int B, int V) {
+                                                                  int B, int V, const bf16_t* __restrict__ dHs, long long ld_h) {
     typedef GruCfg<KC> Cfg;
     constexpr int H = Cfg::H, NT = Cfg::NT, NJT = Cfg::NJT, NW = GRU_NW, NTHR = 64 * NW;
     constexpr bool FULL = Cfg::FULL;
     constexpr int KC3 = 3 * KC, KCL = Cfg::KCL, KCR = KC3 - KCL;
-    constexpr int ROWB = 4 * H * 2 + 16;                   // [dr | du | dn | dn*r]
-    constexpr int WL_BYTES = NW * NJT * KCL * 1024;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[WL_BYTES + 16 * ROWB];
+    constexpr int ROWB = GruBwdRes<KC, STEPS>::ROWB, WL_BYTES = GruBwdRes<KC, STEPS>::WL_BYTES;
+    constexpr int DROWB = GruBwdRes<KC, STEPS>::DROWB;
+    constexpr int DCH = 16 * H / 8;                        // 16-byte pieces of one dHs tile: at most one per thread (H <= 256)
+    static_assert(DCH <= NTHR, "one piece of the dHs tile per thread");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[GruBwdRes<KC, STEPS>::SMEM];
     unsigned char* wl = smem;
     unsigned char* gcur = smem + WL_BYTES;
+    unsigned char* dtile = gcur + 16 * ROWB;               // (STEPS only)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int frow = lane & 15, fg = lane >> 4;
@@ -524,7 +568,7 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[q][e] = 0.f;
-        if (on && b_ok) {
+        if (on && b_ok && (!STEPS || dc)) {
             const f32x4 v = *(const f32x4*)(dc + (long long)b * H + jt * 16 + fg * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dh[q][e] = v[e];
@@ -538,13 +582,50 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
 #pragma unroll
         for (int k = 0; k < Cfg::SLOTS; ++k) { sv[k] = *(const uint4*)(tp + k * 64 * 8); svn[k] = sv[k]; }
     }
+    // dHs: thread tid < DCH owns piece (row d_rb, 16-byte column d_cc) of every step's tile.  The request itself is unconditional, as
+    // the tape's are (a request under a condition makes the wait-count pass wait for everything in flight in front of it, the previous
+    // step's stores included: that put a wait into the gate pass of every step): rows of items >= B are never read -- such a thread, and
+    // with H < 256 the threads beyond the tile, request a row of the workgroup's first item instead, and zeros are parked for them.
+    const int d_i = tid < DCH ? tid : tid % DCH;
+    const int d_rb = d_i / (H / 8), d_cc = d_i % (H / 8);
+    const bool d_on = b0 + d_rb < B;
+    const bf16_t* dsrc = STEPS ? dHs + ((long long)(d_on ? b0 + d_rb : b0) * V) * ld_h + d_cc * 8 : nullptr;
+    // Pipeline of the tile of step k: requested at the top of step k + 2 (with the tape of step k + 1), waited for behind that step's
+    // matrix phase, parked in the LDS tile at the top of step k + 1, read back in MFMA lane order (8 bytes per owned tile) behind that
+    // step's first barrier -- the matrix phase hides the LDS round trip --, and added to dh from registers in the gate pass of step k.
+    // (Read from LDS in the gate pass itself, the round trip sat at the head of every step's dependent chain: 0.2067 against 0.2056 ms at B = 256, V = 100.)
+    uint4 dpre = make_uint4(0, 0, 0, 0);          // the tile the next step's top parks
+    uint2 dcur[NJT], dnext[NJT];                  // lane-order values of this step / of the next one
+#pragma unroll
+    for (int q = 0; q < NJT; ++q) dcur[q] = dnext[q] = make_uint2(0, 0);
+    if constexpr (STEPS) {
+        const uint4 d0 = *(const uint4*)(dsrc + (long long)(V - 1) * ld_h);
+        dpre = *(const uint4*)(dsrc + (long long)(V > 1 ? V - 2 : 0) * ld_h);
+        // nothing may be in flight when the loop starts (gru_fwd_res_kernel has the same wait, for the same reason): with these requests
+        // possibly pending at the loop header the pass put vmcnt(0) in front of every step's tape requests, behind the previous step's stores
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        asm volatile("" ::: "memory");
+        if (tid < DCH) *(uint4*)(dtile + d_rb * DROWB + d_cc * 16) = d_on ? d0 : make_uint4(0, 0, 0, 0);
+    }
     __syncthreads();
+    if constexpr (STEPS) {
+#pragma unroll
+        for (int q = 0; q < NJT; ++q)
+            if (FULL || wave + NW * q < NT) dcur[q] = *(const uint2*)(dtile + frow * DROWB + ((wave + NW * q) * 16 + fg * 4) * 2);
+        __syncthreads();          // all reads of the first tile are done before the first step's top parks the second
+    }
 
     for (int t = V - 1; t >= 0; --t) {
         if (t > 0) {
             const bf16_t* tp = tape + ((tape_bt + (t - 1)) * NW + wave) * Cfg::SLOTS * 64 * 8 + lane * 8;
 #pragma unroll
             for (int k = 0; k < Cfg::SLOTS; ++k) svn[k] = *(const uint4*)(tp + k * 64 * 8);
+            if constexpr (STEPS) {
+                // park the tile of step t - 1 (every wave finished reading the one before it ahead of the previous step's last barrier), then
+                // request the tile of step t - 2 into the same registers (at t = 1: step 0's again, never used)
+                if (tid < DCH) *(uint4*)(dtile + d_rb * DROWB + d_cc * 16) = d_on ? dpre : make_uint4(0, 0, 0, 0);
+                dpre = *(const uint4*)(dsrc + (long long)(t > 1 ? t - 2 : 0) * ld_h);
+            }
         }
         float keep[NJT][4];
         f32x4 hp_all[2];
@@ -558,6 +639,11 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
                 unpack8(sv[2 * q], r4, u4);
                 unpack8(sv[2 * q + 1], n4, q4);
                 const f32x4 hp = hp_all[q & 1];
+                if constexpr (STEPS) {
+                    const bf16x4 dv = __builtin_bit_cast(bf16x4, dcur[q]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dh[q][e] += (float)dv[e];
+                }
                 f32x4 dr4, du4, dn4, dnr4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -578,6 +664,13 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
             }
         }
         __syncthreads();
+        if constexpr (STEPS) {          // the tile of step t - 1, parked at the top of this step: used in the next step's gate pass
+            if (t > 0) {
+#pragma unroll
+                for (int q = 0; q < NJT; ++q)
+                    if (FULL || wave + NW * q < NT) dnext[q] = *(const uint2*)(dtile + frow * DROWB + ((wave + NW * q) * 16 + fg * 4) * 2);
+            }
+        }
         // the gradient tile goes to HBM as whole rows (16 rows x 4H bf16): read from LDS here, stored behind the matrix phase (below)
         constexpr int GCH = 16 * 4 * H / 8, GST = (GCH + NTHR - 1) / NTHR;
         uint4 gst[GST];
@@ -620,6 +713,10 @@ __global__ __launch_bounds__(64 * GRU_NW) void gru_bwd_res_kernel(const float* _
         }
 #pragma unroll
         for (int k = 0; k < Cfg::SLOTS; ++k) sv[k] = svn[k];
+        if constexpr (STEPS) {
+#pragma unroll
+            for (int q = 0; q < NJT; ++q) dcur[q] = dnext[q];
+        }
         __syncthreads();
     }
 }
@@ -701,11 +798,21 @@ int launch_gru_fwd(const void* Gi, const void* Wfrag, const float* bhh, void* Ha
     return CPC_OK;
 }
 
+// dHs == NULL: cpc_gru_bwd's kernels.  Otherwise the STEPS instantiations of the same three families, chosen the same way.
 int launch_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
-                   hipStream_t stream) {
+                   hipStream_t stream, const void* dHs, long long ld_h) {
     if (!gru_ok(B, V, H, dtype)) return CPC_EINVAL;
+    if (!dHs && !dc) return CPC_EINVAL;
+    if (dHs && (ld_h < H || ld_h % (dtype == CPC_DTYPE_BF16 ? 8 : 4))) return CPC_EINVAL;
     if (H > 256) {          // 8 waves (tiles w + 8q), static LDS
-        if (dtype == CPC_DTYPE_BF16)
+        if (dHs) {
+            if (dtype == CPC_DTYPE_BF16)
+                hipLaunchKernelGGL((gru_bwd_wide_hs_kernel<bf16_t>), dim3((B + 15) / 16), dim3(512), 0, stream, dc, (const bf16_t*)tape,
+                                   (const bf16_t*)WTfrag, (bf16_t*)dG, B, V, H, (const bf16_t*)dHs, ld_h);
+            else
+                hipLaunchKernelGGL((gru_bwd_wide_hs_kernel<float>), dim3((B + 15) / 16), dim3(512), 0, stream, dc, (const float*)tape,
+                                   (const float*)WTfrag, (float*)dG, B, V, H, (const float*)dHs, ld_h);
+        } else if (dtype == CPC_DTYPE_BF16)
             hipLaunchKernelGGL((gru_bwd_wide_kernel<bf16_t>), dim3((B + 15) / 16), dim3(512), 0, stream, dc, (const bf16_t*)tape,
                                (const bf16_t*)WTfrag, (bf16_t*)dG, B, V, H);
         else
@@ -719,11 +826,25 @@ int launch_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* 
     if (shm > 64 * 1024) return CPC_EINVAL;
     dim3 grid((B + 15) / 16);
     if (dtype == CPC_DTYPE_BF16 && !g_gru_force_streaming && (H == 32 || H == 64 || H == 128 || H == 256)) {
-#define GRU_B(KC) \
-    hipLaunchKernelGGL((gru_bwd_res_kernel<KC>), grid, dim3(64 * GRU_NW), 0, stream, dc, (const bf16_t*)tape, (const bf16_t*)WTfrag, \
-                       (bf16_t*)dG, B, V)
-        if (H == 256) GRU_B(8); else if (H == 128) GRU_B(4); else if (H == 64) GRU_B(2); else GRU_B(1);
+#define GRU_B(KC, STEPS) \
+    hipLaunchKernelGGL((gru_bwd_res_kernel<KC, STEPS>), grid, dim3(64 * GRU_NW), 0, stream, dc, (const bf16_t*)tape, (const bf16_t*)WTfrag, \
+                       (bf16_t*)dG, B, V, (const bf16_t*)dHs, ld_h)
+        if (dHs) {
+            if (H == 256) GRU_B(8, true); else if (H == 128) GRU_B(4, true); else if (H == 64) GRU_B(2, true); else GRU_B(1, true);
+        } else {
+            if (H == 256) GRU_B(8, false); else if (H == 128) GRU_B(4, false); else if (H == 64) GRU_B(2, false); else GRU_B(1, false);
+        }
 #undef GRU_B
+        CPC_CHECK_LAUNCH();
+        return CPC_OK;
+    }
+    if (dHs) {
+        if (dtype == CPC_DTYPE_BF16)
+            hipLaunchKernelGGL((gru_bwd_hs_kernel<bf16_t>), grid, dim3(256), shm, stream, dc, (const bf16_t*)tape, (const bf16_t*)WTfrag,
+                               (bf16_t*)dG, B, V, H, (const bf16_t*)dHs, ld_h);
+        else
+            hipLaunchKernelGGL((gru_bwd_hs_kernel<float>), grid, dim3(256), shm, stream, dc, (const float*)tape, (const float*)WTfrag,
+                               (float*)dG, B, V, H, (const float*)dHs, ld_h);
         CPC_CHECK_LAUNCH();
         return CPC_OK;
     }

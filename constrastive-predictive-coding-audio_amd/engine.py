@@ -1602,7 +1602,12 @@ class CPCEngine:
 
 class GRUContext:
     """AudioGRUModel as the context network (audio_model.py:47-77): one batched input-projection GEMM for all V steps, the
-    persistent GRU kernels for the recurrence, GEMMs for the weight gradients and for dz."""
+    persistent GRU kernels for the recurrence, GEMMs for the weight gradients and for dz.
+
+    AudioGRUModel(num_layers = L > 1): layer 0 is the code below, launch for launch; layer l >= 1 (``self.upper[l - 1]``) has its own
+    operands, input projections, hidden states, tape and dG, reads the hidden states of the layer below as its input rows and runs
+    behind it (layers back to back, DESIGN.md "Stacked GRU").  Backward: the top layer takes dc (cpc_gru_bwd); each layer below takes
+    the gradient its hidden states receive from the input projection above, one row per (item, step) (cpc_gru_bwd_steps)."""
 
     ahead_ok = True       # prepare_weights is a pure function of the parameters (CPCEngine.prepare_ahead)
 
@@ -1617,6 +1622,30 @@ class GRUContext:
             raise NotImplementedError(f"HIP GRU kernel: hidden size must be <= 512 and a multiple of 32 in bf16, of 16 in float32 "
                                       f"(this engine: {'bf16' if ch == 8 else 'float32'}, hidden size {self.H})")
         self.prefix = "autoregressive_model.gruCell."
+        self.L = int(getattr(ar, "num_layers", 1))
+        self.upper = []           # layers 1 .. L-1 (_alloc_upper)
+
+    def _alloc_upper(self):
+        """Per-layer state of layers 1 .. L-1: input size H, input rows = the hidden states h_1 .. h_V of the layer below."""
+        e = self.eng
+        B, V, H, dev, dt = e.B, e.V, self.H, e.device, e.dt
+        for i in range(self.L - 1):
+            lay = SimpleNamespace(prefix=f"autoregressive_model.upper_cells.{i}.")
+            lay.w_ih = torch.empty(3 * H * H, device=dev, dtype=dt)           # [3H][H]
+            lay.w_ih_t = torch.empty(H * 3 * H, device=dev, dtype=dt)         # [H][3H]
+            lay.w_hh_frag = torch.empty(3 * H * H, device=dev, dtype=dt)
+            lay.w_hh_t_frag = torch.empty(3 * H * H, device=dev, dtype=dt)
+            lay.Gi = torch.empty(B * V * 3 * H, device=dev, dtype=dt)
+            lay.Hall = torch.empty(B * (V + 1) * H, device=dev, dtype=dt)
+            lay.tape = torch.zeros(self.tape.numel(), device=dev, dtype=dt)
+            lay.dG = torch.empty(B * V * 4 * H, device=dev, dtype=dt)
+            lay.split_ih = e._pick_split(3 * H, H, B * V)
+            lay.split_hh = self.split_hh
+            lay.ev = torch.cuda.Event()
+            self.upper.append(lay)
+        if self.upper:
+            self.c_low = torch.empty(self.L - 1, B, H, device=dev, dtype=torch.float32)    # last hidden state of every layer below the top
+            self.dH = torch.empty(B * V * H, device=dev, dtype=dt)       # gradient at h_1 .. h_V of the layer being differentiated
 
     def allocate(self):
         e = self.eng
@@ -1631,12 +1660,15 @@ class GRUContext:
         self.dG = torch.empty(B * V * 4 * H, device=dev, dtype=dt)       # [dr | du | dn | dn*r] per (item, step)
         self.split_ih = e._pick_split(3 * H, E, B * V)
         self.split_hh = e._pick_split(2 * H, H, B * V)
+        self._alloc_upper()
         self.scratch = torch.empty(self.slab_floats(), device=dev, dtype=torch.float32)     # side-stream workspace
         self._ev = torch.cuda.Event()
 
     def slab_floats(self):
+        """The side-stream workspace is shared by all layers (their parameter gradients run there one after the other): the largest."""
         e, H = self.eng, self.H
-        return max(self.split_ih * 3 * H * e.E, self.split_hh * 2 * H * H, e.colsum_blocks * 4 * H)
+        return max(self.split_ih * 3 * H * e.E, self.split_hh * 2 * H * H, e.colsum_blocks * 4 * H,
+                   *[lay.split_ih * 3 * H * H for lay in self.upper])
 
     def prepare_weights(self):
         e, H, E, code = self.eng, self.H, self.eng.E, self.eng.code
@@ -1646,6 +1678,12 @@ class GRUContext:
         _hip.call("cpc_cast2d", _hip.ptr(w_ih), _hip.ptr(self.w_ih_t), E, 3 * H, 1, E, code)
         _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(self.w_hh_frag), 3 * H, H, H, 0, code)
         _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(self.w_hh_t_frag), H, 3 * H, H, 1, code)
+        for lay in self.upper:
+            w_ih, w_hh = p[lay.prefix + "weight_ih"], p[lay.prefix + "weight_hh"]
+            _hip.call("cpc_cast2d", _hip.ptr(w_ih), _hip.ptr(lay.w_ih), 3 * H, H, H, 1, code)
+            _hip.call("cpc_cast2d", _hip.ptr(w_ih), _hip.ptr(lay.w_ih_t), H, 3 * H, 1, H, code)
+            _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(lay.w_hh_frag), 3 * H, H, H, 0, code)
+            _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(lay.w_hh_t_frag), H, 3 * H, H, 1, code)
 
     def forward(self):
         e, H = self.eng, self.H
@@ -1656,9 +1694,13 @@ class GRUContext:
         # reset_hidden=False (audio_model.py:69, :75): the last hidden state of the previous call is this call's initial one
         carry = not getattr(self.ar, "reset_hidden", True)
         h0 = self.ar.hidden if carry else None
-        if h0 is not None and (tuple(h0.shape) != (B, H) or h0.device != e.c.device):
-            raise ValueError(f"carried GRU state has shape {tuple(h0.shape)} on {h0.device}, this call needs ({B}, {H}) on {e.c.device}")
+        want = (B, H) if self.L == 1 else (self.L, B, H)          # one state per layer of a stack
+        if h0 is not None and (tuple(h0.shape) != want or h0.device != e.c.device):
+            raise ValueError(f"carried GRU state has shape {tuple(h0.shape)} on {h0.device}, this call needs {want} on {e.c.device}")
         self.carried = h0 is not None
+        if self.L > 1:
+            self._forward_stack(h0, carry)
+            return
         if h0 is not None:
             _hip.call("cpc_gru_fwd_h0", _hip.ptr(self.Gi), _hip.ptr(self.w_hh_frag), _hip.ptr(p.get(self.prefix + "bias_hh")),
                       _hip.ptr(h0.detach().float().contiguous()), _hip.ptr(self.Hall), _hip.ptr(self.tape), _hip.ptr(e.c), B, V, H, code)
@@ -1667,9 +1709,32 @@ class GRUContext:
                       _hip.ptr(self.Hall), _hip.ptr(self.tape), _hip.ptr(e.c), B, V, H, code)
         self.ar.hidden = e.c.detach().clone() if carry else None
 
+    def _forward_stack(self, h0, carry):
+        """The recurrences of a stack, bottom to top (layer 0's input projection is in ``Gi`` already).  Layer l >= 1 projects the rows
+        h_1 .. h_V of the layer below straight out of its hidden-state buffer (item stride (V + 1) H, from element H on)."""
+        e, H = self.eng, self.H
+        p, code, B, V = e.model._param, e.code, e.B, e.V
+        h0 = None if h0 is None else h0.detach().float().contiguous()
+        below = None
+        for l, lay in enumerate([self] + self.upper):
+            if below is not None:
+                _hip.gemm_nt(_hip.ptr(below.Hall, H), _hip.ptr(lay.w_ih), _hip.ptr(lay.Gi), B * V, 3 * H, H, H, H, 3 * H, code,
+                             bias=_hip.ptr(p.get(lay.prefix + "bias_ih")), a_rpi=V, a_item=(V + 1) * H,
+                             a_extent=B * (V + 1) * H - H)
+            c_out = e.c if l == self.L - 1 else self.c_low[l]
+            args = (_hip.ptr(lay.Hall), _hip.ptr(lay.tape), _hip.ptr(c_out), B, V, H, code)
+            if h0 is not None:
+                _hip.call("cpc_gru_fwd_h0", _hip.ptr(lay.Gi), _hip.ptr(lay.w_hh_frag), _hip.ptr(p.get(lay.prefix + "bias_hh")),
+                          _hip.ptr(h0[l]), *args)
+            else:
+                _hip.call("cpc_gru_fwd", _hip.ptr(lay.Gi), _hip.ptr(lay.w_hh_frag), _hip.ptr(p.get(lay.prefix + "bias_hh")), *args)
+            below = lay
+        self.ar.hidden = torch.cat([self.c_low, e.c.detach().unsqueeze(0)], 0) if carry else None
+
     def c_operand(self):
-        """(tensor, element offset, item stride): storage-dtype rows of c, one per item (h_V inside the hidden-state buffer)."""
-        return self.Hall, self.eng.V * self.H, (self.eng.V + 1) * self.H
+        """(tensor, element offset, item stride): storage-dtype rows of c, one per item (h_V inside the top layer's hidden-state buffer)."""
+        top = self.upper[-1] if self.upper else self
+        return top.Hall, self.eng.V * self.H, (self.eng.V + 1) * self.H
 
     def c_float(self):
         return self.eng.c
@@ -1686,7 +1751,22 @@ class GRUContext:
         if phase == 1:               # gradient penalty, pass 1: dc is the adjoint of the summed scores (gp_grads starts from it)
             self._gp_buffers()
             self.gp_dc1.copy_(dc)
-        _hip.call("cpc_gru_bwd", _hip.ptr(dc), _hip.ptr(self.tape), _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
+        if self.upper:
+            # top layer from dc; then, layer by layer, dH = dG_l[:, :3H] W_ih_l (one row per (item, step): the layout cpc_gru_bwd_steps
+            # reads) and the sweep of the layer below.  Each layer's parameter gradients follow its dG on the side stream, in this order:
+            # they share one workspace, and the encoder's gradient-ready hook runs on that stream behind all of them.
+            layers = [self] + self.upper
+            for l in range(self.L - 1, 0, -1):
+                lay, low = layers[l], layers[l - 1]
+                if l == self.L - 1:
+                    _hip.call("cpc_gru_bwd", _hip.ptr(dc), _hip.ptr(lay.tape), _hip.ptr(lay.w_hh_t_frag), _hip.ptr(lay.dG), B, V, H, code)
+                with e.side(lay.ev):
+                    self._layer_params(lay, _hip.ptr(low.Hall, H), H, (V + 1) * H)
+                _hip.gemm_nt(_hip.ptr(lay.dG), _hip.ptr(lay.w_ih_t), _hip.ptr(self.dH), B * V, H, 3 * H, 4 * H, 3 * H, H, code)
+                _hip.call("cpc_gru_bwd_steps", None, _hip.ptr(self.dH), C.c_longlong(H), _hip.ptr(low.tape), _hip.ptr(low.w_hh_t_frag),
+                          _hip.ptr(low.dG), B, V, H, code)
+        else:
+            _hip.call("cpc_gru_bwd", _hip.ptr(dc), _hip.ptr(self.tape), _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
         # the GRU's parameter gradients (ten short launches) are off the critical path dG -> dz -> encoder backward: side stream
         with e.side(self._ev):
             self.backward_params()
@@ -1697,31 +1777,44 @@ class GRUContext:
             dtop.view(B, Ltop, E)[:, t0:t0 + V, :].add_(self.gp_dz.view(B, V, E))
 
     def backward_params(self):
-        """Parameter gradients of the recurrence from dG (all steps), on the current stream."""
+        """Parameter gradients of the recurrence from dG (all steps), on the current stream (layer 0 of a stack)."""
+        e = self.eng
+        E, t0 = e.E, e.T - e.K - e.V
+        self._layer_params(self, _hip.ptr(e.act[-1], t0 * E), E, e.geo.alloc[-1] * E)
+
+    def _layer_params(self, lay, x, In, x_item):
+        """Parameter gradients of one layer (``self`` for layer 0, an entry of ``self.upper`` above it) from its dG.  ``x``: pointer to
+        its input rows, V rows of ``In`` elements per item, items ``x_item`` elements apart (the encoder's top buffer for layer 0, rows
+        h_1 .. h_V of the hidden-state buffer below for the others)."""
         e, H = self.eng, self.H
-        g, code, B, V, E, K = e.model._grad, e.code, e.B, e.V, e.E, e.K
-        Ltop, t0, top = e.geo.alloc[-1], e.T - K - V, e.act[-1]
+        g, code, B, V = e.model._grad, e.code, e.B, e.V
         # dG[b][t] = [dr | du | dn | dn*r]: columns [0,3H) are the gradient of the input-projection term, columns [0,2H) and
         # [3H,4H) that of the recurrent term
-        g_ih, g_hh = g[self.prefix + "weight_ih"], g[self.prefix + "weight_hh"]
+        g_ih, g_hh = g[lay.prefix + "weight_ih"], g[lay.prefix + "weight_hh"]
         sl = self.scratch
-        e._tn_to_grad(_hip.ptr(self.dG), _hip.ptr(top, t0 * E), g_ih, B * V, 3 * H, E, 4 * H, E, self.split_ih,
-                      b_rpi=V, b_item=Ltop * E, scratch=sl)
-        e._tn_to_grad(_hip.ptr(self.dG), _hip.ptr(self.Hall), g_hh, B * V, 2 * H, H, 4 * H, H, self.split_hh,
+        e._tn_to_grad(_hip.ptr(lay.dG), x, g_ih, B * V, 3 * H, In, 4 * H, In, lay.split_ih,
+                      b_rpi=V, b_item=x_item, scratch=sl)
+        e._tn_to_grad(_hip.ptr(lay.dG), _hip.ptr(lay.Hall), g_hh, B * V, 2 * H, H, 4 * H, H, lay.split_hh,
                       b_rpi=V, b_item=(V + 1) * H, scratch=sl)
-        e._tn_to_grad(_hip.ptr(self.dG, 3 * H), _hip.ptr(self.Hall), g_hh, B * V, H, H, 4 * H, H, self.split_hh,
+        e._tn_to_grad(_hip.ptr(lay.dG, 3 * H), _hip.ptr(lay.Hall), g_hh, B * V, H, H, 4 * H, H, lay.split_hh,
                       b_rpi=V, b_item=(V + 1) * H, grad_offset=2 * H * H, scratch=sl)
-        if (self.prefix + "bias_ih") in g:
-            g_bi, g_bh = g[self.prefix + "bias_ih"], g[self.prefix + "bias_hh"]
+        if (lay.prefix + "bias_ih") in g:
+            g_bi, g_bh = g[lay.prefix + "bias_ih"], g[lay.prefix + "bias_hh"]
             M = B * V
             nb = min(e.colsum_blocks, max(1, M // 64))
-            _hip.call("cpc_colsum", _hip.ptr(self.dG), _hip.ptr(sl), M, 4 * H, 4 * H, nb, code)
+            _hip.call("cpc_colsum", _hip.ptr(lay.dG), _hip.ptr(sl), M, 4 * H, 4 * H, nb, code)
             _hip.call("cpc_reduce_slabs", _hip.ptr(sl), _hip.ptr(g_bi), 1, 3 * H, nb, 4 * H, 1, 1, 0, 0)
             _hip.call("cpc_reduce_slabs", _hip.ptr(sl), _hip.ptr(g_bh), 1, 2 * H, nb, 4 * H, 1, 1, 0, 0)
             _hip.call("cpc_reduce_slabs", _hip.ptr(sl, 3 * H), _hip.ptr(g_bh, 2 * H), 1, H, nb, 4 * H, 1, 1, 0, 0)
 
     # ---- Wasserstein gradient penalty (scalogram_engine._gp_step; exact-f32 mode): tangent of c, penalty parts of the gradients
+    GP_STACK_REASON = ("the gradient penalty through a stacked GRU (num_layers > 1) is not implemented: its reverse sweep "
+                       "(cpc_gru_gp_bwd) differentiates ONE recurrence from the adjoint at its last state, and a lower layer of a "
+                       "stack would need the second-order adjoints of every step handed down from the layer above")
+
     def _gp_buffers(self):
+        if self.L > 1:
+            raise NotImplementedError(self.GP_STACK_REASON)
         if getattr(self, "gp_tape", None) is not None:
             return
         e, H = self.eng, self.H
@@ -1744,7 +1837,7 @@ class GRUContext:
         e, H = self.eng, self.H
         p, code, B, V, E, K = e.model._param, e.code, e.B, e.V, e.E, e.K
         Ltop, t0 = e.geo.alloc[-1], e.T - K - V
-        self._gp_buffers()
+        self._gp_buffers()          # (raises for a stack, before any GPU work)
         _hip.gemm_nt(_hip.ptr(top_t, t0 * E), _hip.ptr(self.w_ih), _hip.ptr(self.gp_GiT), B * V, 3 * H, E, E, E, 3 * H, code,
                      a_rpi=V, a_item=Ltop * E)
         _hip.call("cpc_cast2d", _hip.ptr(p[self.prefix + "weight_hh"]), _hip.ptr(self.gp_whh_t), H, 3 * H, 1, H, code)

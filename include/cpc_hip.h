@@ -67,6 +67,8 @@ extern "C" {
  *    cpc_nce_banked_workspace_floats, cpc_nce_loss_banked.
  *    Added later under 9 (backward compatible, no entry point changed): waveform augmentation cpc_wave_power_chunks, cpc_wave_power,
  *    cpc_wave_augment.
+ *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_gru_bwd_steps, the backward sweep of a GRU layer that
+ *    receives a gradient at every hidden state (a lower layer of AudioGRUModel(num_layers > 1)).
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -579,6 +581,19 @@ int cpc_gru_fwd_h0(const void* Gi, const void* Wfrag, const float* bhh, const fl
  * WTfrag = cpc_prep_frag(weight_hh, transpose=1) ([H][3H] logical). */
 int cpc_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
                 void* stream);
+/* The same sweep for a layer that is not the top of a stack (AudioGRUModel(num_layers > 1)): a gradient arrives at EVERY hidden state.
+ *   dHs   T   rows of H elements, row (b, t) at element (b V + t) ld_h: the gradient that reaches h_{t+1} = Hall[b][t+1] from outside
+ *             the recurrence (for a stack: dG_above[:, :3H] W_ih_above, which cpc_gemm_nt writes in exactly this layout, ld_h = H).
+ *             ld_h >= H and a multiple of 8 (bf16) / 4 (f32) elements, the base 16-byte aligned; columns [H, ld_h) and the rows of
+ *             items >= B are never read.  NULL: the call IS cpc_gru_bwd (same kernels, same bits; dc is then required).
+ *   dc    f32 [B][H] the gradient at the last hidden state, or NULL = zeros (a lower layer has none); the last state receives
+ *             dc + dHs[:, V-1].
+ * Step t starts from d = dh + dHs[b][t]; both the gate derivatives and the dh u term that goes on to step t - 1 use this d.
+ * tape, WTfrag, dG, the supported H / dtype and the kernel choice (cpc_gru_set_streaming included) are cpc_gru_bwd's.
+ * CPC_EINVAL before any launch: NULL tape / WTfrag / dG, dc and dHs both NULL, B < 1, V < 1, an H or dtype cpc_gru_bwd refuses,
+ * a bad ld_h with dHs given.  (Added under ABI 9: no existing entry point changed.) */
+int cpc_gru_bwd_steps(const float* dc, const void* dHs, long long ld_h, const void* tape, const void* WTfrag, void* dG, int B, int V,
+                      int H, int dtype, void* stream);
 
 /* The Wasserstein gradient penalty through AudioGRUModel (contrastive_estimation_training.py:144-158: loss.backward() through
  * torch.autograd.grad(..., create_graph=True), here for the GRUCell loop of audio_model.py:66-77).  f32 only, H <= 512.

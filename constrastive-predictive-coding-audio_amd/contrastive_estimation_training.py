@@ -10,14 +10,16 @@ DeterministicSampler :363-382, grad_mean_var :385-391).  ``train`` has two route
   all-reduced over RCCL before the update (per-GPU in-batch negatives).
 * generic: any other score function or optimizer: the model forward and backward run on the HIP path through the autograd
   bridge, the score function is the caller's, and the loss (:106-122, :141) and its gradient come from the same loss kernels
-  (``_InfoNCE``).  ``validate`` takes its per-step losses / accuracies from ``cpc_nce_eval`` on both routes.
+  (``_InfoNCE``, whatever the candidate selection: in-batch, sampled or grouped).  ``validate`` takes its per-step losses / accuracies from ``cpc_nce_eval`` on both routes.
 """
 from __future__ import annotations
 
 import collections
 import ctypes
+import itertools
 import math
 import random
+import types
 
 import numpy as np
 import torch
@@ -301,30 +303,53 @@ def _score_layout(scores4, all_timesteps):
     return S, ld
 
 
+def _step_block_grads(dS, B, K, d_loss):
+    """The default branch's d loss / d scores as autograd wants it: the K equal-step blocks dS[k][b][b'] (rows padded, as
+    _score_layout lays them out) times d_loss on the [b, k, b', k] diagonal of a (B, K, B, K) tensor of zeros."""
+    d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
+    torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
+    return d
+
+
 class _InfoNCE(torch.autograd.Function):
     """Loss of the train step (reference :108-122, :141) from a 4-D score tensor, through the same kernels as the fused route
-    (cpc_nce_loss / cpc_nce_loss_all with the score function already applied): returns (loss incl. regulariser, max score,
-    NaN indicator of the loss before the regulariser); the backward hands d loss / d scores back to autograd."""
+    (the score function already applied): returns (loss incl. regulariser, max score, NaN indicator of the loss before the
+    regulariser); the backward hands d loss / d scores back to autograd.  selection, shaped like engine.CPCEngine._nce_loss's:
+      None: every other batch item is a candidate (cpc_nce_loss; cpc_nce_loss_all with all_timesteps);
+      ("sampled", n_neg, seed, draw): n_neg seeded negatives per target (cpc_nce_loss_sampled; DESIGN.md, "Sampled negatives");
+      ("grouped", groups, mode, n_neg, seed, draw): candidates by group id (cpc_nce_loss_grouped; DESIGN.md, "Grouped negatives");
+        groups: int32 device tensor [B]; mode 0 = same, 1 = other; n_neg 0 = every eligible row.
+    A selection is defined for the default branch only."""
 
     @staticmethod
-    def forward(ctx, scores4, all_timesteps, regularization):
+    def forward(ctx, scores4, all_timesteps, regularization, selection=None):
         import ctypes as C
         from . import _hip
-        _need_gpu(scores4, "the InfoNCE loss")
+        kind = selection[0] if selection is not None else None
+        assert kind is None or not all_timesteps, "a candidate selection exists for score_over_all_timesteps=False only"
+        # every entry point cpc_nce_loss<suffix> has its cpc_nce<suffix>_workspace_floats
+        suffix = "_all" if all_timesteps else f"_{kind}" if kind else ""
+        _need_gpu(scores4, "the InfoNCE loss" + (f" over {kind} negatives" if kind else ""))
         B, K = scores4.shape[0], scores4.shape[1]
+        P, u64 = _hip.ptr, lambda v: C.c_ulonglong(int(v) & (2 ** 64 - 1))
+        pick = ()          # the entry point's arguments between the regulariser and the dtype
+        if kind == "sampled":
+            n_neg, seed, draw = selection[1:]
+            pick = (check_negatives(B, n_neg), u64(seed), u64(draw))
         S, ld = _score_layout(scores4.detach(), all_timesteps)
         dev, f32 = S.device, torch.float32
+        if kind == "grouped":
+            groups, mode, n_neg, seed, draw = selection[1:]
+            if groups.dtype != torch.int32 or tuple(groups.shape) != (B,) or groups.device != dev:
+                raise ValueError(f"groups must be an int32 tensor of shape [{B}] on {dev}")
+            groups = groups.contiguous()
+            pick = (P(groups), int(mode), int(n_neg), u64(seed), u64(draw))
         out = torch.zeros(8, device=dev, dtype=f32)
         dS, dST = torch.zeros_like(S), torch.zeros_like(S)
-        if all_timesteps:
-            ws = torch.empty(int(_hip.lib().cpc_nce_all_workspace_floats(B, K)), device=dev, dtype=f32)
-            ST = S.t().contiguous()
-            _hip.call("cpc_nce_loss_all", _hip.ptr(S), _hip.ptr(ST), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
-                      C.c_float(regularization), _hip.F32)
-        else:
-            ws = torch.empty(int(_hip.lib().cpc_nce_workspace_floats(B, K)), device=dev, dtype=f32)
-            _hip.call("cpc_nce_loss", _hip.ptr(S), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
-                      C.c_float(regularization), _hip.F32)
+        ws = torch.empty(int(getattr(_hip.lib(), f"cpc_nce{suffix}_workspace_floats")(B, K)), device=dev, dtype=f32)
+        ST = S.t().contiguous() if all_timesteps else None          # cpc_nce_loss_all also reads the transposed scores
+        scores = (P(S), P(ST)) if all_timesteps else (P(S),)
+        _hip.call("cpc_nce_loss" + suffix, *scores, P(dS), P(dST), P(out), P(ws), B, K, ld, 0, C.c_float(regularization), *pick, _hip.F32)
         ctx.save_for_backward(dS)
         ctx.meta = (B, K, bool(all_timesteps), scores4.dtype)
         ctx.mark_non_differentiable(out)
@@ -334,81 +359,8 @@ class _InfoNCE(torch.autograd.Function):
     def backward(ctx, d_loss, _d_out):
         (dS,) = ctx.saved_tensors
         B, K, all_t, dtype = ctx.meta
-        if all_t:
-            d = dS.view(B, K, B, K) * d_loss
-        else:
-            d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
-            torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
-        return d.to(dtype), None, None
-
-
-class _SampledInfoNCE(torch.autograd.Function):
-    """_InfoNCE's default branch over n_neg seeded negatives per target (cpc_nce_loss_sampled; DESIGN.md, "Sampled negatives"): the
-    generic route's loss when ContrastiveEstimationTrainer.num_negatives is set.  Same returns as _InfoNCE."""
-
-    @staticmethod
-    def forward(ctx, scores4, regularization, n_neg, seed, draw):
-        import ctypes as C
-        from . import _hip
-        _need_gpu(scores4, "the InfoNCE loss over sampled negatives")
-        B, K = scores4.shape[0], scores4.shape[1]
-        n_neg = check_negatives(B, n_neg)
-        S, ld = _score_layout(scores4.detach(), False)
-        dev, f32 = S.device, torch.float32
-        out = torch.zeros(8, device=dev, dtype=f32)
-        dS, dST = torch.zeros_like(S), torch.zeros_like(S)
-        ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(B, K)), device=dev, dtype=f32)
-        _hip.call("cpc_nce_loss_sampled", _hip.ptr(S), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
-                  C.c_float(regularization), n_neg, C.c_ulonglong(int(seed) & (2 ** 64 - 1)), C.c_ulonglong(int(draw) & (2 ** 64 - 1)),
-                  _hip.F32)
-        ctx.save_for_backward(dS)
-        ctx.meta = (B, K, scores4.dtype)
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
-
-    @staticmethod
-    def backward(ctx, d_loss, _d_out):
-        (dS,) = ctx.saved_tensors
-        B, K, dtype = ctx.meta
-        d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
-        torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
-        return d.to(dtype), None, None, None, None
-
-
-class _GroupedInfoNCE(torch.autograd.Function):
-    """_SampledInfoNCE's twin for candidates by group id (cpc_nce_loss_grouped; DESIGN.md, "Grouped negatives"): the generic route's
-    loss when ContrastiveEstimationTrainer.negative_groups is set.  groups: int32 device tensor [B]; mode 0 = same, 1 = other; n_neg 0
-    = every eligible row.  Same returns as _InfoNCE."""
-
-    @staticmethod
-    def forward(ctx, scores4, regularization, groups, mode, n_neg, seed, draw):
-        import ctypes as C
-        from . import _hip
-        _need_gpu(scores4, "the InfoNCE loss over grouped negatives")
-        B, K = scores4.shape[0], scores4.shape[1]
-        S, ld = _score_layout(scores4.detach(), False)
-        dev, f32 = S.device, torch.float32
-        if groups.dtype != torch.int32 or tuple(groups.shape) != (B,) or groups.device != dev:
-            raise ValueError(f"groups must be an int32 tensor of shape [{B}] on {dev}")
-        groups = groups.contiguous()
-        out = torch.zeros(8, device=dev, dtype=f32)
-        dS, dST = torch.zeros_like(S), torch.zeros_like(S)
-        ws = torch.empty(int(_hip.lib().cpc_nce_grouped_workspace_floats(B, K)), device=dev, dtype=f32)
-        _hip.call("cpc_nce_loss_grouped", _hip.ptr(S), _hip.ptr(dS), _hip.ptr(dST), _hip.ptr(out), _hip.ptr(ws), B, K, ld, 0,
-                  C.c_float(regularization), _hip.ptr(groups), int(mode), int(n_neg), C.c_ulonglong(int(seed) & (2 ** 64 - 1)),
-                  C.c_ulonglong(int(draw) & (2 ** 64 - 1)), _hip.F32)
-        ctx.save_for_backward(dS)
-        ctx.meta = (B, K, scores4.dtype)
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
-
-    @staticmethod
-    def backward(ctx, d_loss, _d_out):
-        (dS,) = ctx.saved_tensors
-        B, K, dtype = ctx.meta
-        d = torch.zeros(B, K, B, K, device=dS.device, dtype=torch.float32)
-        torch.diagonal(d, dim1=1, dim2=3).copy_(dS[:, :, :B].permute(1, 2, 0) * d_loss)
-        return d.to(dtype), None, None, None, None, None, None
+        d = dS.view(B, K, B, K) * d_loss if all_t else _step_block_grads(dS, B, K, d_loss)
+        return d.to(dtype), None, None, None
 
 
 class _RecordingSampler:
@@ -429,6 +381,145 @@ class _RecordingSampler:
 
 
 _NEGATIVE_GROUP_MODES = {"same_file": "same", "other_files": "other"}
+
+
+def _ring_depth(trainer):
+    """Slots of the readback ring and of the snapshot ring: the steps that can be in flight before the host has read the oldest."""
+    return trainer.host_sync_interval + trainer.host_sync_lag + 2
+
+
+class _StepReadback:
+    """A run's per-step values on their way to the logger: ``push`` queues a step's row right behind its launches, ``flush`` reads rows
+    back in order, feeds the logger's meters and sets the trainer's last_grad_norm / last_temperature.  Row layout, the one both
+    sides use: the loss kernel's result cell (cpc_nce_loss: out[0], out[1], out[5]), with clipping the norm before clipping and the
+    coefficient applied behind it (FusedAdam.clip_state[0:2] on the fused routes), with a device temperature the value as the step
+    left it (tstate[5]) behind those."""
+    LOSS, MAX_SCORE, NAN = 0, 1, 5
+    GRAD_NORM, CLIP_COEF = 6, 7
+
+    def __init__(self, trainer, optimizer, clip, fused, on_gpu, device_temp, temp_route):
+        self.trainer, self.optimizer = trainer, optimizer
+        self.clip, self.fused, self.on_gpu = clip, fused, on_gpu
+        self.device_temp, self.temp_route = device_temp, temp_route
+        self.base_width = (self.CLIP_COEF if clip else self.NAN) + 1
+        self.TEMPERATURE = self.base_width if device_temp is not None else None
+        self.width = self.base_width + (1 if device_temp is not None else 0)
+        self.ring, self.ring_pos = [], 0          # pinned host buffers, handed out in turn
+        self.pending = []                         # (step, row, event, lr, host temperature) not yet read back
+        self.bad_grad_norm = False                # the NaN step flush() returned had a finite loss: the gradient was the cause
+
+    def push(self, step, vals):
+        """Queues a step's (loss, max score) for the logger.  On the GPU they travel to a pinned host buffer right behind the
+        step's own kernels and an event marks their arrival: reading them later does not wait for LATER steps' work, which a
+        synchronous read of a device tensor — queued behind everything launched since — would."""
+        tr = self.trainer
+        host_tau = tr.score_function.temperature if self.temp_route == "host" else None
+        if not self.on_gpu:
+            self.pending.append((step, vals.detach()[:self.width].clone(), None, tr.last_lr, host_tau))
+            return
+        while len(self.ring) < _ring_depth(tr):          # (host_sync_interval / host_sync_lag raised while training)
+            self.ring.append(torch.empty(self.width, dtype=torch.float32, pin_memory=True))
+        buf = self.ring[self.ring_pos % len(self.ring)]
+        self.ring_pos += 1
+        if self.clip and self.fused:          # the engine's result cell and FusedAdam.clip_state: two copies, one event
+            buf[:self.GRAD_NORM].copy_(vals.detach()[:self.GRAD_NORM].float(), non_blocking=True)
+            buf[self.GRAD_NORM:self.base_width].copy_(self.optimizer.clip_state[:2], non_blocking=True)
+        else:
+            buf[:self.base_width].copy_(vals.detach()[:self.base_width].float(), non_blocking=True)
+        if self.device_temp is not None:          # the same buffer and event: no further wait
+            buf[self.TEMPERATURE:].copy_(self.device_temp.tstate[5:6], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append((step, buf, ev, tr.last_lr, host_tau))          # (the host knows the step's learning rate: it rides along)
+
+    def flush(self, keep=0):
+        """Reads back all pending steps but the ``keep`` most recent ones (in order); returns the step of a NaN loss."""
+        tr, logger, pending = self.trainer, self.trainer.logger, self.pending
+        n = max(len(pending) - keep, 0)
+        for step, vals, ev, lr_v, host_tau in pending[:n]:
+            if ev is not None:
+                ev.synchronize()
+            row = vals.tolist()
+            loss_v, score_v, nan_v = float(row[self.LOSS]), float(row[self.MAX_SCORE]), float(row[self.NAN])
+            if self.clip:
+                tr.last_grad_norm = float(row[self.GRAD_NORM])
+            tau_v = float(row[self.TEMPERATURE]) if self.device_temp is not None else host_tau
+            # reference order (:124-133 before :164-169): a NaN loss ends the run before anything is logged for that step
+            if nan_v != 0.0 or math.isnan(loss_v):
+                # (the indicator is also what cpc_grad_norm raises: a finite loss under it means the gradient was the cause)
+                self.bad_grad_norm = self.clip and not math.isnan(loss_v) and not math.isfinite(tr.last_grad_norm)
+                pending.clear()
+                return step
+            if logger is not None:
+                logger.loss_meter.update(loss_v)
+                logger.score_meter.update(score_v)
+                if self.clip and hasattr(logger, "grad_norm_meter"):
+                    logger.grad_norm_meter.update(tr.last_grad_norm)
+                if hasattr(logger, "lr_meter"):
+                    logger.lr_meter.update(lr_v)
+                if tau_v is not None and hasattr(logger, "temperature_meter"):
+                    logger.temperature_meter.update(tau_v)
+                logger.log(step)
+            elif tr.verbose:
+                print("loss at step step " + str(step) + ":", loss_v)
+            if tau_v is not None:
+                tr.last_temperature = tau_v
+        del pending[:n]
+        return None
+
+
+class _NanRollback:
+    """The host learns of a NaN loss host_sync_lag steps late; the steps launched meanwhile change nothing on the device that Adam
+    owns (their updates are skipped there), but their forward passes move the BatchNorm running statistics, and the host-side
+    step count advances.  Both are put back to where the reference leaves them (it returns inside the NaN step, after that step's
+    forward pass, :124-133): the buffers are snapshotted at the START of every step (one multi-tensor copy) and the snapshot of
+    step `nan + 1` is restored.  What cannot be taken back: the sampler has handed out the later batches.  The generic route reads
+    every step's loss at once and snapshots nothing."""
+
+    def __init__(self, trainer, optimizer, fused):
+        self.trainer, self.optimizer, self.fused = trainer, optimizer, fused
+        # (grouped by dtype, copied one dtype at a time: a mixed list — float32 statistics and int64 counters — takes _foreach_copy_'s
+        # per-tensor route, 40 device-to-device copies and 0.13 ms per configs[2] step; a uniform list is one multi-tensor kernel)
+        by_dtype = {}
+        for n_, b in trainer.model.named_buffers():
+            if "running_" in n_ or n_.endswith("num_batches_tracked"):
+                by_dtype.setdefault(str(b.dtype), []).append(b)
+        self.bufs = [by_dtype[k] for k in sorted(by_dtype)]          # BatchNorm's buffers, one list per dtype
+        self.ring, self.ring_pos, self.snaps = [], 0, {}          # snaps: step -> (ring slot or None, the optimizer's t)
+        if fused and self.bufs:          # the ring exists before the loop: no allocation inside the hot loop; models without BatchNorm keep none
+            self.ring = [self._slot() for _ in range(_ring_depth(trainer))]
+
+    def _slot(self):
+        return [[torch.empty_like(b) for b in group] for group in self.bufs]
+
+    @staticmethod
+    def _copy(dst, src):
+        for d, s in zip(dst, src):
+            torch._foreach_copy_(d, s)
+
+    def snapshot(self, step):
+        if not self.fused:
+            return
+        depth = _ring_depth(self.trainer)
+        dst = None
+        if self.bufs:
+            while len(self.ring) < depth:          # (host_sync_interval / host_sync_lag raised while training)
+                self.ring.append(self._slot())
+            dst = self.ring[self.ring_pos % depth]
+            self.ring_pos += 1
+            self._copy(dst, self.bufs)
+        self.snaps[step] = (dst, getattr(self.optimizer, "t", None))
+        for old_step in [k for k in self.snaps if k < step - depth + 1]:
+            del self.snaps[old_step]
+
+    def restore(self, step):
+        """After a NaN loss at ``step``: the statistics of the start of step + 1, the optimizer's count of the start of ``step``."""
+        later = self.snaps.get(step + 1)
+        if later is not None and later[0] is not None:          # statistics as they were after the NaN step's own forward pass
+            self._copy(self.bufs, later[0])
+        here = self.snaps.get(step)
+        if here is not None and here[1] is not None and hasattr(self.optimizer, "t"):
+            self.optimizer.t = here[1]                          # no update has happened since the start of the NaN step
 
 
 class ContrastiveEstimationTrainer:
@@ -839,14 +930,21 @@ class ContrastiveEstimationTrainer:
             return "device"
         return "device" if self._engine_normalized() and world == 1 else "host"
 
-    def _device_temperature(self, device):
-        """The DeviceTemperature this trainer keeps for its score function, made on first use."""
+    def _start_temperature(self, temp_route, device, start_step):
+        """_check_temperature's route at the start of a run.  "device": returns the DeviceTemperature this trainer keeps for its score
+        function, made on first use.  "host": the callable's constant is set to the schedule's value at ``start_step``; returns None."""
         sf = self.score_function
-        kept = self._temperature
-        if kept is None or sf.device_temperature is not kept or kept.device != torch.device(device):
-            kept = self._temperature = sf.make_device_temperature(device)
-            sf.device_temperature = kept
-        return kept
+        if temp_route == "device":
+            kept = self._temperature
+            if kept is None or sf.device_temperature is not kept or kept.device != torch.device(device):
+                kept = self._temperature = sf.make_device_temperature(device)
+                sf.device_temperature = kept
+            kept.bind(None)          # (a captured step of an earlier call had it read the step from its optimizer's count)
+            return kept
+        if temp_route == "host":          # the callable's constant follows the schedule; no device value takes part
+            sf.device_temperature = self._temperature = None
+            sf.temperature = sf.schedule.value(int(start_step))
+        return None
 
     def _check_augmentation(self):
         """None without augmentation; else (the WaveAugmentation, protect(L) -> the first protected sample of clips of L samples).
@@ -879,13 +977,12 @@ class ContrastiveEstimationTrainer:
         return aug, protect
 
     @staticmethod
-    def _augmented(batches, aug, protect, counter, clip_offset, with_indices):
-        """The batches of ``batches`` augmented: batch i of the run (counter[0], which goes on over the epochs) at step i.  Every
-        output is a fresh tensor, so the one in hand stays valid while the following batch is prepared."""
+    def _augmented(batches, aug, protect, steps, clip_offset, with_indices):
+        """The batches of ``batches`` augmented: batch i of the run at step i (``steps``: the run's itertools.count, which goes on
+        over the epochs).  Every output is a fresh tensor, so the one in hand stays valid while the following batch is prepared."""
         for item in batches:
             batch = item[0] if with_indices else item
-            out = aug(batch, counter[0], clip_offset=clip_offset, protect_from=protect(batch.shape[1]))
-            counter[0] += 1
+            out = aug(batch, next(steps), clip_offset=clip_offset, protect_from=protect(batch.shape[1]))
             yield (out, item[1]) if with_indices else out
 
     @staticmethod
@@ -959,205 +1056,28 @@ class ContrastiveEstimationTrainer:
         grouping = self._check_negative_groups()
         bank_kw = self._bank_kw(self._check_negative_bank())
         augmenting = self._check_augmentation()
-        aug_counter = [int(continue_training_at_step)]          # the step of the next batch the augmentation sees
+        aug_steps = itertools.count(int(continue_training_at_step))          # the step of the next batch the augmentation sees
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
-        trust_ratio, trust_clip = self._check_trust()
-        ema_decay, ema_warmup = self._check_ema()
+        trust = self._check_trust()
+        ema = self._check_ema()
         device = self._device()
         rank, world = self._world()
         temp_route = self._check_temperature(world)
         self.model.train()
-        fused = self._fused() or self._engine_difference() or self._engine_normalized()
-        device_temp = None
-        if temp_route == "device":
-            device_temp = self._device_temperature(device)
-            device_temp.bind(None)          # (a captured step of an earlier call had it read the step from its optimizer's count)
-        elif temp_route == "host":          # the callable's constant follows the schedule; no device value takes part
-            self.score_function.device_temperature = self._temperature = None
-            self.score_function.temperature = self.score_function.schedule.value(int(continue_training_at_step))
+        device_temp = self._start_temperature(temp_route, device, continue_training_at_step)
         score_kw = self._score_kw()
-        if fused:
-            from .engine import FusedAdam, GlobalNegatives, GradAllReduce, GraphedStep
-            self.model._flatten_parameters(device)
-            graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
-            lamb = dict(trust_ratio=True, trust_clip=trust_clip) if trust_ratio else {}
-            if ema_decay is not None:          # (without a decay FusedAdam is called as before the keywords existed)
-                flat = self.model._flat_param
-                if self._ema is not None and (self._ema.shape != flat.shape or self._ema.device != flat.device):
-                    self.reset_ema()          # another model or device: the old average means nothing here
-                lamb.update(ema_decay=ema_decay, ema_warmup=ema_warmup, ema=self._ema)
-            if device_temp is not None:          # (without one FusedAdam is called as before the keyword existed)
-                lamb.update(temperature=device_temp)
-            optimizer = FusedAdam(self.model, lr=lr, device_step=graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                                  decay_filter=decay_filter, schedule=schedule, step_offset=int(continue_training_at_step), **lamb)
-            if ema_decay is not None:
-                self._ema, self._ema_owner = optimizer.ema, optimizer
-            self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
-            graph_steps = {}
-            glob_neg = {}
-            self.model.link_grads()
-            sync = GradAllReduce(self.model, optimizer=optimizer) if world > 1 else None
-        else:
-            self.model._flatten_parameters(device)
-            if trust_ratio:          # LAMB's decay is inside its direction: no multiply in front of the step
-                from .engine import TorchLamb
-                optimizer = TorchLamb(self.model.named_parameters(), lr=lr, weight_decay=weight_decay, decay_filter=decay_filter,
-                                      trust_clip=trust_clip)
-            else:
-                optimizer = self.optimizer(self.model.parameters(), lr=lr)
-        generic_ema = None
-        if ema_decay is not None and not fused:
-            from .engine import TorchEma
-            flat = self.model._flat_param
-            if self._ema is None or self._ema.shape != flat.shape or self._ema.device != flat.device:
-                self._ema = flat.detach().float().clone()
-            generic_ema = self._ema_owner = TorchEma(self.model.named_parameters(), ema_decay, ema_warmup, shadow=self._shadow_views())
-        decayed = []
-        if weight_decay > 0.0 and not fused and not trust_ratio:          # the generic route multiplies them itself, in front of optimizer.step()
-            from .engine import default_decay_filter
-            decayed = [p for n_, p in self.model.named_parameters() if (decay_filter or default_decay_filter)(n_, p)]
-        if self.optimizer_state is not None:
-            state, self.optimizer_state = self.optimizer_state, None
-            optimizer.load_state_dict(state)
-            if generic_ema is not None:          # (FusedAdam.load_state_dict has taken its "ema" itself)
-                entries = state.get("state", {})
-                names = [n for n, _ in self.model.named_parameters()]
-                if entries and all(i in entries and "ema" in entries[i] for i in range(len(names))):
-                    generic_ema.load_state_dict({"ema": {n: entries[i]["ema"] for i, n in enumerate(names)}})
-                else:
-                    with torch.no_grad():
-                        self._ema.copy_(self.model._flat_param.detach())
+        run = self._make_optimizer(lr, device, world, int(continue_training_at_step), max_grad_norm,
+                                   (weight_decay, decay_filter, schedule), trust, ema, device_temp)
+        optimizer, fused = run.optimizer, run.fused
         sampler = FileBatchSampler(index_count_per_file=self.dataset.get_example_count_per_file(),
                                    batch_size=batch_size * world, file_batch_size=self.file_batch_size, drop_last=True,
                                    verbose=self.verbose)
         if grouping is not None and grouping[1] is None:
             grouping = (grouping[0], file_group_ids(self.dataset.get_example_count_per_file()))
         self.training_step = continue_training_at_step
-        pending = []          # (step, device scalars) not yet read back
-        guarded = set()       # engines whose sticky NaN flag was cleared for this run
-
-        on_gpu = torch.device(device).type == "cuda"
-        ring, ring_pos = [], [0]
-
-        clip = max_grad_norm is not None
-        base_width = 8 if clip else 6     # with clipping: + the norm before clipping and the coefficient applied (clip_state[0:2])
-        width = base_width + (1 if device_temp is not None else 0)          # + the temperature as the step left it (tstate[5])
-
-        def stash(step, vals):
-            """Queues a step's (loss, max score) for the logger.  On the GPU they travel to a pinned host buffer right behind the
-            step's own kernels and an event marks their arrival: reading them later does not wait for LATER steps' work, which a
-            synchronous read of a device tensor — queued behind everything launched since — would."""
-            host_tau = self.score_function.temperature if temp_route == "host" else None
-            if not on_gpu:
-                pending.append((step, vals.detach()[:width].clone(), None, self.last_lr, host_tau))
-                return
-            need = self.host_sync_interval + self.host_sync_lag + 2
-            while len(ring) < need:
-                ring.append(torch.empty(width, dtype=torch.float32, pin_memory=True))
-            buf = ring[ring_pos[0] % len(ring)]
-            ring_pos[0] += 1
-            if clip and fused:          # the engine's result cell and FusedAdam.clip_state: two copies, one event
-                buf[:6].copy_(vals.detach()[:6].float(), non_blocking=True)
-                buf[6:base_width].copy_(optimizer.clip_state[:2], non_blocking=True)
-            else:
-                buf[:base_width].copy_(vals.detach()[:base_width].float(), non_blocking=True)
-            if device_temp is not None:          # the same buffer and event: no further wait
-                buf[base_width:].copy_(device_temp.tstate[5:6], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append((step, buf, ev, self.last_lr, host_tau))          # (the host knows the step's learning rate: it rides along)
-
-        bad_grad_norm = [False]
-
-        def flush(keep=0):
-            """Reads back all pending steps but the ``keep`` most recent ones (in order); returns the step of a NaN loss."""
-            n = max(len(pending) - keep, 0)
-            for step, vals, ev, lr_v, host_tau in pending[:n]:
-                if ev is not None:
-                    ev.synchronize()
-                row = vals.tolist()
-                loss_v, score_v, nan_v = float(row[0]), float(row[1]), float(row[5])        # cpc_nce_loss: out[0], out[1], out[5]
-                if clip:
-                    self.last_grad_norm = float(row[6])
-                tau_v = float(row[base_width]) if device_temp is not None else host_tau
-                # reference order (:124-133 before :164-169): a NaN loss ends the run before anything is logged for that step
-                if nan_v != 0.0 or math.isnan(loss_v):
-                    # (the indicator is also what cpc_grad_norm raises: a finite loss under it means the gradient was the cause)
-                    bad_grad_norm[0] = clip and not math.isnan(loss_v) and not math.isfinite(self.last_grad_norm)
-                    pending.clear()
-                    return step
-                if self.logger is not None:
-                    self.logger.loss_meter.update(loss_v)
-                    self.logger.score_meter.update(score_v)
-                    if clip and hasattr(self.logger, "grad_norm_meter"):
-                        self.logger.grad_norm_meter.update(self.last_grad_norm)
-                    if hasattr(self.logger, "lr_meter"):
-                        self.logger.lr_meter.update(lr_v)
-                    if tau_v is not None and hasattr(self.logger, "temperature_meter"):
-                        self.logger.temperature_meter.update(tau_v)
-                    self.logger.log(step)
-                elif self.verbose:
-                    print("loss at step step " + str(step) + ":", loss_v)
-                if tau_v is not None:
-                    self.last_temperature = tau_v
-            del pending[:n]
-            return None
-
-        # The host learns of a NaN loss host_sync_lag steps late; the steps launched meanwhile change nothing on the device that Adam
-        # owns (their updates are skipped there), but their forward passes move the BatchNorm running statistics, and the host-side
-        # step count advances.  Both are put back to where the reference leaves them (it returns inside the NaN step, after that step's
-        # forward pass, :124-133): the buffers are snapshotted at the START of every step (one multi-tensor copy) and the snapshot of
-        # step `nan + 1` is restored.  What cannot be taken back: the sampler has handed out the later batches.
-        bn_bufs = [b for n_, b in self.model.named_buffers() if "running_" in n_ or n_.endswith("num_batches_tracked")]
-        # (sorted by dtype, copied one dtype at a time: a mixed list — float32 statistics and int64 counters — takes _foreach_copy_'s
-        # per-tensor route, 40 device-to-device copies and 0.13 ms per configs[2] step; a uniform list is one multi-tensor kernel)
-        bn_bufs.sort(key=lambda b: str(b.dtype))
-        bn_groups = []
-        for i_, b_ in enumerate(bn_bufs):
-            if not bn_groups or bn_bufs[bn_groups[-1][0]].dtype != b_.dtype:
-                bn_groups.append([i_, i_ + 1])
-            else:
-                bn_groups[-1][1] = i_ + 1
-
-        def copy_groups(dst, src):
-            for lo_, hi_ in bn_groups:
-                torch._foreach_copy_(dst[lo_:hi_], src[lo_:hi_])
-        snap_ring, snap_pos, snaps = [], [0], {}
-        if fused and bn_bufs:          # the ring exists before the loop: no allocation inside the hot loop; models without BatchNorm keep none
-            snap_ring = [[torch.empty_like(b) for b in bn_bufs] for _ in range(self.host_sync_interval + self.host_sync_lag + 2)]
-
-        def snapshot(step):
-            if not fused:
-                return
-            depth = self.host_sync_interval + self.host_sync_lag + 2
-            if bn_bufs:
-                while len(snap_ring) < depth:          # (host_sync_interval / host_sync_lag raised while training)
-                    snap_ring.append([torch.empty_like(b) for b in bn_bufs])
-                dst = snap_ring[snap_pos[0] % depth]
-                snap_pos[0] += 1
-                copy_groups(dst, bn_bufs)
-            else:
-                dst = None
-            snaps[step] = (dst, getattr(optimizer, "t", None))
-            for old_step in [k for k in snaps if k < step - depth + 1]:
-                del snaps[old_step]
-
-        def nan_return(step):
-            later = snaps.get(step + 1)
-            if later is not None and later[0] is not None:          # statistics as they were after the NaN step's own forward pass
-                copy_groups(bn_bufs, later[0])
-            here = snaps.get(step)
-            if here is not None and here[1] is not None and hasattr(optimizer, "t"):
-                optimizer.t = here[1]                               # no update has happened since the start of the NaN step
-            self.training_step = step          # the reference leaves train() inside step `step`, before its update (:124-133)
-            self.reset_negative_bank()         # (its latest rows come from the NaN step and the ones launched behind it)
-            if bad_grad_norm[0]:
-                print("gradient norm not finite at step", step, "(max_grad_norm): no update was applied")
-            print("nan loss")
-            print("returned with nan loss at step", step)
-            return None
-
+        readback = _StepReadback(self, optimizer, run.clip, fused, device.type == "cuda", device_temp, temp_route)
+        rollback = _NanRollback(self, optimizer, fused)
         # A full collection of Python's cyclic garbage collector walks every tracked object of the process (38 - 43 ms with the module
         # trees of a model alive) and lands in whichever step crosses its allocation threshold — a GPU that is only a few steps of work
         # ahead of the host idles through it.  What is alive now stays alive for the whole run: collect once and freeze it, later
@@ -1165,20 +1085,18 @@ class ContrastiveEstimationTrainer:
         import gc
         gc.collect()
         gc.freeze()
-        prof = None
         for current_epoch in range(epochs):
             if self.verbose:
                 print("epoch", current_epoch)
-            ctx = torch.autograd.profiler.profile(use_device="cuda", enabled=profile)
-            with ctx as prof_ctx:
+            with torch.autograd.profiler.profile(use_device="cuda", enabled=profile) as prof_ctx:
                 ahead = None
-                if (fused and not graphed and self.preprocessing is not None and self.preprocess_ahead and device.type == "cuda"
+                if (fused and not run.graphed and self.preprocessing is not None and self.preprocess_ahead and device.type == "cuda"
                         and switches.preprocess_ahead()):
                     ahead = InputAhead(self._model_input, device)
                 batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world,
                                         with_indices=grouping is not None)
                 if augmenting is not None:          # in front of everything that sees a batch, the one preprocessed ahead included
-                    batches = self._augmented(batches, augmenting[0], augmenting[1], aug_counter, rank * int(batch_size),
+                    batches = self._augmented(batches, augmenting[0], augmenting[1], aug_steps, rank * int(batch_size),
                                               grouping is not None)
                 # (the sampler is read one batch ahead only where that batch is preprocessed ahead)
                 for batch, next_batch in (_with_next(batches) if ahead is not None else ((b_, None) for b_ in batches)):
@@ -1187,7 +1105,7 @@ class ContrastiveEstimationTrainer:
                         batch, batch_idx = batch
                         next_batch = next_batch[0] if next_batch is not None else None
                         groups_kw = self._groups_kw(grouping, batch_idx, device)
-                    snapshot(self.training_step)
+                    rollback.snapshot(self.training_step)
                     # the step's learning rate, before its first hook can fire (under use_graph the device evaluates the same factor)
                     self.last_lr = step_lr = lr if schedule is None else lr * schedule.factor(self.training_step)
                     if fused and schedule is not None:
@@ -1197,97 +1115,177 @@ class ContrastiveEstimationTrainer:
                     elif temp_route == "host":
                         self.score_function.temperature = score_kw["temperature"] = \
                             self.score_function.schedule.value(int(self.training_step))
-                    if fused and graphed:
-                        eng = self.model.engine(batch.shape[0], batch.shape[1], device)
-                        key = (batch.shape[0], batch.shape[1])
-                        if key not in graph_steps:
-                            graph_steps[key] = GraphedStep(eng, optimizer, self.score_function is softplus_score_function,
-                                                           float(self.regularization), bool(self.score_over_all_timesteps), **score_kw)
-                        if id(eng) not in guarded:
-                            eng.nan_flag().zero_()
-                            guarded.add(id(eng))
-                        vals = graph_steps[key](batch)
+                    if run.graphed:
+                        vals = self._graphed_step(run, batch, score_kw)
                     elif fused:
-                        if self.preprocessing is not None:
-                            if ahead is not None:
-                                if not ahead.pending:              # first step of the epoch: nothing was submitted beside a previous one
-                                    ahead.submit(batch)
-                                _, x_eng = ahead.take()
-                            else:
-                                x_eng = self._model_input(batch)
-                            eng = self.model.engine_for(x_eng)
-                            if ahead is not None and next_batch is not None:
-                                # the engine runs it behind its encoder's forward pass, where its main queue turns latency-bound
-                                eng.side_job = lambda nb=next_batch: ahead.submit(nb)
-                        else:
-                            x_eng = batch.contiguous()
-                            eng = self.model.engine(batch.shape[0], batch.shape[1], device)
-                        gneg = None
-                        if self.global_negatives and world > 1:
-                            gneg = glob_neg.get(id(eng))
-                            if gneg is None:
-                                gneg = glob_neg[id(eng)] = GlobalNegatives(eng)
-                        # the operand copies of the next step are rebuilt as soon as Adam has updated their parameters
-                        # (engine.CPCEngine.prepare_ahead; under data parallelism Adam follows each reduced gradient piece)
-                        optimizer.after_update = eng.prepare_ahead
-                        # NaN guard on the device (reference :124-133 returns before backward() / optimizer.step()): the loss
-                        # kernel raises the engine's sticky flag, every Adam launch of this and of later steps is a no-op while it
-                        # is up, and the host leaves train() when the step's indicator arrives (host_sync_lag steps later)
-                        if id(eng) not in guarded:
-                            eng.nan_flag().zero_()
-                            guarded.add(id(eng))
-                        optimizer.skip_flag = eng.nan_flag()
-                        if clip:
-                            optimizer.nan_pair = eng.nan_pair()
-                        if sync is not None:      # per-GPU negatives: mean of the shard gradients; global negatives: they add up
-                            sync.grad_scale = 1.0 if gneg is not None else 1.0 / world
-                        if self.wasserstein_gradient_penalty:
-                            # three passes through the network (scalogram_engine.ScalogramCPCEngine._gp_step); the parameter
-                            # gradients are complete only at the end, so Adam runs once, after them
-                            out = eng.loss_and_grads(x_eng, softplus=self.score_function is softplus_score_function,
-                                                     regularization=float(self.regularization),
-                                                     all_timesteps=bool(self.score_over_all_timesteps), global_negatives=gneg,
-                                                     after_loss=sync.reduce_flag if sync is not None else None,
-                                                     gradient_penalty=float(self.gradient_penalty_factor))
-                        else:
-                            out = eng.loss_and_grads(x_eng, softplus=self.score_function is softplus_score_function,
-                                                     regularization=float(self.regularization),
-                                                     all_timesteps=bool(self.score_over_all_timesteps),
-                                                     grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
-                                                     global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None,
-                                                     **score_kw, **self._negatives_kw(), **groups_kw, **bank_kw)
-                        if sync is not None:
-                            sync.finish()
-                        # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
-                        optimizer.step(grad_scale=1.0 if gneg is not None else 1.0 / world)
-                        vals = out
+                        vals = self._fused_step(run, batch, next_batch, ahead, score_kw, groups_kw, bank_kw)
                     else:
                         vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm,
-                                                  (step_lr if schedule is not None else None, step_lr * weight_decay, decayed),
-                                                  ema=generic_ema, **groups_kw)
-                    stash(self.training_step, vals)
+                                                  (step_lr if schedule is not None else None, step_lr * weight_decay, run.decayed),
+                                                  ema=run.generic_ema, **groups_kw)
+                    readback.push(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
-                        nan_step = flush()
+                        nan_step = readback.flush()
                         if nan_step is not None:
-                            return nan_return(nan_step)
+                            return self._nan_return(nan_step, readback, rollback)
                     # the readback trails the launches by host_sync_lag steps: the host waits for step i - 1's loss while step i
                     # already runs (reading step i's loss right away left the GPU idle for 0.3 ms of every 5.1 ms step while the
                     # host prepared the next one); every step is still logged, in order, and a NaN loss still ends the run
-                    if len(pending) >= self.host_sync_interval + self.host_sync_lag:
-                        nan_step = flush(keep=self.host_sync_lag)
+                    if len(readback.pending) >= self.host_sync_interval + self.host_sync_lag:
+                        nan_step = readback.flush(keep=self.host_sync_lag)
                         if nan_step is not None:
-                            return nan_return(nan_step)
+                            return self._nan_return(nan_step, readback, rollback)
                     self.training_step += 1
                     if max_steps is not None and self.training_step >= max_steps:
-                        nan_step = flush()
+                        nan_step = readback.flush()
                         if nan_step is not None:
-                            return nan_return(nan_step)
+                            return self._nan_return(nan_step, readback, rollback)
                         return prof_ctx if profile else None
-            prof = prof_ctx if profile else None
-        nan_step = flush()
+        nan_step = readback.flush()
         if nan_step is not None:
-            return nan_return(nan_step)
+            return self._nan_return(nan_step, readback, rollback)
         return None
+
+    def _nan_return(self, step, readback, rollback):
+        """Leaves train() after a NaN loss at ``step``: BatchNorm's statistics and the step counts as the reference leaves them."""
+        rollback.restore(step)
+        self.training_step = step          # the reference leaves train() inside step `step`, before its update (:124-133)
+        self.reset_negative_bank()         # (its latest rows come from the NaN step and the ones launched behind it)
+        if readback.bad_grad_norm:
+            print("gradient norm not finite at step", step, "(max_grad_norm): no update was applied")
+        print("nan loss")
+        print("returned with nan loss at step", step)
+        return None
+
+    def _make_optimizer(self, lr, device, world, start_step, max_grad_norm, adamw, trust, ema, device_temp):
+        """The optimizer of one train() call and what its step routes share, as one namespace: optimizer, fused (the engine route),
+        graphed (use_graph's captured step), sync (GradAllReduce under data parallelism), generic_ema (the generic route's TorchEma),
+        decayed (the parameters the generic route decays itself), device / world / clip and the step routes' caches: graph_steps
+        ((B, L) -> GraphedStep), glob_neg (id(engine) -> GlobalNegatives), guarded (engines whose sticky NaN flag was cleared for this
+        run).  adamw, trust, ema: what _check_adamw, _check_trust and _check_ema return.  Loads and clears optimizer_state."""
+        (weight_decay, decay_filter, schedule), (trust_ratio, trust_clip), (ema_decay, ema_warmup) = adamw, trust, ema
+        fused = self._fused() or self._engine_difference() or self._engine_normalized()
+        run = types.SimpleNamespace(fused=fused, graphed=False, sync=None, generic_ema=None, decayed=[], device=device, world=world,
+                                    clip=max_grad_norm is not None, graph_steps={}, glob_neg={}, guarded=set())
+        self.model._flatten_parameters(device)
+        if fused:
+            from .engine import FusedAdam, GradAllReduce
+            run.graphed = bool(self.use_graph) and world == 1 and self.preprocessing is None
+            lamb = dict(trust_ratio=True, trust_clip=trust_clip) if trust_ratio else {}
+            if ema_decay is not None:          # (without a decay FusedAdam is called as before the keywords existed)
+                flat = self.model._flat_param
+                if self._ema is not None and (self._ema.shape != flat.shape or self._ema.device != flat.device):
+                    self.reset_ema()          # another model or device: the old average means nothing here
+                lamb.update(ema_decay=ema_decay, ema_warmup=ema_warmup, ema=self._ema)
+            if device_temp is not None:          # (without one FusedAdam is called as before the keyword existed)
+                lamb.update(temperature=device_temp)
+            optimizer = FusedAdam(self.model, lr=lr, device_step=run.graphed, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                                  decay_filter=decay_filter, schedule=schedule, step_offset=start_step, **lamb)
+            if ema_decay is not None:
+                self._ema, self._ema_owner = optimizer.ema, optimizer
+            self.last_optimizer = optimizer          # (inspection only: tests read its step count after a NaN return)
+            self.model.link_grads()
+            run.sync = GradAllReduce(self.model, optimizer=optimizer) if world > 1 else None
+        elif trust_ratio:          # LAMB's decay is inside its direction: no multiply in front of the step
+            from .engine import TorchLamb
+            optimizer = TorchLamb(self.model.named_parameters(), lr=lr, weight_decay=weight_decay, decay_filter=decay_filter,
+                                  trust_clip=trust_clip)
+        else:
+            optimizer = self.optimizer(self.model.parameters(), lr=lr)
+        run.optimizer = optimizer
+        if ema_decay is not None and not fused:
+            from .engine import TorchEma
+            flat = self.model._flat_param
+            if self._ema is None or self._ema.shape != flat.shape or self._ema.device != flat.device:
+                self._ema = flat.detach().float().clone()
+            run.generic_ema = self._ema_owner = TorchEma(self.model.named_parameters(), ema_decay, ema_warmup,
+                                                         shadow=self._shadow_views())
+        if weight_decay > 0.0 and not fused and not trust_ratio:          # the generic route multiplies them itself, in front of optimizer.step()
+            from .engine import default_decay_filter
+            run.decayed = [p for n_, p in self.model.named_parameters() if (decay_filter or default_decay_filter)(n_, p)]
+        if self.optimizer_state is not None:
+            state, self.optimizer_state = self.optimizer_state, None
+            optimizer.load_state_dict(state)
+            if run.generic_ema is not None:          # (FusedAdam.load_state_dict has taken its "ema" itself)
+                entries = state.get("state", {})
+                names = [n for n, _ in self.model.named_parameters()]
+                if entries and all(i in entries and "ema" in entries[i] for i in range(len(names))):
+                    run.generic_ema.load_state_dict({"ema": {n: entries[i]["ema"] for i, n in enumerate(names)}})
+                else:
+                    with torch.no_grad():
+                        self._ema.copy_(self.model._flat_param.detach())
+        return run
+
+    @staticmethod
+    def _clear_nan_flag_once(run, eng):
+        """The engine's sticky NaN flag is cleared the first time a run meets the engine."""
+        if id(eng) not in run.guarded:
+            eng.nan_flag().zero_()
+            run.guarded.add(id(eng))
+
+    def _graphed_step(self, run, batch, score_kw):
+        """use_graph: the whole step replayed from the hipGraph captured for the batch's shape (engine.GraphedStep)."""
+        eng = self.model.engine(batch.shape[0], batch.shape[1], run.device)
+        key = (batch.shape[0], batch.shape[1])
+        if key not in run.graph_steps:
+            from .engine import GraphedStep
+            run.graph_steps[key] = GraphedStep(eng, run.optimizer, self.score_function is softplus_score_function,
+                                               float(self.regularization), bool(self.score_over_all_timesteps), **score_kw)
+        self._clear_nan_flag_once(run, eng)
+        return run.graph_steps[key](batch)
+
+    def _fused_step(self, run, batch, next_batch, ahead, score_kw, groups_kw, bank_kw):
+        """The engine route: forward, loss, analytic backward and the fused optimizer's update as HIP kernels.  ahead: None or the
+        epoch's InputAhead, which hands over this batch's model input and is given ``next_batch`` beside this step."""
+        optimizer, sync = run.optimizer, run.sync
+        if self.preprocessing is not None:
+            if ahead is not None:
+                if not ahead.pending:              # first step of the epoch: nothing was submitted beside a previous one
+                    ahead.submit(batch)
+                _, x_eng = ahead.take()
+            else:
+                x_eng = self._model_input(batch)
+            eng = self.model.engine_for(x_eng)
+            if ahead is not None and next_batch is not None:
+                # the engine runs it behind its encoder's forward pass, where its main queue turns latency-bound
+                eng.side_job = lambda nb=next_batch: ahead.submit(nb)
+        else:
+            x_eng = batch.contiguous()
+            eng = self.model.engine(batch.shape[0], batch.shape[1], run.device)
+        gneg = None
+        if self.global_negatives and run.world > 1:
+            gneg = run.glob_neg.get(id(eng))
+            if gneg is None:
+                from .engine import GlobalNegatives
+                gneg = run.glob_neg[id(eng)] = GlobalNegatives(eng)
+        # the operand copies of the next step are rebuilt as soon as Adam has updated their parameters
+        # (engine.CPCEngine.prepare_ahead; under data parallelism Adam follows each reduced gradient piece)
+        optimizer.after_update = eng.prepare_ahead
+        # NaN guard on the device (reference :124-133 returns before backward() / optimizer.step()): the loss
+        # kernel raises the engine's sticky flag, every Adam launch of this and of later steps is a no-op while it
+        # is up, and the host leaves train() when the step's indicator arrives (host_sync_lag steps later)
+        self._clear_nan_flag_once(run, eng)
+        optimizer.skip_flag = eng.nan_flag()
+        if run.clip:
+            optimizer.nan_pair = eng.nan_pair()
+        # per-GPU negatives: mean of the shard gradients; global negatives: the shard gradients add up
+        grad_scale = 1.0 if gneg is not None else 1.0 / run.world
+        if sync is not None:
+            sync.grad_scale = grad_scale
+        if self.wasserstein_gradient_penalty:
+            # three passes through the network (scalogram_engine.ScalogramCPCEngine._gp_step); the parameter
+            # gradients are complete only at the end, so Adam runs once, after them
+            route_kw = {"gradient_penalty": float(self.gradient_penalty_factor)}
+        else:
+            route_kw = dict(grad_ready_hook=sync.hook if sync is not None else getattr(optimizer, "hook", None),
+                            **score_kw, **self._negatives_kw(), **groups_kw, **bank_kw)
+        out = eng.loss_and_grads(x_eng, softplus=self.score_function is softplus_score_function,
+                                 regularization=float(self.regularization), all_timesteps=bool(self.score_over_all_timesteps),
+                                 global_negatives=gneg, after_loss=sync.reduce_flag if sync is not None else None, **route_kw)
+        if sync is not None:
+            sync.finish()
+        optimizer.step(grad_scale=grad_scale)
+        return out
 
     def _negatives_kw(self):
         """{} for the in-batch loss; else the step's negatives = (num_negatives, negative_seed, draw = training_step) — the same
@@ -1309,14 +1307,13 @@ class ContrastiveEstimationTrainer:
         early returns above it — a NaN loss, a gradient norm that is not finite — leave the average where it is)."""
         predicted_z, targets, _, _ = self.model(self._model_input(batch))
         scores = self.score_function(predicted_z, targets)
+        selection = None
         if negative_groups is not None:
-            n_neg, seed, draw = self._negatives_kw().get("negatives", (0, 0, 0))
-            loss, out = _GroupedInfoNCE.apply(scores, float(self.regularization), negative_groups[0], group_mode(negative_groups[1]),
-                                              n_neg, seed, draw)
-        elif self.num_negatives is None:
-            loss, out = _InfoNCE.apply(scores, bool(self.score_over_all_timesteps), float(self.regularization))
-        else:
-            loss, out = _SampledInfoNCE.apply(scores, float(self.regularization), *self._negatives_kw()["negatives"])
+            selection = ("grouped", negative_groups[0], group_mode(negative_groups[1]),
+                         *self._negatives_kw().get("negatives", (0, 0, 0)))
+        elif self.num_negatives is not None:
+            selection = ("sampled", *self._negatives_kw()["negatives"])
+        loss, out = _InfoNCE.apply(scores, bool(self.score_over_all_timesteps), float(self.regularization), selection)
         nan = out[5:6].clone()
         if world > 1:          # every rank has its own loss: all ranks leave at the same step
             import torch.distributed as dist

@@ -957,7 +957,7 @@ class CPCEngine:
                       whole-batch selection: that step runs the very launches of a call without a bank
           scores      _scores: score GEMM(s) or cpc_diff_scores; "banked": one score GEMM over the ring's rows (_bank_scores)
           loss        _nce_loss: dense, sampled, grouped, banked or all-timesteps kernel ("linear" scores for every kind but "softplus", as
-                      contrastive_estimation_training._InfoNCE does); or scores and loss in one, _nce_all_fused, where
+                      contrastive_estimation_training._InfoNCE does, over the same selection); or scores and loss in one, _nce_all_fused, where
                       fused_scores_ok() holds
           fix-up      "difference": _diff_coefficients
           gradients   the linear score's two contractions, _score_grads / _score_grads_all ("banked": the second one reduces over the

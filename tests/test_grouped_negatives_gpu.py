@@ -553,7 +553,7 @@ def test_trainer_ids_resume_and_empty_sets(golden_dir):
 
 
 def test_generic_route_logs_the_fused_route_loss(golden_dir):
-    """Another optimizer sends the step through the autograd bridge and _GroupedInfoNCE: same first-step loss as the fused route."""
+    """Another optimizer sends the step through the autograd bridge and _InfoNCE's grouped selection: same first-step loss as the fused route."""
     g, meta, data, params = _small(golden_dir)
     B, seed = meta["B"], 123
     for score_function, N in ((softplus_score_function, 2), (linear_score_function, None), (difference_score_function, 1)):

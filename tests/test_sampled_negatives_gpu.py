@@ -417,7 +417,7 @@ def test_trainer_three_steps_and_resume(golden_dir):
 
 @pytest.mark.parametrize("score_function", [softplus_score_function, linear_score_function, difference_score_function])
 def test_generic_route_logs_the_fused_route_loss(golden_dir, score_function):
-    """Another optimizer sends the step through the autograd bridge and _SampledInfoNCE: same first-step loss as the fused route."""
+    """Another optimizer sends the step through the autograd bridge and _InfoNCE's sampled selection: same first-step loss as the fused route."""
     g, meta, data, params = _small(golden_dir)
     B, N, seed = meta["B"], 2, 123
     losses = []

@@ -2,7 +2,7 @@
 transformer.py:131-171, :223-272): the same constructor arguments, attribute names and ``state_dict`` keys, so checkpoints
 move in both directions.  The transformer containers hold the parameters (standard torch containers, default initialisers, the reference's construction
 order); inside ``AudioPredictiveCodingModel`` (or ``AttentionModel(z)``) the arithmetic and its gradients run in the HIP kernels
-behind ``engine.AttentionContext``; a stand-alone ``TransformerEncoderLayer`` / ``TransformerEncoder`` call runs the same kernels
+behind ``contexts.AttentionContext``; a stand-alone ``TransformerEncoderLayer`` / ``TransformerEncoder`` call runs the same kernels
 in float32 and is differentiable like the reference's modules (``_LayerFn`` / ``_NormFn``: autograd functions over the C ABI's
 forward and backward entry points).
 """
@@ -30,7 +30,7 @@ class PositionalEncoder(nn.Module):
     def forward(self, x):
         """x (steps, batch, code_size) on the GPU -> x * sqrt(code_size) + pe[:steps] (reference attention_model.py:28-35) through
         cpc_pe_scale_fwd.  Inference only when called stand-alone (inside AudioPredictiveCodingModel the same kernel runs as part
-        of engine.AttentionContext, where its gradient exists); unlike the reference the caller's tensor is not rescaled in place."""
+        of contexts.AttentionContext, where its gradient exists); unlike the reference the caller's tensor is not rescaled in place."""
         from . import _hip
         if not x.is_cuda:
             raise RuntimeError("PositionalEncoder runs on the GPU only (no CPU fallback)")
@@ -105,7 +105,7 @@ def _ln_backward(g1, g2, r, stats, weight, M, C, dp, seed, site):
 class _LayerFn(torch.autograd.Function):
     """One post-norm encoder layer (transformer.py:262-271) on rows X (B*S, C) float32 through the C ABI: in_proj GEMM, cpc_attn_fwd,
     out_proj GEMM, cpc_add_ln_fwd (residual + dropout + LayerNorm), linear1 + ReLU GEMM, cpc_dropout, linear2 GEMM, cpc_add_ln_fwd;
-    backward: the same kernels engine.AttentionContext.backward issues for a layer (cpc_ln_bwd, masked data-gradient GEMMs,
+    backward: the same kernels contexts.AttentionContext.backward issues for a layer (cpc_ln_bwd, masked data-gradient GEMMs,
     cpc_attn_bwd, reduction-form GEMMs for the weight gradients).  Dropout (train mode, p > 0): the counter-based masks of
     include/cpc_hip.h with sites site0 ... site0 + 3, regenerated in the backward pass."""
 
@@ -281,5 +281,5 @@ class AttentionModel(nn.Module):
     def forward(self, x):
         """(batch, channels, steps) on the GPU -> (batch, output_size).  Inference only when called stand-alone; unlike the
         reference this does not rescale the caller's tensor in place (attention_model.py:30)."""
-        from .engine import standalone_context_forward
+        from .contexts import standalone_context_forward
         return standalone_context_forward(self, x, self.output_size)

@@ -120,7 +120,7 @@ class AudioGRUModel(nn.Module):
     def forward(self, input):
         """(batch, input_size, steps) on the GPU -> last hidden state (batch, hidden_size), differentiable with respect to the
         input and the parameters (stand-alone calls go through the autograd bridge _ContextForward)."""
-        from .engine import standalone_context_forward
+        from .contexts import standalone_context_forward
         return standalone_context_forward(self, input, self.hidden_size)
 
 
@@ -178,7 +178,7 @@ class ConvolutionalArModel(nn.Module):
     def forward(self, x):
         """(batch, channels, steps) on the GPU -> the last position (batch, ar_size).  Inference only when called
         stand-alone (BatchNorm follows self.training); gradients flow through AudioPredictiveCodingModel."""
-        from .engine import standalone_context_forward
+        from .contexts import standalone_context_forward
         return standalone_context_forward(self, x, self.ar_size)
 
 

@@ -51,7 +51,7 @@ class InputAhead:
     handing a block to the other stream while it is still being read."""
 
     def __init__(self, fn, device):
-        from .engine import side_stream
+        from .contexts import side_stream
         self.fn, self.device = fn, torch.device(device)
         self.aux = side_stream(self.device)
         self.pending = []
@@ -668,7 +668,7 @@ class ContrastiveEstimationTrainer:
             from .audio_model import AudioGRUModel
             ar = getattr(model, "autoregressive_model", None)
             if isinstance(ar, AudioGRUModel) and getattr(ar, "num_layers", 1) > 1:
-                from .engine import GRUContext
+                from .contexts import GRUContext
                 raise NotImplementedError(GRUContext.GP_STACK_REASON)
             model.gradient_penalty_engine = True      # engines built from now on also give the gradient w.r.t. the scalogram
         if self.verbose:

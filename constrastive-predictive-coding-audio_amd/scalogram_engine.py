@@ -16,8 +16,8 @@ from typing import List, Optional
 import torch
 
 from . import _hip, switches
-from .engine import (CPCEngine, Float32Context, _ceil_div, check_negative_bank_supported, check_negatives_supported, check_temperature,
-                     make_context, score_kind, side_stream)
+from .contexts import Context, ContextHost, Float32Context, _ceil_div, make_context
+from .engine import CPCEngine, check_negative_bank_supported, check_negatives_supported, check_temperature, score_kind
 
 
 class Grid:
@@ -1286,23 +1286,15 @@ class ScalogramCPCEngine(CPCEngine):
         """``gradient_penalty``: also provide the gradient with respect to the input scalogram and the tangent pass the
         Wasserstein gradient penalty needs (loss_and_grads(..., gradient_penalty=factor))."""
         enc, ar = model.encoder, model.autoregressive_model
+        B, Cin, Hin, Win = (int(v) for v in in_shape)
+        # (the waveform encoder's constructor, CPCEngine.__init__, does not apply: the shared part of the two is ContextHost's)
+        ContextHost.__init__(self, model, device, dtype, B, model.enc_size, model.ar_size, model.prediction_steps, model.visible_steps)
         self.gp_capable = bool(gradient_penalty)
         self._twins = {}
-        self.model = model
-        self.device = torch.device(device)
-        self.dt = dtype
-        self.code = _hip.dtype_code(dtype)
-        B, Cin, Hin, Win = (int(v) for v in in_shape)
-        self.B, self.in_shape = B, (B, Cin, Hin, Win)
+        self.in_shape = (B, Cin, Hin, Win)
         self.L = Win
-        self.E = int(model.enc_size)
-        self.H = int(model.ar_size)
-        self.K = int(model.prediction_steps)
-        self.V = int(model.visible_steps)
         self.x_off = 0
         self.n = 0
-        self.colsum_blocks = 1024
-        model._flatten_parameters(self.device)
         # ---- encoder graph
         blocks = list(enc.blocks)
         top0 = blocks[0].cfg['top_padding_1'] or 0
@@ -1342,7 +1334,6 @@ class ScalogramCPCEngine(CPCEngine):
             self.act, self.dact = [self.top_grid.t], [self.d_top_grid.t]
         else:
             self.act, self.dact = [out.t], [self.blocks[-1].d_out.t]
-        self.aux = side_stream(self.device)      # side stream, see engine.CPCEngine
         self.ctx = make_context(self, ar) if (self.V + self.K) > 0 else None
         need = [b.slab for b in self.blocks] + [self.colsum_blocks * max(max(b.a_a.C, b.conv_b.cout) for b in self.blocks)]
         self._alloc_head(need)
@@ -1354,7 +1345,7 @@ class ScalogramCPCEngine(CPCEngine):
     supports_prepare_ahead = True
 
     def prepare_ahead(self, lo, hi, final):
-        if final and self.ctx is not None and getattr(self.ctx, "ahead_ok", False) and self.use_aux and switches.prepare_ahead():
+        if final and self.ctx is not None and self.ctx.ahead_ok and self.use_aux and switches.prepare_ahead():
             self._prepare_all_ahead()
 
     def _check_input(self, x):
@@ -1486,7 +1477,7 @@ class ScalogramCPCEngine(CPCEngine):
             # bf16 storage: tangent grids and penalty weight-gradient GEMMs in bf16 like the primal ones, the float32 first stage kept.
             # Grid-based context networks (ConvolutionalArModel / ScalogramResidualEncoder contexts: the reference's e22-e26 and its
             # script default e29) run in bf16 too; a GRU or attention context computes in float32 inside the bf16 engine
-            # (engine.Float32Context: their second-order sweeps are float32 kernels).
+            # (contexts.Float32Context: their second-order sweeps are float32 kernels).
             if not isinstance(self.ctx, (ConvArGridContext, ResNetArContext, Float32Context)):
                 raise NotImplementedError(f"gradient penalty with bf16 storage: no route for {type(self.ctx).__name__} "
                                           f"(compute_dtype='fp32' runs it)")
@@ -1774,7 +1765,7 @@ class _ArBlock:
                       _desc(self.rp, self.rp.desc), self.pool * self.stride, 1, code)
 
 
-class ConvArGridContext:
+class ConvArGridContext(Context):
     """ConvolutionalArModel with batch_norm and / or residual (e.g. ar_conv_architecture_2/3) as the context network."""
 
     ahead_ok = True       # prepare_weights is a pure function of the parameters (ScalogramCPCEngine.prepare_ahead)
@@ -1855,7 +1846,7 @@ class ConvArGridContext:
         self._z_rows(e.dact[-1]).copy_(self.d_x0.t.view(e.B, e.V, e.E))
 
 
-class ResNetArContext:
+class ResNetArContext(Context):
     """ScalogramResidualEncoder used as the autoregressive model (reference configs ar_resnet_architecture_1/2: blocks with
     (1,k) kernels, pooling_1 = 2 with ceil mode, batch norm, residual branches): z (B, E, V) is the grid [B][W = V][H = 1][E];
     the model takes the first remaining time step of the (B, C, T') result (audio_model.py:203-204)."""

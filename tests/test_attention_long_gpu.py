@@ -419,7 +419,7 @@ def _gp_model(golden_dir, dtype, p_drop):
 def test_attention_long_gradient_penalty_against_oracle(golden_dir, dtype, p_drop):
     """The Wasserstein gradient penalty through an AttentionModel context at visible_steps = 100 (cpc_attn128_tangent / _gp / _bwd):
     exact-f32 mode, with and without train-mode dropout (masks handed to the oracle), and a bf16 engine whose context runs in f32
-    (engine.Float32Context), against the oracle's double backward.  Bounds as test_scalogram_gpu.py's penalty tests: 1e-4 loss / 1e-3
+    (contexts.Float32Context), against the oracle's double backward.  Bounds as test_scalogram_gpu.py's penalty tests: 1e-4 loss / 1e-3
     gradients in f32; in bf16 the loss within 1e-2 and gradient cosines > 0.95 (weights) / 0.85 (vectors)."""
     from cpc_audio_amd.audio_dataset import FileBatchSampler
     import random

@@ -580,7 +580,7 @@ def test_scalogram_engine_with_a_stacked_gru(golden_dir):
 
 # ------------------------------------------------------------------------------------------ the single-layer step
 # What GRUContext(num_layers = 1) launched before stacks existed, in order: prepare_weights, forward, backward (the parameter gradients
-# on the side stream between the sweep and the dz GEMM), read off engine.GRUContext at that commit.
+# on the side stream between the sweep and the dz GEMM), read off GRUContext (then in engine.py) at that commit.
 PARENT_LAUNCHES = {
     "prepare_weights": ["cpc_cast2d", "cpc_cast2d", "cpc_prep_frag", "cpc_prep_frag"],
     "forward": ["gemm_nt", "cpc_gru_fwd"],
@@ -589,6 +589,27 @@ PARENT_LAUNCHES = {
                  "cpc_colsum", "cpc_reduce_slabs", "cpc_reduce_slabs", "cpc_reduce_slabs",
                  "gemm_nt"],
 }
+_LAYER_PARAMS = ["gemm_tn", "cpc_reduce_slabs", "gemm_tn", "cpc_reduce_slabs", "gemm_tn", "cpc_reduce_slabs",
+                 "cpc_colsum", "cpc_reduce_slabs", "cpc_reduce_slabs", "cpc_reduce_slabs"]
+# The same three phases of the two-layer context (_model(dtype, 2, 64), both storage types alike), recorded with _Spy at the commit
+# before GRUContext's layers became one loop: per layer the projection GEMM and the recurrence; backward the top sweep, that layer's
+# parameter gradients, the GEMM that hands dH down, the sweep below with its parameter gradients, the dz GEMM.
+PARENT_LAUNCHES_TWO_LAYERS = {
+    "prepare_weights": ["cpc_cast2d", "cpc_cast2d", "cpc_prep_frag", "cpc_prep_frag"] * 2,
+    "forward": ["gemm_nt", "cpc_gru_fwd", "gemm_nt", "cpc_gru_fwd"],
+    "backward": ["cpc_gru_bwd"] + _LAYER_PARAMS + ["gemm_nt", "cpc_gru_bwd_steps"] + _LAYER_PARAMS + ["gemm_nt"],
+}
+
+
+def _context_launches(eng):
+    got, ctx = {}, eng.ctx
+    for phase, fn in (("prepare_weights", ctx.prepare_weights), ("forward", ctx.forward), ("backward", lambda: ctx.backward(eng.dc))):
+        with _Spy() as spy:
+            fn()
+            torch.cuda.current_stream().wait_stream(eng.aux)
+            torch.cuda.synchronize()
+        got[phase] = spy.names
+    return got
 
 
 class _Spy:
@@ -630,24 +651,13 @@ def test_single_layer_step_is_the_parent_step(dtype):
     assert "cpc_gru_bwd_steps" not in spy.names and spy.names.count("cpc_gru_bwd") == 1 and spy.names.count("cpc_gru_fwd") == 1
     ctx = eng.ctx
     assert ctx.L == 1 and ctx.upper == []
-    got = {}
-    for phase, fn in (("prepare_weights", ctx.prepare_weights), ("forward", ctx.forward), ("backward", lambda: ctx.backward(eng.dc))):
-        with _Spy() as spy:
-            fn()
-            torch.cuda.current_stream().wait_stream(eng.aux)
-            torch.cuda.synchronize()
-        got[phase] = spy.names
-    assert got == PARENT_LAUNCHES
+    assert _context_launches(eng) == PARENT_LAUNCHES
     model2 = _model(dtype, 2, 64).to(DEV)
     eng2 = model2.engine(B_S, data.shape[1])
     eng2.loss_and_grads(data.to(DEV), softplus=True, regularization=1.0)
-    with _Spy() as spy:
-        eng2.ctx.prepare_weights()
-        eng2.ctx.forward()
-        eng2.ctx.backward(eng2.dc)
-        torch.cuda.current_stream().wait_stream(eng2.aux)
-        torch.cuda.synchronize()
-    n = spy.names
+    got2 = _context_launches(eng2)
+    assert got2 == PARENT_LAUNCHES_TWO_LAYERS
+    n = got2["prepare_weights"] + got2["forward"] + got2["backward"]
     assert n.count("cpc_gru_fwd") == 2 and n.count("cpc_gru_bwd") == 1 and n.count("cpc_gru_bwd_steps") == 1
     assert n.count("gemm_nt") == 2 + 2 and n.count("gemm_tn") == 6 and n.count("cpc_prep_frag") == 4
     assert n.index("cpc_gru_bwd") < n.index("cpc_gru_bwd_steps")

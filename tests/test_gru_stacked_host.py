@@ -224,7 +224,7 @@ def test_gradient_penalty_through_a_stack_is_refused_by_the_trainer():
     """The penalty's reverse sweep covers one recurrence: a trainer asked for it on a stacked GRU raises in its constructor, with the
     reason, before any GPU work; the same request on a single layer is accepted."""
     from cpc_audio_amd.contrastive_estimation_training import ContrastiveEstimationTrainer, linear_score_function
-    from cpc_audio_amd.engine import GRUContext
+    from cpc_audio_amd.contexts import GRUContext
 
     def trainer(L):
         enc = AudioEncoder(SMALL)

@@ -126,7 +126,7 @@ def test_wide_gru_fwd_bwd(dt, H, B, V):
 def test_wide_gru_gradient_penalty_kernels(B, V, E, H):
     """cpc_gru_gp_fwd / cpc_gru_gp_bwd at H = 384 and 512 (512 threads per workgroup): the gradient of the directional derivative
     D = <xt, d S / d x>, S = <wc, GRU(x)>, with respect to the GRU's parameters and its input, assembled from the kernels' outputs
-    as engine.GRUContext.gp_grads does, against autograd's double backward in float64 (test_hip_kernels.py's construction)."""
+    as contexts.GRUContext.gp_grads does, against autograd's double backward in float64 (test_hip_kernels.py's construction)."""
     g = torch.Generator().manual_seed(B * 1000 + H)
     f64 = lambda *sh, s=1.0: (torch.randn(*sh, generator=g) * s).float().double()
     Wih, Whh = f64(3 * H, E, s=E ** -0.5), f64(3 * H, H, s=H ** -0.5)
@@ -324,7 +324,7 @@ def test_wide_gru_train_and_validate_against_oracle():
 def test_wide_gru_gradient_penalty_against_oracle(golden_dir, dtype):
     """The Wasserstein gradient penalty through an AudioGRUModel(64, 512) context on the scalogram fixture's encoder (its parameters,
     a seeded GRU): exact-f32 mode (GRUContext.tangent / gp_grads on cpc_gru_gp_*) and a bf16 engine whose GRU runs in float32
-    (engine.Float32Context), against the oracle's double backward.  Bounds of test_attention_long_gpu.py's penalty test: 1e-4 loss /
+    (contexts.Float32Context), against the oracle's double backward.  Bounds of test_attention_long_gpu.py's penalty test: 1e-4 loss /
     1e-3 gradients in f32; in bf16 the loss within 1e-2 and gradient cosines > 0.95 (weights) / 0.85 (vectors)."""
     import copy
     import json

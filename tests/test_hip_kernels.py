@@ -1024,7 +1024,7 @@ def test_add_layernorm_fwd_bwd(dt, M, C, bcast):
 def test_gru_gradient_penalty_kernels(B, V, E, H):
     """cpc_gru_gp_fwd / cpc_gru_gp_bwd (f32) at hidden sizes up to the kernels' limit: the gradient of the directional derivative
     D = <xt, d S / d x>, S = <wc, GRU(x)>, with respect to the GRU's parameters and its input, assembled from the kernels' outputs
-    as engine.GRUContext.gp_grads does, against autograd's double backward in float64."""
+    as contexts.GRUContext.gp_grads does, against autograd's double backward in float64."""
     g = torch.Generator().manual_seed(B * 1000 + H)
     f64 = lambda *sh, s=1.0: (torch.randn(*sh, generator=g) * s).float().double()
     Wih, Whh = f64(3 * H, E, s=E ** -0.5), f64(3 * H, H, s=H ** -0.5)

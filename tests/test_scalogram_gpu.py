@@ -420,8 +420,8 @@ def test_gradient_penalty_matches_reference(golden_dir, fixture):
     HIP path, exact-f32 mode: losses, every parameter gradient and the parameters after three steps against runs of the
     reference itself (scalogram encoder with BatchNorm / residual blocks + BatchNorm ConvolutionalArModel, linear scores, both
     loss branches; ``scalogram_model``: the same encoder with the AudioGRUModel context, runs 3-5 of that fixture — the second
-    derivatives of the gates, engine.GRUContext.gp_grads; ``scalogram_model_gp_att``: an AttentionModel context, dropout 0 — the
-    second-order terms of LayerNorm, softmax and the two attention products, engine.AttentionContext._backward_gp)."""
+    derivatives of the gates, contexts.GRUContext.gp_grads; ``scalogram_model_gp_att``: an AttentionModel context, dropout 0 — the
+    second-order terms of LayerNorm, softmax and the two attention products, contexts.AttentionContext._backward_gp)."""
     g = _load(golden_dir, fixture + ".npz")
     meta = json.load(open(os.path.join(golden_dir, fixture + ".json")))
     B, K, H = meta["B"], meta["K"], meta["H"]
@@ -477,7 +477,7 @@ def test_gradient_penalty_bf16_matches_reference(golden_dir, fixture):
     vectors (BatchNorm scale / shift, biases: heavily cancelling sums at this fixture's size) within 0.85 (gradients that are zero
     up to rounding skipped).  INTEGRATION.md lists the deviation.
     ``scalogram_model`` (AudioGRUModel context, runs 3-5 of that fixture) and ``scalogram_model_gp_att`` (AttentionModel context): the
-    encoder in bf16 storage, the context network in float32 inside the bf16 engine (engine.Float32Context), same bounds."""
+    encoder in bf16 storage, the context network in float32 inside the bf16 engine (contexts.Float32Context), same bounds."""
     g = _load(golden_dir, fixture + ".npz")
     meta = json.load(open(os.path.join(golden_dir, fixture + ".json")))
     B, K, H = meta["B"], meta["K"], meta["H"]

@@ -1,5 +1,5 @@
 """CPU check (float64, torch autograd's double backward as the judge) of the algebra behind the Wasserstein gradient penalty
-through the attention context network (engine.AttentionContext.tangent / gp_*; csrc/attn.hip: ln_tangent, ln_gp, attn_tangent,
+through the attention context network (contexts.AttentionContext.tangent / gp_*; csrc/attn.hip: ln_tangent, ln_gp, attn_tangent,
 attn_gp kernels).  D(theta) = <v, d S / d z> is the directional derivative of the summed scores S along v; its gradient is the
 reverse sweep of the joint (primal, tangent) program: delta = adjoint of S (also the adjoint of the tangent variables),
 nu = what the primal variables gain through the tangent program's coefficients (sources at LayerNorm, softmax, Q.K, P.V).

@@ -35,6 +35,7 @@ static int gemm_nt_from_args(const cpc_gemm_nt_args* a, const void* mask_bits, f
     p.a_rpi2 = a->a_rpi2; p.a_item2 = a->a_item2; p.c_rpi2 = a->c_rpi2; p.c_item2 = a->c_item2; p.k_ranges = a->k_ranges;
     if (a->a_rpi2 && a->a_extent > 0) return CPC_EINVAL;
     if (a->k_taps < 0 || a->k_taps == 1 || (a->k_taps > 1 && (a->k_tap_stride <= 0 || a->k_tap_stride_a < 0 || a->a_extent > 0))) return CPC_EINVAL;
+    if (a->k_taps == 0 && a->k_tap_stride_a) return CPC_EINVAL;      // a piece stride without pieces: refused, not ignored
     p.k_taps = a->k_taps; p.k_tap_stride = a->k_taps > 1 ? a->k_tap_stride : 0; p.k_tap_stride_a = a->k_taps > 1 ? a->k_tap_stride_a : 0;
     p.k_taps_linear = a->k_taps > 1;
     if (a->dtype == CPC_DTYPE_F32) p.flags |= GEMM_OUT_F32;

@@ -1194,6 +1194,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_fast_kernel(GemmNT p) {
                 if (p.flags & GEMM_SKIP_PAD_ROWS) continue;
                 v = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
+            if (n + 4 > p.N) {           // a group straddling N: zeros into the pad columns, as the generic kernel (the B rows are clamped here)
+#pragma unroll
+                for (int e = 1; e < 4; ++e) v[e] = n + e < p.N ? v[e] : 0.f;
+            }
             store4(Cb + coff + n, v);
         }
     }
@@ -2175,7 +2179,8 @@ int launch_gemm_nt(const GemmNT& p_in, int dtype, int batch, hipStream_t stream)
     const bool of32 = p.flags & GEMM_OUT_F32;
     if (dtype == CPC_DTYPE_F32 && batch == 1 && (p.N == 8 || p.N == 16 || p.N == 32) && p.K <= 32 && p.K % 4 == 0 && !p.mask &&
         p.a_rpi == 0 && p.b_rpi == 0 && p.M >= 4096 && p.ldc % 4 == 0 && (p.c_rpi == 0 || p.c_item % 4 == 0) &&
-        !(p.flags & GEMM_FORCE_GENERIC) && p.m_off == 0 && ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.C % 16 == 0)) {
+        !(p.flags & GEMM_FORCE_GENERIC) && p.m_off == 0 && ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.C % 16 == 0) &&
+        !p.a_rpi2 && !p.c_rpi2 && !p.k_ranges && p.k_taps <= 1) {       // (the skinny kernel knows one row level and the whole K axis only)
         if (p.flags & GEMM_QUERY_EPI) return 100 + EPI_GENERIC;
         const long long rows_pp = 256 / (p.N / 8);
         const int blocks = (int)std::min<long long>(256 * 8, (p.M + rows_pp - 1) / rows_pp);
@@ -2335,7 +2340,7 @@ int launch_gemm_tn(const GemmTN& p, int dtype, int nsplit, int batch, hipStream_
     if (p.a_rpi2 && (!p.a_rpi || p.a_item2 % ch)) return CPC_EINVAL;
     const int eff_chunk = nsplit > 1 ? p.m_chunk : p.M;
     if (dtype == CPC_DTYPE_F32 && batch == 1 && p.I <= 32 && p.J <= 64 && p.I * (p.J / 4) <= 256 && p.c_rpi == 0 &&
-        p.lda >= (p.I + 3) / 4 * 4 && !(p.flags & GEMM_FORCE_GENERIC)) {
+        p.lda >= (p.I + 3) / 4 * 4 && !(p.flags & GEMM_FORCE_GENERIC) && !p.a_rpi2) {     // (a_rpi2: refused below, no f32 kernel has it)
         GemmTN q = p;
         q.m_chunk = eff_chunk;
         hipLaunchKernelGGL(gemm_tn_skinny_f32_kernel, dim3(nsplit), dim3(256), 0, stream, q);

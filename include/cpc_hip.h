@@ -86,7 +86,9 @@ int cpc_abi_version(void);
  * Replaces, in channels-last layout: F.conv1d forward of AudioEncoder layers 2..5 (audio_model.py:38-41, A rows
  * overlap: lda = stride*C_in, K = kernel*C_in), their data gradient (autograd of the same lines), nn.GRUCell's
  * input projection for all steps at once (audio_model.py:72), prediction_model (audio_model.py:208) and the
- * tensordot of the score functions restricted to equal steps (contrastive_estimation_training.py:13-14, :20-21). */
+ * tensordot of the score functions restricted to equal steps (contrastive_estimation_training.py:13-14, :20-21).
+ * PAD COLUMNS.  N % 4 != 0 is accepted without bias and mask only, and the rows of C must have room for round-up(N, 4) columns: every
+ * kernel then stores ZEROS into columns N .. round-up(N, 4) - 1 of each row it writes; nothing beyond them is touched. */
 typedef struct cpc_gemm_nt_args {
     const void* A;  const void* Bt;  void* C;
     const float* bias;            /* [N] f32 or NULL */
@@ -119,7 +121,7 @@ typedef struct cpc_gemm_nt_args {
      * 32 f32), dense in Bt, while piece j of a row of A starts j * k_tap_stride_a elements after the row address — the window of an nn.Conv2d
      * read straight from a channels-last grid (piece = kh rows x C channels of one kernel column; k_tap_stride_a = one grid column), no
      * im2col matrix.  The over-read contract applies to every piece.  k_taps = 0: off (overlapped rows with lda < K are detected by the launcher
-     * and visited tap-innermost on their own). */
+     * and visited tap-innermost on their own); k_tap_stride_a must be 0 then (CPC_EINVAL otherwise). */
     int k_taps; long long k_tap_stride; long long k_tap_stride_a;
 } cpc_gemm_nt_args;
 int cpc_gemm_nt(const cpc_gemm_nt_args* args, void* stream);

@@ -3,7 +3,9 @@ plain PyTorch CPU references (float64 where cheap).  The scalogram stem, depthwi
 test_scalogram_kernels_gpu.py; test_host_logic.py::test_every_abi_entry_point_is_named_by_a_test lists the entry points that only
 whole-model tests reach.  The 1-D convolution kernels (layer 1, cpc_conv_fwd / _dgrad / _wgrad, cpc_conv_w_prep, cpc_reduce_conv_w,
 cpc_reduce_slabs, cpc_colsum) are judged element by element against float64 at their edges in test_conv1d_kernels_gpu.py; the tests of
-them here keep the default geometry and the whole-tensor measure below.
+them here keep the default geometry and the whole-tensor measure below.  The GEMMs themselves (cpc_gemm_nt, cpc_gemm_tn, cpc_gemm_nt_bits:
+every kernel body, every field of the argument blocks) are judged element by element against float64 in test_gemm_kernels_gpu.py; the
+tests of them here keep the large shapes and the bitwise agreement between the tile variants.
 
 Tolerances: f32 mode 2e-5 relative to the operand scale (exact-f32 MFMA, different summation order);
 bf16 mode 1e-2 (inputs rounded to 8 significant bits, f32 accumulation).

@@ -222,6 +222,7 @@ _SIGNATURES = {
     "cpc_wave_power_chunks": ([_I], _I),
     "cpc_wave_power": ([_P, _P, _I, _I, _L, _I, _P], _I),
     "cpc_wave_augment": ([_P, _P, _P, _P, _I, _I, _L, _L, C.POINTER(CpcWaveAugment), _P], _I),
+    "cpc_mel_pointwise": ([_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -923,4 +923,18 @@ int cpc_wave_augment(const float* x, float* y, const float* partial, float* para
     return launch_wave_augment(x, y, partial, params_out, B, L, ldx, ldy, cfg, (hipStream_t)stream);
 }
 
+int cpc_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
+                      float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,
+                      float delta_scaling, void* stream) {
+    if (!spec || !band_lo || !band_n || !band_off || !band_w || !out) return CPC_EINVAL;
+    if ((delta != 0 && delta != 1) || (take_log != 0 && take_log != 1) || (delta && !take_log)) return CPC_EINVAL;
+    if (B < 1 || n_mels < 1 || n_mels > 1024 || n_freq < 2 || n_freq > 4097 || Tn < 1 + delta) return CPC_EINVAL;
+    if (lds < 2LL * n_freq || (lds & 1)) return CPC_EINVAL;
+    if (((uintptr_t)spec & 7) || (delta && ((uintptr_t)out & 7))) return CPC_EINVAL;      // float2 loads of the rows, float2 stores with delta
+    if (take_log && (!std::isfinite(log_offset) || log_offset <= 0.f)) return CPC_EINVAL;
+    if (!std::isfinite(scaling) || !std::isfinite(delta_scaling)) return CPC_EINVAL;
+    return launch_mel_pointwise(spec, lds, band_lo, band_n, band_off, band_w, out, B, Tn, n_freq, n_mels, delta, take_log, log_offset, scaling,
+                                delta_scaling, (hipStream_t)stream);
+}
+
 }  // extern "C"

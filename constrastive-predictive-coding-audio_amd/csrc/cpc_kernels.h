@@ -231,6 +231,10 @@ int wave_power_chunks(int n);
 int launch_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, hipStream_t stream);
 int launch_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
                         const cpc_wave_augment_cfg* cfg, hipStream_t stream);
+// Log-mel front end (mel.hip): power -> mel bands -> log -> optional delta channel; arguments checked by the entry point.
+int launch_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
+                         float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,
+                         float delta_scaling, hipStream_t stream);
 int launch_lr_factors(int kind, long long warmup_steps, long long total_steps, float min_ratio, long long step0, int count, float* out,
                       hipStream_t stream);
 int conv_w_prep_plan(void* jobs_host, int njobs, int* total_blocks, int* lds_bytes);

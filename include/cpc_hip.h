@@ -69,6 +69,8 @@ extern "C" {
  *    cpc_wave_augment.
  *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_gru_bwd_steps, the backward sweep of a GRU layer that
  *    receives a gradient at every hidden state (a lower layer of AudioGRUModel(num_layers > 1)).
+ *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_mel_pointwise, the log-mel front end behind the
+ *    framed DFT GEMM.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -1025,6 +1027,27 @@ int cpc_wave_power_chunks(int n);
 int cpc_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, void* stream);
 int cpc_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
                      const CpcWaveAugment* cfg, void* stream);
+
+
+/* Log-mel front end (not in the reference; DESIGN.md, "Log-mel front end"): what follows the framed, windowed DFT, which is one
+ * cpc_gemm_nt over overlapped waveform rows.
+ *   spec  f32 [B][Tn][lds], (re, im) interleaved per bin k < n_freq; elements at or beyond 2 n_freq of a row are never read.
+ *   out   f32 [B][W][n_mels][Cc], (W, Cc) = (Tn - 1, 2) with delta, (Tn, 1) without (channels-last; the scalogram engine's input grid).
+ *   p[t][k] = fl(fl(re^2) + fl(im^2)); band m: M[t][m] = the f32 fma chain acc = fmaf(band_w[band_off[m] + j], p[t][band_lo[m] + j], acc)
+ *   from acc = 0 over j = 0 .. band_n[m] - 1 ascending, the range clamped to bins [0, n_freq) (a wrong table reads no other part of
+ *   spec; band_w must hold band_off[m] + band_n[m] floats).  No atomics; the same bits from run to run, whatever the grid.
+ *   take_log = 0: out = M (delta must be 0).  take_log = 1: l = logf(M + log_offset);
+ *     delta = 0: out[b][t][m] = scaling * l[t][m];
+ *     delta = 1: out[b][w][m] = (scaling * l[w + 1][m], delta_scaling * (l[w + 1][m] - l[w][m])).
+ *   A spectrum row is read once, plus one row per run of 31 / 15 / 7 output frames with delta (n_freq <= 1025 / <= 2049 / above).
+ *   A weight table of at most 2 n_freq floats (every bank of triangles) is kept in LDS; a longer one is read from global memory.
+ *   CPC_EINVAL before any launch: a NULL pointer; B, Tn or n_mels < 1; Tn < 2 with delta; n_freq outside [2, 4097]; n_mels > 1024;
+ *   lds < 2 n_freq or odd; delta or take_log outside {0, 1}; take_log = 0 with delta = 1; log_offset not finite or <= 0 with take_log;
+ *   scaling or delta_scaling not finite; spec not 8-byte aligned, or out not 8-byte aligned with delta.  stream is a hipStream_t.
+ *   Does not throw, allocate or synchronise. */
+int cpc_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
+                      float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,
+                      float delta_scaling, void* stream);
 
 #ifdef __cplusplus
 }

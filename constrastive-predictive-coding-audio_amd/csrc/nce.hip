@@ -996,6 +996,7 @@ int launch_nce_fused_grad(const void* Sb, const float* lse, void* dS, void* dST,
 int launch_nce_fused_finalize(const float* colp, int ncolp, const float* valid, int nvalid, const float* gradp, int ngrad, float* sums, int mode,
                               float n_rows, float n_items, int K, float reg, int softplus, float* out, hipStream_t stream) {
     if (mode < 0 || mode > 2 || (mode != 2 && (!colp || !valid || !gradp)) || (mode != 0 && !sums) || (mode != 1 && !out)) return CPC_EINVAL;
+    if (mode != 2 && (ncolp < 0 || nvalid < 0 || ngrad < 0)) return CPC_EINVAL;       // (a negative count would read as an empty array: a caller's mistake, not a strip without rows)
     hipLaunchKernelGGL(nce_fused_finalize_kernel, dim3(1), dim3(256), 0, stream, colp, ncolp, valid, nvalid, gradp, ngrad, sums, mode, n_rows, n_items,
                        K, reg, softplus, out);
     CPC_CHECK_LAUNCH();

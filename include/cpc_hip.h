@@ -731,7 +731,26 @@ int cpc_nce_loss_all(const float* S, const float* ST, void* dS, void* dST, float
  *                      global score matrix all-reduces them (SUM, SUM, SUM, MAX) — and mode 2: out from sums.  n_rows_total /
  *                      n_items_total: rows (predictions) and items of the WHOLE score matrix.
  * Rectangular problems (M != N, diag_off != 0) are the strips of engine.GlobalNegatives: a rank computes all predictions x its own
- * targets and its own predictions x all targets instead of the whole global matrix. */
+ * targets and its own predictions x all targets instead of the whole global matrix.
+ * Preconditions (CPC_EINVAL otherwise, before any launch: a refused call writes nothing):
+ *   cpc_score_lse      P, T, pm, ps not NULL; M, N > 0 and multiples of 256; E >= 128 and a multiple of 64; ldp, ldt >= E and multiples of 8;
+ *                      P and T 16-byte aligned; with S: lds >= N, a multiple of 4, S 16-byte aligned (lds is ignored when S is NULL).
+ *                      Reads E elements of every row of P and T, nothing of the ldp - E / ldt - E padding; writes columns [0, N) of S.
+ *                      valid[r] is written only where 0 <= r + diag_off < N: every other element of valid keeps what it held (any
+ *                      diag_off is accepted; with diag_off >= N or <= -M nothing of valid is touched).  S = NULL changes no other output.
+ *   cpc_nce_lse_merge  pm, ps, lse, colp not NULL; nparts, ncols > 0 (ncols need not be a multiple of 256: the last block of colp covers
+ *                      the columns that exist).  nrows_total is used by softplus scores only and need not be 256 nparts.
+ *   cpc_nce_fused_grad S, lse, dS not NULL and, with dST, 16-byte aligned; items > 0; K even, 2 <= K <= 24; ncols > 0 and a multiple
+ *                      of 4; ld >= ncols and a multiple of 8 (the bf16 rows of dS are stored in 8-byte groups from 16-byte loads of S: the
+ *                      same ld serves both); with dST: ldT >= items K and a multiple of 8.  Columns [ncols, ld) of S are not read, those
+ *                      of dS and columns [items K, ldT) of dST not written.  dST = NULL and gradp = NULL leave dS as it is with them.
+ *   cpc_nce_fused_finalize   mode in {0, 1, 2}; colp, valid, gradp not NULL and ncolp, nvalid, ngrad >= 0 unless mode == 2; sums not NULL
+ *                      unless mode == 0; out not NULL unless mode == 1.  Writes out[0..5] and, only when out[5] is raised, out[6] = 1
+ *                      (sticky: the caller clears it); out[7] and sums[4..] are never touched; mode 1 writes sums[0..3] only.
+ * Non-finite scores: a NaN score reaches ps of its tile and column (the maxima are taken with fmaxf, which drops it, so pm stays
+ * finite), from there lse, colp, out[0] and the flags out[5] / out[6].  An infinite score does NOT give lse = +inf as in the dense
+ * kernels: the epilogue forms exp(s - max) = exp(inf - inf), so a +inf score (and a column that is -inf throughout the 128 rows of a half tile) gives ps = NaN
+ * and lse = NaN, i.e. the step is flagged like a NaN; a -inf score beside finite ones contributes exp(-inf) = 0. */
 int cpc_score_lse(const void* P, const void* T, float* S, float* pm, float* ps, float* valid, int M, int N, int E, long long ldp,
                   long long ldt, long long lds, int diag_off, void* stream);
 int cpc_nce_lse_merge(const float* pm, const float* ps, int nparts, int ncols, int softplus, float nrows_total, float* lse, float* colp,

@@ -606,6 +606,10 @@ def nt_cases():
     a = NT(BF16, PERSIST_M, 256, 128, bias=True, flags=RELU, a_rpi=160, a_item=160 * 128, c_rpi=160, c_item=160 * 256, c_valid=150)
     a["rows"] = persist_rows(a)
     cases.append(("bf16-256-persistent", a))
+    # its twin with K = 192: nk = 3 stages, so every second tile of a workgroup starts on the other LDS slot (the odd-stage tile change)
+    a = NT(BF16, PERSIST_M, 256, 192, bias=True, flags=RELU, a_rpi=160, a_item=160 * 192, c_rpi=160, c_item=160 * 256, c_valid=150)
+    a["rows"] = persist_rows(a)
+    cases.append(("bf16-256-persistent-K192", a))
     return cases
 
 

@@ -334,7 +334,8 @@ class SimpleCase:
 def test_nce_fused_grad_partial_item_blocks_and_runtime_k(softplus, items, K):
     """cpc_nce_fused_grad on a strip (diag_off != 0, ncols % 8 == 4, ld > ncols) with partial last item blocks, for the compile-time K
     kernels and the run-time K one: dS and dS^T against float64 autograd of the oracle loss, the regulariser partials, the pad columns
-    of dS and dS^T untouched, and dST = NULL / gradp = NULL give the same dS bit for bit."""
+    of dS and dS^T untouched, and dST = NULL / gradp = NULL give the same dS bit for bit.
+    (Per-element bounds and the exact-data twins of this kernel: test_fused_score_kernels_gpu.py.)"""
     reg = 0.5
     c = _fused_grad_case(items, K, softplus, reg, items * 31 + K)
     ldT = (items * K // 8 + 1) * 8

@@ -54,7 +54,7 @@ mask, c_item % 8 != 0); K order storage, tap-innermost (lda < K, K % lda == 0, l
                           -two-level-kranges-exact, -gathered-taps; staged: 256-staged, -staged-mask-crpi, -batch3, -two-level-kranges,
                           -grid-conv-combo, -bias-unaligned; form-mask: 256-form-mask(-skip); form-bits (cpc_gemm_nt_bits): 256-form-bits;
                           narrow: 256-narrow-outf32, -narrow-N260, -N258, -C-unaligned, -mask-unaligned;
-                          persistent: 256-persistent (M = 256 513 + 32, N = 256, K = 128: 520 blocks)
+                          persistent: 256-persistent (M = 256 513 + 32, N = 256, K = 128: 520 blocks), -persistent-K192 (3 K stages)
     tn skinny (f32)       I = 16, J = 24 at M in {1, 31, 32, 33, 101}, split3 / split5, rows-items8, rows-nodma, A-unaligned;
                           skinny-bound (I J / 4 = 256), skinny-ragged-I (I = 31)
     tn generic            f32: I = 40, J = 72 at the same M, split3 / split5 (J = 136), rows-items-odd, B-unaligned-rows, batch3, crpi,
@@ -215,20 +215,20 @@ def test_gemm_nt_persistent():
     """The persistent kernel (more than 512 tiles of 256 x 256; M = 256 513 + 32 ends in a ragged tile): a seeded subset of the rows and
     every pad row against float64, and all rows bitwise against the LDS-staged epilogue (CPC_GEMM_NO_PERS) and the non-persistent
     register epilogue of the 128 x 128 tile."""
-    cid = "bf16-256-persistent"
-    a = dict(NT_CASES)[cid]
-    assert G.nt_path(BF16, a) == "nt 256 persistent" and G.nt_path(BF16, dict(a, flags=a["flags"] | G.NO_PERS)) == "nt 256 staged"
-    for exact in (False, True):
-        d = G.nt_data(a, exact)
-        ref = G.nt_run_reference(a, d)
-        out = run_nt(a, d)
-        verdict(out, ref, BF16, exact, "nt 256 persistent", cid, checked=ref.written)
-        m = torch.arange(a["M"])
-        pad = out.view(a["M"], a["N"])[((m % a["c_rpi"]) >= a["c_valid"]).to(DEV)]
-        assert bool((pad == 0).all()) and not bool(torch.isnan(out.float()).any())
-        assert same_bits(run_nt(a, d, flags=a["flags"] | G.NO_PERS), out)
-        if not exact:
-            assert same_bits(run_nt(a, d, flags=a["flags"] | G.SMALL_TILE), out)
+    for cid in ("bf16-256-persistent", "bf16-256-persistent-K192"):        # K = 128: two stages per tile; K = 192: three, the odd-stage tile change
+        a = dict(NT_CASES)[cid]
+        assert G.nt_path(BF16, a) == "nt 256 persistent" and G.nt_path(BF16, dict(a, flags=a["flags"] | G.NO_PERS)) == "nt 256 staged"
+        for exact in (False, True):
+            d = G.nt_data(a, exact)
+            ref = G.nt_run_reference(a, d)
+            out = run_nt(a, d)
+            verdict(out, ref, BF16, exact, "nt 256 persistent", cid, checked=ref.written)
+            m = torch.arange(a["M"])
+            pad = out.view(a["M"], a["N"])[((m % a["c_rpi"]) >= a["c_valid"]).to(DEV)]
+            assert bool((pad == 0).all()) and not bool(torch.isnan(out.float()).any())
+            assert same_bits(run_nt(a, d, flags=a["flags"] | G.NO_PERS), out)
+            if not exact:
+                assert same_bits(run_nt(a, d, flags=a["flags"] | G.SMALL_TILE), out)
 
 
 # ======================================================================================================================= TN

@@ -255,6 +255,7 @@ def test_case_lists_reach_every_kernel_path_and_the_mirror_agrees_with_the_libra
                 assert has(grp, cond), (grp, what)
     assert has("nt fast128", lambda a: a["flags"] & G.OUT_F32) and has("nt generic", lambda a: a["flags"] & G.OUT_F32) and has("nt 256", lambda a: a["flags"] & G.OUT_F32)
     assert {(a["N"], a["K"]) for a in by["nt skinny"]} >= {(8, 4), (16, 20), (32, 32)}
+    assert {a["K"] // 64 for _, a in NT_CASES if G.nt_choice(a)["path"] == "nt 256 persistent"} >= {2, 3}          # even and odd stage counts
     assert any(a["M"] == G.PERSIST_M for _, a in NT_CASES) and {a["nsplit"] for _, a in TN_CASES} >= {1, 3, 5}
 
 

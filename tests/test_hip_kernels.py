@@ -796,7 +796,8 @@ def _fused_scores(Pm, Tm, softplus, reg, K, diag_off, n_rows_total, n_items_tota
 def test_fused_all_timesteps_score_path(softplus, items, K, E, reg):
     """score_over_all_timesteps=True through the fused kernels (bf16): the score GEMM whose epilogue leaves the column log-sum-exp
     pairs, the merge, the gradient pass on the bf16 scores and the loss scalars — against the oracle's loss on the same (bf16-rounded)
-    operands and autograd's gradient (contrastive_estimation_training.py:12-22, :108-114, :141)."""
+    operands and autograd's gradient (contrastive_estimation_training.py:12-22, :108-114, :141).
+    (Each entry point against float64 per element, with exact-data twins and multi-tile walks: test_fused_score_kernels_gpu.py.)"""
     R = items * K
     g = torch.Generator().manual_seed(items + K + E)
     bf = torch.bfloat16

@@ -348,7 +348,21 @@ int cpc_ln_bwd(const void* g1, const void* g2, const void* r, const float* stats
  *   per-block partial sums of the penalty part of the weight gradient, sum dy * rstd * P rt.  C <= 1024.
  * cpc_attn_tangent: out_t = (pt m) v + (P m) vt, pt = P (u - <P,u>), u = scale (qt k^T + q kt^T), m the dropout factors; qkvt in
  *   the layout of qkv.
- * cpc_attn_gp: dqkv += the second-order terms of the attention core, dout = delta at its output (formulas in csrc/attn.hip). */
+ * cpc_attn_gp: dqkv += the second-order terms of the attention core, dout = delta at its output (formulas in csrc/attn.hip).
+ * Preconditions, each refused with CPC_EINVAL before any launch unless stated as the caller's duty
+ * (tests/test_penalty_reference_host.py pins the refusals without a GPU, tests/test_penalty_kernels_gpu.py that nothing is written):
+ *   cpc_ln_tangent  at, r, stats, w, yt not NULL (bt and rt_out may be NULL: no second summand / rt not stored); M >= 1; C >= 1 with
+ *                   no upper limit and no multiple required (one wave per row, lanes stride over the columns); 0 <= drop_p < 1.
+ *   cpc_ln_gp       g1, rt, r, stats, w, dr, slabs not NULL (g2 and dr_b may be NULL); M >= 1; 1 <= C <= 1024 (cpc_ln_tangent
+ *                   accepts wider rows, this entry point does not); nblocks >= 1; 0 <= drop_p < 1.  dr and dr_b ACCUMULATE (+=);
+ *                   every one of the nblocks slabs is written, blocks beyond ceil(M/4) write zeros.  bcast > 0 must divide M and
+ *                   g1 must hold M / bcast rows (caller's duty).
+ *   cpc_attn_tangent / cpc_attn_gp (and the cpc_attn128 pair)
+ *                   every pointer not NULL; B >= 1; 1 <= S <= 64 (128 for cpc_attn128_*); heads >= 1 dividing C; head size C / heads a
+ *                   multiple of 4 and <= 64; 0 <= drop_p < 1.  qkv, qkvt, dout, dqkv and out_t are read and written as 16-byte
+ *                   vectors: each must be 16-byte aligned (caller's duty; with the head size a multiple of 4 every row and head
+ *                   offset then is).  P is the f32 weights cpc_attn_fwd / cpc_attn128_fwd saved, [B * heads][S][S].  dqkv ACCUMULATES.
+ *                   The dropout factor of weight (bh, i, j) has element index bh S S + i S + j in both families. */
 int cpc_ln_tangent(const float* at, const float* bt, const float* r, const float* stats, const float* w, float* rt_out, float* yt,
                    int M, int C, float drop_p, unsigned long long seed, unsigned site, void* stream);
 int cpc_ln_gp(const float* g1, const float* g2, const float* rt, const float* r, const float* stats, const float* w, float* dr,
@@ -609,7 +623,11 @@ int cpc_gru_bwd_steps(const float* dc, const void* dHs, long long ld_h, const vo
  * state; W = weight_hh [3H][H].  dA f32 [B][V][8][H]: columns [0,4H) = [d r_pre | d z_pre | d n_pre | d n_pre * r] of the summed
  * scores (to be contracted with the TANGENT inputs / hidden states for the weight gradients), columns [4H,8H) the same four of
  * the second-order adjoint (contracted with the primal inputs / hidden states; [4H,7H) W_ih is what the encoder's top-layer
- * gradient gains). */
+ * gradient gains).
+ * Preconditions, each refused with CPC_EINVAL before any launch: every pointer not NULL (bhh included: a GRU without biases is not
+ * supported here); B >= 1, V >= 1, 1 <= H <= 512.  H need NOT be a multiple of 16 or of the wave size (one thread per hidden unit,
+ * the last wave partly idle).  Both kernels write every element of tape, ct_out and dA (no accumulation); the tangent slots of
+ * h_{t-1} and W_hn h at t = 0 are exact zeros.  (Pinned by tests/test_penalty_reference_host.py and tests/test_penalty_kernels_gpu.py.) */
 int cpc_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const float* bhh, float* tape, float* ct_out, int B,
                    int V, int H, void* stream);
 int cpc_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA, int B, int V, int H, void* stream);

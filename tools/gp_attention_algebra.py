@@ -4,7 +4,12 @@ attn_gp kernels).  D(theta) = <v, d S / d z> is the directional derivative of th
 reverse sweep of the joint (primal, tangent) program: delta = adjoint of S (also the adjoint of the tangent variables),
 nu = what the primal variables gain through the tangent program's coefficients (sources at LayerNorm, softmax, Q.K, P.V).
 
-Run:  python tools/gp_attention_algebra.py        (prints relative errors, all ~1e-15)"""
+Run:  python tools/gp_attention_algebra.py        (prints relative errors, all ~1e-15)
+
+Role: a derivation aid for the WHOLE sweep (two layers, four dropout sites, end layer); it never runs in the test suite.  The judge
+of the per-kernel formulas (ln_tangent / ln_gp / attn_tangent / attn_gp below) is tests/test_penalty_reference_host.py, which holds
+their restatement in tests/penalty_reference.py (ln_gp_closed, attn_gp_closed) against jvp + grad on the definitions at every shape
+the kernel tests use."""
 import math
 import torch
 

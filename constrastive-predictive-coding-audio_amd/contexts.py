@@ -1,8 +1,8 @@
 """The context networks of the CPC train step, and what they may see of the engine that hosts them.
 
 A context network (``Context``: GRUContext for AudioGRUModel, ConvArContext / scalogram_engine.ConvArGridContext for
-ConvolutionalArModel, AttentionContext for AttentionModel, scalogram_engine.ResNetArContext, Float32Context around the first or the
-third) turns the frames z = rows [T-K-V, T-K) of the encoder's top buffer into c and, backward, dc into dz in the same rows of the top
+ConvolutionalArModel, AttentionContext for AttentionModel, scalogram_engine.ResNetArContext for a ScalogramResidualEncoder — the two
+of scalogram_engine share its GridContext base —, Float32Context around the first or the third) turns the frames z = rows [T-K-V, T-K) of the encoder's top buffer into c and, backward, dc into dz in the same rows of the top
 buffer's gradient plus its own parameter gradients.  It is built by make_context() for a ``ContextHost``: engine.CPCEngine and
 scalogram_engine.ScalogramCPCEngine for a train step, ContextOnlyEngine for a stand-alone ``AudioGRUModel(...)(z)`` call, Float32Host
 for a context that computes in float32 inside a bf16 engine.  A context reads its host and never writes it.

@@ -6,6 +6,14 @@ kernels (scalogram_model.py:390-395 with e.g. kernel_size_2 = (64,1)) become ove
 every other kernel shape runs as im2col + GEMM + col2im; BatchNorm2d uses batch statistics in train mode, running
 statistics in eval mode.  The encoder's output (one frequency row left) IS the [B][frames][E] buffer the context networks
 read, so everything downstream is shared with engine.CPCEngine.
+
+In the file's order: ``Grid`` owns the form a kernel takes it in (``g.arg`` = address and descriptor, ``g.d`` / ``g.padded_d`` the cast
+descriptors); module-level functions issue the grid launches that blocks of both kinds repeat (pooling, cropped residual add, ReLU mask,
+slab sums); ``_Conv`` / ``_SepConv``, ``_BatchNorm`` / ``_CastRelu`` (one statistics pass, ``_BatchStats``, shared with ``_Stem``) and
+``_Stem`` / ``_StemResidual`` are the layers, ``_Block`` one ScalogramEncoderBlock of them; ``ScalogramCPCEngine`` with the
+gradient-penalty step; then ``_ArBlock`` and the two context networks that run on grids, ``ConvArGridContext`` and ``ResNetArContext``,
+on their common ``GridContext``.  Buffers a route needs only sometimes are declared empty where their owner is built and allocated by
+the first step that takes the route.
 """
 from __future__ import annotations
 
@@ -37,6 +45,8 @@ class Grid:
         self.desc = (C.c_int * 6)(self.B, self.W, self.H, self.Ha, self.top, self.C)
         # the same memory seen as a grid whose top padding rows are ordinary (zero) data rows
         self.padded_desc = (C.c_int * 6)(self.B, self.W, self.top + self.H, self.Ha, 0, self.C)
+        # the form a kernel takes a descriptor in (const int[6] behind a void pointer), cast once
+        self.d, self.padded_d = C.cast(self.desc, C.c_void_p), C.cast(self.padded_desc, C.c_void_p)
 
     def allocate(self):
         guard = self.guard_rows * self.C
@@ -52,12 +62,14 @@ class Grid:
         return Grid(self.B, self.W, self.H, self.C, device, dtype, top=self.top, tail=self.Ha - self.top - self.H, guard_rows=guard_rows)
 
     @property
+    def arg(self):
+        """(address, descriptor): the two arguments a grid kernel takes for this grid, ``*g.arg`` in a launch.  A kernel that takes one
+        descriptor for two grids of one geometry gets ``g.ptr()`` and the ``.d`` of the grid whose geometry is meant."""
+        return self.ptr(), self.d
+
+    @property
     def count(self):
         return self.B * self.W * self.H
-
-
-def _desc(t, desc):
-    return C.cast(desc, C.c_void_p)
 
 
 def _accumulate(dst: Grid, src: Grid):
@@ -75,6 +87,56 @@ def _twin(eng, grid: Grid) -> Grid:
     if tw is None:
         tw = eng._twins[id(grid)] = grid.like(grid.t.device, guard_rows=grid.guard_rows)
     return tw
+
+
+# ---- the grid launches that blocks of both kinds (_Block, _ArBlock) issue: they pair every address with its descriptor and take the
+# element counts and the dtype code from the grids
+def _maxpool(src: Grid, dst: Grid, p, x_f32=0):
+    """dst = p x p max pooling (ceil mode) of src; ``x_f32``: src is the float32 input of the first block."""
+    _hip.call("cpc_maxpool2d_fwd", *src.arg, *dst.arg, p, x_f32, dst.code)
+
+
+def _maxpool_select(eng, src: Grid, dst: Grid, p, x_f32=0):
+    """Tangent of _maxpool(src, dst): the tangent of src taken where the primal src has its window maximum."""
+    _hip.call("cpc_maxpool2d_select", src.ptr(), *_twin(eng, src).arg, *_twin(eng, dst).arg, p, x_f32, dst.code)
+
+
+def _maxpool_bwd(src: Grid, d_src: Grid, d_dst: Grid, p, accumulate):
+    """Backward of _maxpool(src, dst): the gradient d_dst goes to the window maxima of d_src (added to it, or written beside zeros)."""
+    _hip.call("cpc_maxpool2d_bwd", src.ptr(), *d_src.arg, *d_dst.arg, p, accumulate, d_dst.code)
+
+
+def _residual_add(main: Grid, res: Grid, out: Grid, oh, ow=0, relu=0, r_f32=0):
+    """out = [relu](main + res cropped by (oh, ow)); ``r_f32``: res is a float32 grid in a bf16 engine."""
+    _hip.call("cpc_residual_add", *main.arg, *res.arg, *out.arg, oh, ow, relu, r_f32, out.code)
+
+
+def _residual_add_bwd(d_out: Grid, out: Grid, d_main: Grid, d_res: Grid, oh, ow=0, relu=0, r_f32=0):
+    """Backward of _residual_add: d_out (masked by out > 0 with ``relu``) -> d_main and the cropped interior of d_res."""
+    _hip.call("cpc_residual_add_bwd", d_out.ptr(), *out.arg, *d_main.arg, *d_res.arg, oh, ow, relu, r_f32, out.code)
+
+
+def _relu_mask(g: Grid, act: Grid):
+    """g *= (act > 0) over every allocated row of two grids of one geometry."""
+    _hip.call("cpc_relu_mask", g.ptr(), act.ptr(), g.rows * g.C, g.code)
+
+
+def _sum_slabs(eng, dst, n, nb, stride=None, offset=0):
+    """dst[n] = sum of the nb partial rows (``stride`` floats apart, n by default) a reduction kernel left in eng.slabs from ``offset`` on."""
+    _hip.call("cpc_reduce_slabs", _hip.ptr(eng.slabs, offset), _hip.ptr(dst), 1, n, nb, n if stride is None else stride, 1, 1, 0, 0)
+
+
+def _sum_bn_slabs(eng, C_, nb, dgamma, dbeta):
+    """The two column blocks of the partial rows [nb][2 C] of a BatchNorm backward reduction: sum q xhat -> dgamma, sum q -> dbeta."""
+    _sum_slabs(eng, dgamma, C_, nb, 2 * C_)
+    _sum_slabs(eng, dbeta, C_, nb, 2 * C_, C_)
+
+
+def _identity_stats(C_, dev):
+    """"Statistics" and parameters of an identity normalisation (mean 0, 1/sigma 1; gamma 1, beta 0): what the normalisation kernels take
+    where they only move a grid into another geometry or dtype (_CastRelu, _BatchNorm.tangent)."""
+    return SimpleNamespace(stats=torch.cat([torch.zeros(C_), torch.ones(C_)]).to(dev), ones=torch.ones(C_, device=dev),
+                           zeros=torch.zeros(C_, device=dev))
 
 
 def _col_group(cout, kw=1, stride=(1, 1), pad=0):
@@ -140,6 +202,9 @@ class _Conv:
             raise ValueError(f"{wname}: input {hin} x {gin.W} is smaller than the kernel")
         self.mode = 'col' if _col_ok(self.kw, self.sh, self.sw, self.pad, self.cin, in_f32) else 'win'
         self.gather = self.gather_w = self.parity = False
+        self.col = None           # the im2col matrix (mode 'win' without the gathered-window weight gradient, below)
+        # made on first use: the im2col matrix of the input's tangent, the scratch grid of an accumulating data gradient, the split-K slabs
+        self.col_t = self._din_tmp = self._wslab = None
         B = gin.B
         if self.cout % 8:
             raise NotImplementedError("scalogram encoder channel counts must be multiples of 8")
@@ -354,10 +419,10 @@ class _Conv:
         p, code = e.model._param, self.code
         bias = _hip.ptr(p.get(self.bname)) if self.bname else None
         flags = _hip.GEMM_RELU if self.relu else 0
-        col, mask, mask_w = getattr(self, "col", None), None, None
+        col, mask, mask_w = self.col, None, None
         if tangent:
             if self.mode == 'win' and not self.gather:
-                if getattr(self, "col_t", None) is None:
+                if self.col_t is None:
                     self.col_t = torch.empty_like(self.col)     # the primal im2col matrix is still needed by the weight gradient
                 col = self.col_t
             if self.relu:
@@ -385,14 +450,14 @@ class _Conv:
                          self.cout, code, bias=bias, mask=mask_w, a_rpi=self.Ho, a_item=self.sw * gin.Ha * self.cin, a_rpi2=self.Wo,
                          a_item2=gin.W * gin.Ha * self.cin, c_rpi=self.Ho, c_item=y0.Ha * self.cout, c_valid=self.Ho, flags=flags, **taps)
         else:
-            _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(col), _desc(gin, gin.padded_desc), self.kh, self.kw, self.sh, self.sw,
+            _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(col), gin.padded_d, self.kh, self.kw, self.sh, self.sw,
                       self.pad, self.pad, self.Ho, self.Wo, self.Kp, 1 if self.in_f32 else 0, code)
             _hip.gemm_nt(_hip.ptr(col), _hip.ptr(self.w_fwd), y0.ptr(y0.top * self.cout), self.M, self.cout, self.Kp, self.Kp, self.Kp,
                          self.cout, code, bias=bias, mask=mask_w, c_rpi=self.Ho, c_item=y0.Ha * self.cout, c_valid=self.Ho, flags=flags)
 
     def _scratch(self):
         e = self.eng
-        if getattr(self, "_wslab", None) is None:
+        if self._wslab is None:
             self._wslab = torch.empty(max(self.slab, 1), device=e.device, dtype=torch.float32)
             self._bscratch = torch.empty(e.colsum_blocks * self.cout, device=e.device, dtype=torch.float32)
             self._ev = (torch.cuda.Event(), torch.cuda.Event())
@@ -469,7 +534,7 @@ class _Conv:
 
             def gemm():
                 if self.gather:      # (float32: the forward pass wrote no im2col matrix; build it here, from the grid this gradient is taken against)
-                    _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(self.col), _desc(gin, gin.padded_desc), self.kh, self.kw, self.sh, self.sw,
+                    _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(self.col), gin.padded_d, self.kh, self.kw, self.sh, self.sw,
                               self.pad, self.pad, self.Ho, self.Wo, self.Kp, 0, code)
                 _hip.gemm_tn(_hip.ptr(self.col if self.gather else col), dy0.ptr(dy0.top * self.cout), _hip.ptr(wslab), self.M, self.Kp, self.cout, self.Kp,
                              self.cout, self.cout, code, b_rpi=self.Ho, b_item=dy0.Ha * self.cout, nsplit=self.nsplit,
@@ -482,7 +547,7 @@ class _Conv:
         """Penalty part of the weight gradient: (tangent of the input) x (gradient of the summed scores w.r.t. the output, which
         the first backward pass of the step left in dy0); nothing for the bias, which the tangent does not see."""
         e = self.eng
-        self._wgrad(_twin(e, self.gin), getattr(self, "col_t", None), self.dy0, gp_grad[self.wname], None)
+        self._wgrad(_twin(e, self.gin), self.col_t, self.dy0, gp_grad[self.wname], None)
 
     def _dgrad_bands(self, dy0: Grid, dst: Grid, Kd, mask_input):
         G, gin = self.G, self.gin
@@ -502,39 +567,24 @@ class _Conv:
         if gb is not None and self.bn_after is not None and self.bn_after.trained and not switches.bn_bias_colsum():
             gb.zero_()
             gb = None
-        self._wgrad(gin, getattr(self, "col", None), dy0, g[self.wname], gb)
+        self._wgrad(gin, self.col, dy0, g[self.wname], gb)
         if din is None or not self.need_dgrad:
             return
-        if self.mode == 'col' and self.G > 1:
-            G = self.G
+        if self.mode == 'col':
             dst = din
-            if accumulate:
-                if getattr(self, "_din_tmp", None) is None:
+            if accumulate:          # the overlapped-row GEMM overwrites: go through a scratch grid of the same layout
+                if self._din_tmp is None:
                     self._din_tmp = din.like(e.device, e.dt)
                 dst = self._din_tmp
-            Kd = self.Rd * self.cout
+            # a GEMM row is one (super-)row of G input rows; its window of output-gradient rows is the kernel's height, or the Rd rows of
+            # the grouped operand (G = 1: the plain overlapped-row form, the same call)
+            G, r0, nr = self.G, self.r0, self.nr
+            Kd = (self.Rd if G > 1 else self.kh) * self.cout
             if self.bands is not None:
                 self._dgrad_bands(dy0, dst, Kd, mask_input)
             else:
-                r0, nr = self.r0, self.nr
                 _hip.gemm_nt(dy0.ptr((r0 * G - (self.kh - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0 * G * self.cin), self.ncol * nr,
                              G * self.cin, Kd, G * self.cout, Kd, G * self.cin, code, mask=gin.ptr(r0 * G * self.cin) if mask_input else None,
-                             a_rpi=nr, a_item=dy0.Ha * self.cout, c_rpi=nr, c_item=dst.Ha * self.cin, c_valid=nr)
-            if accumulate:
-                _accumulate(din, dst)
-        elif self.mode == 'col':
-            D = self.kh
-            dst = din
-            if accumulate:          # the overlapped-row GEMM overwrites: go through a scratch grid of the same layout
-                if getattr(self, "_din_tmp", None) is None:
-                    self._din_tmp = din.like(e.device, e.dt)
-                dst = self._din_tmp
-            if self.bands is not None:
-                self._dgrad_bands(dy0, dst, D * self.cout, mask_input)
-            else:
-                r0, nr = self.r0, self.nr
-                _hip.gemm_nt(dy0.ptr((r0 - (D - 1)) * self.cout), _hip.ptr(self.w_dgrad), dst.ptr(r0 * self.cin), self.ncol * nr, self.cin,
-                             D * self.cout, self.cout, D * self.cout, self.cin, code, mask=gin.ptr(r0 * self.cin) if mask_input else None,
                              a_rpi=nr, a_item=dy0.Ha * self.cout, c_rpi=nr, c_item=dst.Ha * self.cin, c_valid=nr)
             if accumulate:
                 _accumulate(din, dst)
@@ -547,10 +597,10 @@ class _Conv:
             # scalogram_resnet_architecture_7; 128-wide tiles or the LDS-staged epilogue change nothing)
             _hip.gemm_nt(dy0.ptr(dy0.top * self.cout), _hip.ptr(self.w_t), _hip.ptr(self.dcol), self.M, self.Kp, self.cout, self.cout,
                          self.cout, self.Kp, code, a_rpi=self.Ho, a_item=dy0.Ha * self.cout)
-            _hip.call("cpc_col2im2d", _hip.ptr(self.dcol), din.ptr(), _desc(din, din.padded_desc), self.kh, self.kw, self.sh, self.sw,
+            _hip.call("cpc_col2im2d", _hip.ptr(self.dcol), din.ptr(), din.padded_d, self.kh, self.kw, self.sh, self.sw,
                       self.pad, self.pad, self.Ho, self.Wo, self.Kp, 1 if accumulate else 0, code)
             if mask_input:
-                _hip.call("cpc_relu_mask", din.ptr(), gin.ptr(), din.rows * din.C, code)
+                _relu_mask(din, gin)
 
 
 class _SepConv:
@@ -608,7 +658,7 @@ class _SepConv:
     def forward(self):
         e, gin, mid = self.eng, self.gin, self.mid
         w = e.model._param[self.wname]
-        _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(self.col), _desc(gin, gin.padded_desc), self.kh_dw, self.kw, self.sh, self.sw,
+        _hip.call("cpc_im2col2d", gin.ptr(), _hip.ptr(self.col), gin.padded_d, self.kh_dw, self.kw, self.sh, self.sw,
                   self.pad, self.pad, self.Ho, self.Wo, self.Kp, 1 if self.in_f32 else 0, self.code)
         _hip.call("cpc_dw_fwd", _hip.ptr(self.col), _hip.ptr(w), mid.ptr(mid.top * self.C), C.c_longlong(self.M), self.C, self.taps,
                   self.Kp, self.Ho, C.c_longlong(mid.Ha * self.C), self.code)
@@ -625,10 +675,10 @@ class _SepConv:
         if din is not None and self.need_dgrad:
             _hip.call("cpc_dw_bwd_col", d_mid.ptr(off), _hip.ptr(w), _hip.ptr(self.dcol), C.c_longlong(self.M), self.C, self.taps, self.Kp,
                       self.Ho, C.c_longlong(d_mid.Ha * self.C), self.code)
-            _hip.call("cpc_col2im2d", _hip.ptr(self.dcol), din.ptr(), _desc(din, din.padded_desc), self.kh_dw, self.kw, self.sh, self.sw,
+            _hip.call("cpc_col2im2d", _hip.ptr(self.dcol), din.ptr(), din.padded_d, self.kh_dw, self.kw, self.sh, self.sw,
                       self.pad, self.pad, self.Ho, self.Wo, self.Kp, 1 if accumulate else 0, self.code)
             if mask_input:
-                _hip.call("cpc_relu_mask", din.ptr(), gin.ptr(), din.rows * din.C, self.code)
+                _relu_mask(din, gin)
 
 
 def _make_conv(eng, base, mod, gin, bias, **kw):
@@ -638,7 +688,31 @@ def _make_conv(eng, base, mod, gin, bias, **kw):
     return _Conv(eng, base + ".weight", base + ".bias" if bias else None, mod, gin, **kw)
 
 
-class _BatchNorm:
+class _BatchStats:
+    """The statistics pass of a BatchNorm module (an owner with ``eng``, ``mod``, ``C``, ``nb`` and ``stats``): ``stats`` = (mean,
+    1 / sigma) per channel, of the batch in train mode — the module's running statistics and batch count move as nn.BatchNorm2d moves
+    them — and from the running statistics in eval mode."""
+
+    def _statistics(self, launch, count):
+        """``launch()``: the owner's statistics kernel, which leaves its ``nb`` partial rows of (sum, sum of squares) over the ``count``
+        positions per channel in eng.slabs."""
+        e, mod = self.eng, self.mod
+        self.trained = bool(mod.training or not mod.track_running_stats)
+        if self.trained:
+            launch()
+            rm = mod.running_mean if mod.track_running_stats else None
+            rv = mod.running_var if mod.track_running_stats else None
+            momentum = 0.1 if mod.momentum is None else float(mod.momentum)
+            _hip.call("cpc_bn_finalize", _hip.ptr(e.slabs), self.nb, self.C, count, float(mod.eps), momentum, _hip.ptr(self.stats),
+                      _hip.ptr(rm), _hip.ptr(rv))
+            if mod.track_running_stats and mod.num_batches_tracked is not None:
+                e.count_batch(mod.num_batches_tracked)
+        else:
+            self.stats[0].copy_(mod.running_mean)
+            self.stats[1].copy_(torch.rsqrt(mod.running_var + mod.eps))
+
+
+class _BatchNorm(_BatchStats):
     """nn.BatchNorm2d + ReLU between a convolution output grid y0 and the activation grid a."""
 
     def __init__(self, eng, prefix, mod, y0: Grid, a: Grid):
@@ -660,15 +734,17 @@ class _BatchNorm:
         self.abits = None
         if eng.dt == torch.bfloat16 and not self.x_f32 and self.C % 8 == 0 and not eng.gp_capable:
             self.abits = torch.zeros(a.rows * a.C // 8, device=eng.device, dtype=torch.uint8)
+        # gradient-penalty steps only, made by their first one: sum q xhat of the first backward pass (backward), the tangent y. with
+        # the rest of the tangent pass's buffers (tangent)
+        self.s2 = self.yt = None
 
     def apply_residual(self, res: Grid, out: Grid, oh, ow, relu_out, r_f32, obits=None):
         """The apply pass of forward(apply=False), fused with the block's cropped residual add and the ReLU between blocks
         (cpc_bn_apply_residual): the activation grid ``a`` is not written, only its sign bits (and, ``obits``, those of the block output)."""
         e = self.eng
         p = e.model._param
-        _hip.call("cpc_bn_apply_residual", self.y0.ptr(), _desc(self.y0, self.y0.desc), res.ptr(), _desc(res, res.desc), out.ptr(), _desc(out, out.desc),
-                  _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(p[self.prefix + ".bias"]), oh, ow, 1, relu_out, r_f32,
-                  _hip.ptr(self.abits), _desc(self.a, self.a.desc), _hip.ptr(obits), e.code)
+        _hip.call("cpc_bn_apply_residual", *self.y0.arg, *res.arg, *out.arg, _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]),
+                  _hip.ptr(p[self.prefix + ".bias"]), oh, ow, 1, relu_out, r_f32, _hip.ptr(self.abits), self.a.d, _hip.ptr(obits), e.code)
 
     def backward_res(self, d_out: Grid, obits, d_res: Optional[Grid], oh, ow):
         """backward() with the block's residual add folded in (cpc_bn_bwd_reduce_res / _apply_res): the gradient of the block output d_out,
@@ -676,38 +752,25 @@ class _BatchNorm:
         e = self.eng
         p, g, code = e.model._param, e.model._grad, e.code
         gw, gb = g[self.prefix + ".weight"], g[self.prefix + ".bias"]
-        _hip.call("cpc_bn_bwd_reduce_res", d_out.ptr(), _desc(d_out, d_out.desc), _hip.ptr(obits), _hip.ptr(self.abits), _desc(self.a, self.a.desc),
-                  self.y0.ptr(), _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(e.slabs), self.nb_bwd, code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(gw), 1, self.C, self.nb_bwd, 2 * self.C, 1, 1, 0, 0)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs, self.C), _hip.ptr(gb), 1, self.C, self.nb_bwd, 2 * self.C, 1, 1, 0, 0)
-        _hip.call("cpc_bn_bwd_apply_res", d_out.ptr(), _desc(d_out, d_out.desc), _hip.ptr(obits), _hip.ptr(self.abits), _desc(self.a, self.a.desc),
-                  self.y0.ptr(), self.dy0.ptr(), _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]),
-                  _hip.ptr(gw), _hip.ptr(gb), float(self.y0.count), 1 if self.trained else 0, d_res.ptr() if d_res is not None else None,
-                  _desc(d_res, d_res.desc) if d_res is not None else None, oh, ow, code)
+        _hip.call("cpc_bn_bwd_reduce_res", *d_out.arg, _hip.ptr(obits), _hip.ptr(self.abits), self.a.d,
+                  *self.y0.arg, _hip.ptr(self.stats), _hip.ptr(e.slabs), self.nb_bwd, code)
+        _sum_bn_slabs(e, self.C, self.nb_bwd, gw, gb)
+        # (y0 and its gradient dy0 share one descriptor; so do the activation's sign bits and, in backward(), the activation's gradient da)
+        _hip.call("cpc_bn_bwd_apply_res", *d_out.arg, _hip.ptr(obits), _hip.ptr(self.abits), self.a.d, self.y0.ptr(), *self.dy0.arg,
+                  _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb), float(self.y0.count),
+                  1 if self.trained else 0, *(d_res.arg if d_res is not None else (None, None)), oh, ow, code)
 
     def forward(self, apply=True):
-        e, mod = self.eng, self.mod
+        e, y0 = self.eng, self.y0
         p, code = e.model._param, e.code
-        self.trained = bool(mod.training or not mod.track_running_stats)
-        if self.trained:
-            _hip.call("cpc_bn_stats", self.y0.ptr(), _hip.ptr(e.slabs), self.y0.rows, self.C, self.nb, self.y0.code)
-            rm = mod.running_mean if mod.track_running_stats else None
-            rv = mod.running_var if mod.track_running_stats else None
-            momentum = 0.1 if mod.momentum is None else float(mod.momentum)
-            _hip.call("cpc_bn_finalize", _hip.ptr(e.slabs), self.nb, self.C, float(self.y0.count), float(mod.eps), momentum,
-                      _hip.ptr(self.stats), _hip.ptr(rm), _hip.ptr(rv))
-            if mod.track_running_stats and mod.num_batches_tracked is not None:
-                e.count_batch(mod.num_batches_tracked)
-        else:
-            self.stats[0].copy_(mod.running_mean)
-            self.stats[1].copy_(torch.rsqrt(mod.running_var + mod.eps))
+        self._statistics(lambda: _hip.call("cpc_bn_stats", y0.ptr(), _hip.ptr(e.slabs), y0.rows, self.C, self.nb, y0.code), float(y0.count))
         if not apply:
             return
         if self.abits is not None:
-            _hip.call("cpc_bn_apply_bits", self.y0.ptr(), _desc(self.y0, self.y0.desc), self.a.ptr(), _desc(self.a, self.a.desc),
+            _hip.call("cpc_bn_apply_bits", *y0.arg, *self.a.arg,
                       _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(p[self.prefix + ".bias"]), 1, _hip.ptr(self.abits), code)
         else:
-            _hip.call("cpc_bn_apply", self.y0.ptr(), _desc(self.y0, self.y0.desc), self.a.ptr(), _desc(self.a, self.a.desc), _hip.ptr(self.stats),
+            _hip.call("cpc_bn_apply", *y0.arg, *self.a.arg, _hip.ptr(self.stats),
                       _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(p[self.prefix + ".bias"]), 1, self.x_f32, code)
 
     def backward(self, da: Grid):
@@ -715,24 +778,22 @@ class _BatchNorm:
         p, g, code = e.model._param, e.model._grad, e.code
         gw, gb = g[self.prefix + ".weight"], g[self.prefix + ".bias"]
         if self.abits is not None:
-            _hip.call("cpc_bn_bwd_reduce_bits", da.ptr(), _hip.ptr(self.abits), _desc(self.a, self.a.desc), self.y0.ptr(),
-                      _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(e.slabs), self.nb_bwd, code)
+            _hip.call("cpc_bn_bwd_reduce_bits", da.ptr(), _hip.ptr(self.abits), self.a.d, *self.y0.arg,
+                      _hip.ptr(self.stats), _hip.ptr(e.slabs), self.nb_bwd, code)
         else:
-            _hip.call("cpc_bn_bwd_reduce", da.ptr(), self.a.ptr(), _desc(self.a, self.a.desc), self.y0.ptr(), _desc(self.y0, self.y0.desc),
+            _hip.call("cpc_bn_bwd_reduce", da.ptr(), *self.a.arg, *self.y0.arg,
                       _hip.ptr(self.stats), _hip.ptr(e.slabs), 1, self.nb_bwd, self.x_f32, code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(gw), 1, self.C, self.nb_bwd, 2 * self.C, 1, 1, 0, 0)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs, self.C), _hip.ptr(gb), 1, self.C, self.nb_bwd, 2 * self.C, 1, 1, 0, 0)
+        _sum_bn_slabs(e, self.C, self.nb_bwd, gw, gb)
         if self.abits is not None:
-            _hip.call("cpc_bn_bwd_apply_bits", da.ptr(), _hip.ptr(self.abits), _desc(self.a, self.a.desc), self.y0.ptr(), self.dy0.ptr(),
-                      _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb),
-                      float(self.y0.count), 1 if self.trained else 0, code)
+            _hip.call("cpc_bn_bwd_apply_bits", da.ptr(), _hip.ptr(self.abits), self.a.d, self.y0.ptr(), *self.dy0.arg, _hip.ptr(self.stats),
+                      _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb), float(self.y0.count), 1 if self.trained else 0, code)
         else:
-            _hip.call("cpc_bn_bwd_apply", da.ptr(), self.a.ptr(), _desc(self.a, self.a.desc), self.y0.ptr(), self.dy0.ptr(),
-                      _desc(self.y0, self.y0.desc), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb),
-                      float(self.y0.count), 1, 1 if self.trained else 0, self.x_f32, code)
+            _hip.call("cpc_bn_bwd_apply", da.ptr(), *self.a.arg, self.y0.ptr(), *self.dy0.arg, _hip.ptr(self.stats),
+                      _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(gw), _hip.ptr(gb), float(self.y0.count), 1, 1 if self.trained else 0,
+                      self.x_f32, code)
         gp = e._gp_phase
         if gp == 1:          # first backward pass of a gradient-penalty step (seeds: the summed scores): keep sum q xhat
-            if getattr(self, "s2", None) is None:
+            if self.s2 is None:
                 self.s2 = torch.empty_like(gw)
             self.s2.copy_(gw)
         elif gp == 3:        # last pass: the second-order terms of this BatchNorm join the adjoint of its input (gp_terms)
@@ -753,30 +814,27 @@ class _BatchNorm:
         y0, a = self.y0, self.a
         y0_t, a_t = _twin(e, y0), _twin(e, a)
         C_ = self.C
-        if getattr(self, "yt", None) is None:
+        if self.yt is None:
             dev = e.device
             self.yt = y0.like(dev, guard_rows=y0.guard_rows)
             self.xterm = y0.like(dev, guard_rows=y0.guard_rows)
             self.t_dgamma = torch.zeros(C_, device=dev, dtype=torch.float32)
             self.t_dbeta = torch.zeros(C_, device=dev, dtype=torch.float32)
             self.s1 = torch.zeros(C_, device=dev, dtype=torch.float32)
-            self.ident = torch.cat([torch.zeros(C_), torch.ones(C_)]).to(dev)             # "statistics" of an identity normalisation
-            self.ones, self.zeros = torch.ones(C_, device=dev), torch.zeros(C_, device=dev)
+            self.ident = _identity_stats(C_, dev)
             self.coef = torch.zeros(3 * C_, device=dev, dtype=torch.float32)
             self.inv_gamma_stats = torch.zeros(2 * C_, device=dev, dtype=torch.float32)
-        # sums over the batch of a. and xhat a. (no mask: the tangent enters the normalisation itself)
-        _hip.call("cpc_bn_bwd_reduce", y0_t.ptr(), None, _desc(y0, y0.desc), y0.ptr(), _desc(y0, y0.desc), _hip.ptr(self.stats),
-                  _hip.ptr(e.slabs), 0, self.nb_bwd, fx, fcode)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(self.t_dgamma), 1, C_, self.nb_bwd, 2 * C_, 1, 1, 0, 0)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs, C_), _hip.ptr(self.t_dbeta), 1, C_, self.nb_bwd, 2 * C_, 1, 1, 0, 0)
+        # sums over the batch of a. and xhat a. (no mask, hence no activation: the tangent enters the normalisation itself, in y0's geometry)
+        _hip.call("cpc_bn_bwd_reduce", y0_t.ptr(), None, y0_t.d, *y0.arg, _hip.ptr(self.stats), _hip.ptr(e.slabs), 0, self.nb_bwd, fx, fcode)
+        _sum_bn_slabs(e, C_, self.nb_bwd, self.t_dgamma, self.t_dbeta)
         # y. = gamma rstd (a. - <a.> - xhat <xhat a.>)
-        _hip.call("cpc_bn_bwd_apply", y0_t.ptr(), None, _desc(y0, y0.desc), y0.ptr(), self.yt.ptr(), _desc(y0, y0.desc), _hip.ptr(self.stats),
-                  _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(self.t_dgamma), _hip.ptr(self.t_dbeta), float(y0.count), 0, 1,
-                  fx, fcode)
+        _hip.call("cpc_bn_bwd_apply", y0_t.ptr(), None, y0_t.d, y0.ptr(), *self.yt.arg, _hip.ptr(self.stats),
+                  _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(self.t_dgamma), _hip.ptr(self.t_dbeta), float(y0.count), 0, 1, fx, fcode)
         # into the activation's geometry (identity "normalisation": mean 0, rstd 1, gamma 1, beta 0, no ReLU), then the primal mask
-        _hip.call("cpc_bn_apply", self.yt.ptr(), _desc(y0, y0.desc), a_t.ptr(), _desc(a, a.desc), _hip.ptr(self.ident), _hip.ptr(self.ones),
-                  _hip.ptr(self.zeros), 0, self.x_f32, code)
-        _hip.call("cpc_relu_mask", a_t.ptr(), a.ptr(), a.rows * a.C, code)
+        ident = self.ident
+        _hip.call("cpc_bn_apply", *self.yt.arg, *a_t.arg, _hip.ptr(ident.stats), _hip.ptr(ident.ones),
+                  _hip.ptr(ident.zeros), 0, self.x_f32, code)
+        _relu_mask(a_t, a)
 
     def gp_terms(self, da: Grid, gp_grad):
         """After the first backward pass (``da`` = its adjoint at this BatchNorm's output, before the ReLU mask; dy0 = at its input)
@@ -790,16 +848,17 @@ class _BatchNorm:
         # S1 = sum q a^.  with a^. = y. / gamma: the backward reduction run on x := y., "statistics" (0, 1/gamma)
         self.inv_gamma_stats[:C_].zero_()
         self.inv_gamma_stats[C_:].copy_(1.0 / gamma)
-        _hip.call("cpc_bn_bwd_reduce", da.ptr(), self.a.ptr(), _desc(self.a, self.a.desc), self.yt.ptr(), _desc(self.y0, self.y0.desc),
+        _hip.call("cpc_bn_bwd_reduce", da.ptr(), *self.a.arg, *self.yt.arg,
                   _hip.ptr(self.inv_gamma_stats), _hip.ptr(e.slabs), 1, self.nb_bwd, self.x_f32, code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(self.s1), 1, C_, self.nb_bwd, 2 * C_, 1, 1, 0, 0)
+        _sum_slabs(e, self.s1, C_, self.nb_bwd, 2 * C_)
         gp_grad[self.prefix + ".weight"].copy_(self.s1)
         self.coef[:C_].copy_(-(gamma * rstd) * self.s1 / n)                  # on xhat
         self.coef[C_:2 * C_].copy_(-rstd * self.s2 / n)                      # on y. (= gamma a^.)
         self.coef[2 * C_:].copy_(-rstd * self.t_dgamma / n)                  # on delta_in
         # (first-stage BatchNorm of a bf16 engine: x, y., the adjoint and the result are all float32 grids)
         fcode, fx = (_hip.F32, 0) if self.x_f32 else (code, self.x_f32)
-        _hip.call("cpc_bn_gp_cross", self.y0.ptr(), self.yt.ptr(), self.dy0.ptr(), self.xterm.ptr(), _desc(self.y0, self.y0.desc),
+        # (four grids of y0's geometry behind one descriptor)
+        _hip.call("cpc_bn_gp_cross", self.y0.ptr(), self.yt.ptr(), self.dy0.ptr(), self.xterm.ptr(), self.y0.d,
                   _hip.ptr(self.stats), _hip.ptr(self.coef), fx, fcode)
 
 
@@ -813,34 +872,34 @@ class _CastRelu:
         self.eng, self.y0, self.a = eng, y0, a
         self.C = y0.C
         self.x_f32 = 1 if (y0.dtype == torch.float32 and eng.dt != torch.float32) else 0
-        dev = eng.device
-        self.ident = torch.cat([torch.zeros(self.C), torch.ones(self.C)]).to(dev)      # mean 0, 1/sigma 1
-        self.ones, self.zeros = torch.ones(self.C, device=dev), torch.zeros(self.C, device=dev)
+        self.ident = _identity_stats(self.C, eng.device)
         self.slab = 0
         self.dy0: Optional[Grid] = None
         self.trained = False
 
     def forward(self):
-        _hip.call("cpc_bn_apply", self.y0.ptr(), _desc(self.y0, self.y0.desc), self.a.ptr(), _desc(self.a, self.a.desc), _hip.ptr(self.ident),
-                  _hip.ptr(self.ones), _hip.ptr(self.zeros), 1, self.x_f32, self.eng.code)
+        ident = self.ident
+        _hip.call("cpc_bn_apply", *self.y0.arg, *self.a.arg, _hip.ptr(ident.stats),
+                  _hip.ptr(ident.ones), _hip.ptr(ident.zeros), 1, self.x_f32, self.eng.code)
 
     def backward(self, da: Grid):
-        _hip.call("cpc_bn_bwd_apply", da.ptr(), self.a.ptr(), _desc(self.a, self.a.desc), self.y0.ptr(), self.dy0.ptr(),
-                  _desc(self.y0, self.y0.desc), _hip.ptr(self.ident), _hip.ptr(self.ones), _hip.ptr(self.zeros), _hip.ptr(self.zeros),
+        ident = self.ident
+        _hip.call("cpc_bn_bwd_apply", da.ptr(), *self.a.arg, self.y0.ptr(), *self.dy0.arg,
+                  _hip.ptr(ident.stats), _hip.ptr(ident.ones), _hip.ptr(ident.zeros), _hip.ptr(ident.zeros),
                   float(self.y0.count), 1, 0, self.x_f32, self.eng.code)
 
     def tangent(self):
-        e = self.eng
+        e, ident = self.eng, self.ident
         a_t = _twin(e, self.a)
-        _hip.call("cpc_bn_apply", _twin(e, self.y0).ptr(), _desc(self.y0, self.y0.desc), a_t.ptr(), _desc(self.a, self.a.desc),
-                  _hip.ptr(self.ident), _hip.ptr(self.ones), _hip.ptr(self.zeros), 0, self.x_f32, e.code)
-        _hip.call("cpc_relu_mask", a_t.ptr(), self.a.ptr(), self.a.rows * self.a.C, e.code)
+        _hip.call("cpc_bn_apply", *_twin(e, self.y0).arg, *a_t.arg,
+                  _hip.ptr(ident.stats), _hip.ptr(ident.ones), _hip.ptr(ident.zeros), 0, self.x_f32, e.code)
+        _relu_mask(a_t, self.a)
 
     def gp_terms(self, da: Grid, gp_grad):
         pass          # piecewise linear, no parameters: nothing of second order
 
 
-class _Stem:
+class _Stem(_BatchStats):
     """First convolution of the encoder + its train-mode BatchNorm + ReLU on the float32 scalogram (scalogram_model.py:392-406 of
     block 0) through csrc/stem.hip: the convolution's output is recomputed in every pass instead of being stored (DESIGN.md,
     scalogram family).  Stands where conv_a and bn_a stand in a _Block whose input gradient is not needed."""
@@ -863,27 +922,15 @@ class _Stem:
 
     def _args(self):
         p = self.eng.model._param
-        return (self.gin.ptr(), _desc(self.gin, self.gin.desc), _hip.ptr(p[self.wname]), _hip.ptr(p.get(self.bname)) if self.bname else None,
+        return (*self.gin.arg, _hip.ptr(p[self.wname]), _hip.ptr(p.get(self.bname)) if self.bname else None,
                 C.cast(self.conv, C.c_void_p))
 
     def forward(self):
-        e, mod = self.eng, self.mod
+        e = self.eng
         p = e.model._param
-        self.trained = bool(mod.training or not mod.track_running_stats)
-        if self.trained:
-            _hip.call("cpc_stem_stats", *self._args(), _hip.ptr(e.slabs), self.nb)
-            rm = mod.running_mean if mod.track_running_stats else None
-            rv = mod.running_var if mod.track_running_stats else None
-            momentum = 0.1 if mod.momentum is None else float(mod.momentum)
-            _hip.call("cpc_bn_finalize", _hip.ptr(e.slabs), self.nb, self.C, self.count, float(mod.eps), momentum, _hip.ptr(self.stats),
-                      _hip.ptr(rm), _hip.ptr(rv))
-            if mod.track_running_stats and mod.num_batches_tracked is not None:
-                e.count_batch(mod.num_batches_tracked)
-        else:
-            self.stats[0].copy_(mod.running_mean)
-            self.stats[1].copy_(torch.rsqrt(mod.running_var + mod.eps))
+        self._statistics(lambda: _hip.call("cpc_stem_stats", *self._args(), _hip.ptr(e.slabs), self.nb), self.count)
         _hip.call("cpc_stem_apply", *self._args(), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(p[self.prefix + ".bias"]),
-                  self.a.ptr(), _desc(self.a, self.a.desc), self.nb, e.code)
+                  *self.a.arg, self.nb, e.code)
 
     def backward(self, da: Grid):
         """da: gradient of the activation (before its ReLU mask) -> BatchNorm scale / shift gradients and the convolution's weight
@@ -892,15 +939,12 @@ class _Stem:
         p, g = e.model._param, e.model._grad
         gw, gb = g[self.prefix + ".weight"], g[self.prefix + ".bias"]
         a = self.a
-        _hip.call("cpc_stem_bwd_reduce", *self._args(), _hip.ptr(self.stats), da.ptr(), a.ptr(), _desc(a, a.desc), _hip.ptr(e.slabs), self.nb,
-                  e.code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(gw), 1, self.C, self.nb, 2 * self.C, 1, 1, 0, 0)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs, self.C), _hip.ptr(gb), 1, self.C, self.nb, 2 * self.C, 1, 1, 0, 0)
+        _hip.call("cpc_stem_bwd_reduce", *self._args(), _hip.ptr(self.stats), da.ptr(), *a.arg, _hip.ptr(e.slabs), self.nb, e.code)
+        _sum_bn_slabs(e, self.C, self.nb, gw, gb)
         dg, db = (gw, gb) if self.trained else (self.zeros, self.zeros)
         _hip.call("cpc_stem_bwd_wgrad", *self._args(), _hip.ptr(self.stats), _hip.ptr(p[self.prefix + ".weight"]), _hip.ptr(dg), _hip.ptr(db),
-                  self.count, da.ptr(), a.ptr(), _desc(a, a.desc), _hip.ptr(e.slabs), self.nb, e.code)
-        n = self.C * self.taps
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(g[self.wname]), 1, n, self.nb, n, 1, 1, 0, 0)
+                  self.count, da.ptr(), *a.arg, _hip.ptr(e.slabs), self.nb, e.code)
+        _sum_slabs(e, g[self.wname], self.C * self.taps, self.nb)
         if self.bname and self.bname in g:
             if self.trained:          # exactly zero in front of a train-mode BatchNorm (its input gradient has zero mean per channel)
                 g[self.bname].zero_()
@@ -925,26 +969,26 @@ class _StemResidual:
         e, m, xp, o = self.eng, self.main, self.xp, self.out
         p = e.model._param
         if bn is not None:
-            _hip.call("cpc_stem_residual_bn_add", bn.y0.ptr(), _desc(bn.y0, bn.y0.desc), xp.ptr(), _desc(xp, xp.desc), _hip.ptr(p[self.wname]),
-                      o.ptr(), _desc(o, o.desc), self.oh, self.ow, 1 if self.relu else 0, _hip.ptr(bn.stats), _hip.ptr(p[bn.prefix + ".weight"]),
-                      _hip.ptr(p[bn.prefix + ".bias"]), _hip.ptr(bn.abits), _desc(bn.a, bn.a.desc), _hip.ptr(obits), e.code)
+            _hip.call("cpc_stem_residual_bn_add", *bn.y0.arg, *xp.arg, _hip.ptr(p[self.wname]),
+                      *o.arg, self.oh, self.ow, 1 if self.relu else 0, _hip.ptr(bn.stats), _hip.ptr(p[bn.prefix + ".weight"]),
+                      _hip.ptr(p[bn.prefix + ".bias"]), _hip.ptr(bn.abits), bn.a.d, _hip.ptr(obits), e.code)
             return
-        _hip.call("cpc_stem_residual_add", m.ptr(), _desc(m, m.desc), xp.ptr(), _desc(xp, xp.desc), _hip.ptr(p[self.wname]),
-                  o.ptr(), _desc(o, o.desc), self.oh, self.ow, 1 if self.relu else 0, e.code)
+        _hip.call("cpc_stem_residual_add", *m.arg, *xp.arg, _hip.ptr(p[self.wname]),
+                  *o.arg, self.oh, self.ow, 1 if self.relu else 0, e.code)
 
     def backward_bits(self, d_out: Grid, obits):
         """The projection's weight gradient alone, the ReLU mask from the output's sign bits (cpc_stem_residual_wgrad_bits): the masked
         gradient of the main branch is not stored — the second BatchNorm's fused backward passes read d_out and the same bits."""
         e, xp, o, m = self.eng, self.xp, self.out, self.main
-        _hip.call("cpc_stem_residual_wgrad_bits", d_out.ptr(), _hip.ptr(obits), _desc(o, o.desc), _desc(m, m.desc), xp.ptr(), _desc(xp, xp.desc),
+        _hip.call("cpc_stem_residual_wgrad_bits", d_out.ptr(), _hip.ptr(obits), o.d, m.d, *xp.arg,
                   _hip.ptr(e.slabs), self.oh, self.ow, self.nb, e.code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(e.model._grad[self.wname]), 1, self.n, self.nb, self.n, 1, 1, 0, 0)
+        _sum_slabs(e, e.model._grad[self.wname], self.n, self.nb)
 
     def backward(self, d_out: Grid, d_main: Grid):
         e, xp, o = self.eng, self.xp, self.out
-        _hip.call("cpc_stem_residual_bwd", d_out.ptr(), o.ptr(), _desc(o, o.desc), d_main.ptr(), _desc(d_main, d_main.desc), xp.ptr(),
-                  _desc(xp, xp.desc), _hip.ptr(e.slabs), self.oh, self.ow, 1 if self.relu else 0, self.nb, e.code)
-        _hip.call("cpc_reduce_slabs", _hip.ptr(e.slabs), _hip.ptr(e.model._grad[self.wname]), 1, self.n, self.nb, self.n, 1, 1, 0, 0)
+        _hip.call("cpc_stem_residual_bwd", d_out.ptr(), *o.arg, *d_main.arg, *xp.arg,
+                  _hip.ptr(e.slabs), self.oh, self.ow, 1 if self.relu else 0, self.nb, e.code)
+        _sum_slabs(e, e.model._grad[self.wname], self.n, self.nb)
 
 
 class _Block:
@@ -952,6 +996,9 @@ class _Block:
 
     def __init__(self, eng, idx, blk, gin: Grid, in_f32, last, next_top, prefix="encoder.", need_input_grad=None):
         self.eng, self.idx, self.blk, self.gin, self.in_f32, self.last = eng, idx, blk, gin, in_f32, last
+        # forward() decides per step whether the residual add's backward runs inside the second BatchNorm's passes; those then read the
+        # sign bits of the block output (allocated by the first forward pass that takes the route)
+        self._fused_bwd, self.obits = False, None
         dev, dt = eng.device, eng.dt
         cfg = blk.cfg
         pre = f"{prefix}blocks.{idx}."
@@ -1123,7 +1170,7 @@ class _Block:
             c.prepare()
 
     def forward(self):
-        e, code = self.eng, self.eng.code
+        e = self.eng
         if self.stem is not None:
             self.stem.forward()
         else:
@@ -1131,8 +1178,7 @@ class _Block:
         if self.bn_a is not None:
             self.bn_a.forward()
         if self.pool1 > 1:
-            _hip.call("cpc_maxpool2d_fwd", self.a_full.ptr(), _desc(self.a_full, self.a_full.desc), self.a_a.ptr(),
-                      _desc(self.a_a, self.a_a.desc), self.pool1, 0, code)
+            _maxpool(self.a_full, self.a_a, self.pool1)
         self.conv_b.forward()
         # second BatchNorm + ReLU, residual add and the ReLU between blocks in one pass where nothing else reads the normalised branch
         # (switches.bn_residual off: two passes; the gradient penalty's tangent pass reads it)
@@ -1142,61 +1188,54 @@ class _Block:
         if self.bn_b is not None:
             self.bn_b.forward(apply=not fuse)
         if self.pool2 > 1:
-            _hip.call("cpc_maxpool2d_fwd", self.main_full.ptr(), _desc(self.main_full, self.main_full.desc), self.main.ptr(),
-                      _desc(self.main, self.main.desc), self.pool2, 0, code)
+            _maxpool(self.main_full, self.main, self.pool2)
         if self.blk.residual:
             if self.rp is not None:
-                _hip.call("cpc_maxpool2d_fwd", self.gin.ptr(), _desc(self.gin, self.gin.desc), self.rp.ptr(), _desc(self.rp, self.rp.desc),
-                          self.blk.res_pool, 1 if self.in_f32 else 0, self.rp.code)
+                _maxpool(self.gin, self.rp, self.blk.res_pool, 1 if self.in_f32 else 0)
             if self.res_conv is not None:
                 self.res_conv.forward()
             if self.stem_res is not None:
                 # (fused backward for the first block: needs the ReLU behind the add, i.e. a block that is not the last one)
                 self._fused_bwd = fuse and self.stem_res.relu
-                if self._fused_bwd and getattr(self, "obits", None) is None:
+                if self._fused_bwd and self.obits is None:
                     self.obits = torch.zeros(self.out.rows * self.out.C // 8, device=e.device, dtype=torch.uint8)
                 self.stem_res.forward(self.bn_b if fuse else None, self.obits if self._fused_bwd else None)
             elif fuse:
                 # (the backward pass folds the residual add into the BatchNorm's passes where the residual operand is a bf16 grid: it then
                 # needs the sign bits of the block output in place of the output itself)
                 self._fused_bwd = not self.r_f32
-                if self._fused_bwd and not self.last and getattr(self, "obits", None) is None:
+                if self._fused_bwd and not self.last and self.obits is None:
                     self.obits = torch.zeros(self.out.rows * self.out.C // 8, device=e.device, dtype=torch.uint8)
                 self.bn_b.apply_residual(self.res, self.out, self.oh, self.ow, 0 if self.last else 1, self.r_f32,
                                          self.obits if (self._fused_bwd and not self.last) else None)
             else:
-                _hip.call("cpc_residual_add", self.main.ptr(), _desc(self.main, self.main.desc), self.res.ptr(), _desc(self.res, self.res.desc),
-                          self.out.ptr(), _desc(self.out, self.out.desc), self.oh, self.ow, 0 if self.last else 1, self.r_f32, code)
+                _residual_add(self.main, self.res, self.out, self.oh, self.ow, 0 if self.last else 1, self.r_f32)
 
     # ---- Wasserstein gradient penalty
     def tangent(self):
         """The block applied to the tangent of its input: bias-free convolutions, BatchNorm tangents, pooling and ReLU selections
         taken from the primal pass."""
-        e, code = self.eng, self.eng.code
+        e = self.eng
         T = lambda grid: _twin(e, grid)
         self.conv_a.forward(tangent=True)
         if self.bn_a is not None:
             self.bn_a.tangent()
         if self.pool1 > 1:
-            _hip.call("cpc_maxpool2d_select", self.a_full.ptr(), T(self.a_full).ptr(), _desc(self.a_full, self.a_full.desc),
-                      T(self.a_a).ptr(), _desc(self.a_a, self.a_a.desc), self.pool1, 0, code)
+            _maxpool_select(e, self.a_full, self.a_a, self.pool1)
         self.conv_b.forward(tangent=True)
         if self.bn_b is not None:
             self.bn_b.tangent()
         if self.pool2 > 1:
-            _hip.call("cpc_maxpool2d_select", self.main_full.ptr(), T(self.main_full).ptr(), _desc(self.main_full, self.main_full.desc),
-                      T(self.main).ptr(), _desc(self.main, self.main.desc), self.pool2, 0, code)
+            _maxpool_select(e, self.main_full, self.main, self.pool2)
         if self.blk.residual:
             if self.rp is not None:
-                _hip.call("cpc_maxpool2d_select", self.gin.ptr(), T(self.gin).ptr(), _desc(self.gin, self.gin.desc), T(self.rp).ptr(),
-                          _desc(self.rp, self.rp.desc), self.blk.res_pool, 1 if self.in_f32 else 0, self.rp.code)
+                _maxpool_select(e, self.gin, self.rp, self.blk.res_pool, 1 if self.in_f32 else 0)
             if self.res_conv is not None:
                 self.res_conv.forward(tangent=True)
             out_t = T(self.out)
-            _hip.call("cpc_residual_add", T(self.main).ptr(), _desc(self.main, self.main.desc), T(self.res).ptr(),
-                      _desc(self.res, self.res.desc), out_t.ptr(), _desc(self.out, self.out.desc), self.oh, self.ow, 0, self.r_f32, code)
+            _residual_add(T(self.main), T(self.res), out_t, self.oh, self.ow, 0, self.r_f32)
             if not self.last:
-                _hip.call("cpc_relu_mask", out_t.ptr(), self.out.ptr(), self.out.rows * self.out.C, code)
+                _relu_mask(out_t, self.out)
 
     def gp_grads(self, gp_grad):
         """Penalty parts of this block's parameter gradients + the BatchNorms' second-order terms (between the first backward
@@ -1213,9 +1252,8 @@ class _Block:
             self.bn_a.gp_terms(self.d_a_full if self.pool1 > 1 else self.d_a, gp_grad)
 
     def backward(self):
-        e, code = self.eng, self.eng.code
         first = not self.need_input_grad
-        fused_bwd = getattr(self, "_fused_bwd", False)
+        fused_bwd = self._fused_bwd
         if self.stem_res is not None and fused_bwd:
             self.stem_res.backward_bits(self.d_out, self.obits)
         elif self.stem_res is not None:
@@ -1225,27 +1263,24 @@ class _Block:
         elif self.blk.residual:
             # (d_res was zeroed when it was allocated: the cropped add's backward overwrites the same interior every step and never
             # touches the border)
-            _hip.call("cpc_residual_add_bwd", self.d_out.ptr(), self.out.ptr(), _desc(self.out, self.out.desc), self.d_main.ptr(),
-                      _desc(self.d_main, self.d_main.desc), self.d_res.ptr(), _desc(self.d_res, self.d_res.desc), self.oh, self.ow,
-                      0 if self.last else 1, self.r_f32, code)
+            _residual_add_bwd(self.d_out, self.out, self.d_main, self.d_res, self.oh, self.ow, 0 if self.last else 1, self.r_f32)
 
-        def unpool(full, d_full, pooled, d_pooled, p):
+        def unpool(full, d_full, d_pooled, p):
             """gradient of the pooled activation -> gradient of the full-resolution one (zero outside the windows)"""
             d_full.t.zero_()
-            _hip.call("cpc_maxpool2d_bwd", full.ptr(), d_full.ptr(), _desc(full, full.desc), d_pooled.ptr(), _desc(pooled, pooled.desc),
-                      p, 1, code)
+            _maxpool_bwd(full, d_full, d_pooled, p, 1)
             return d_full
 
         # second convolution
         g_b, act_b = self.d_main, self.main
         if self.pool2 > 1:
-            g_b, act_b = unpool(self.main_full, self.d_main_full, self.main, self.d_main, self.pool2), self.main_full
+            g_b, act_b = unpool(self.main_full, self.d_main_full, self.d_main, self.pool2), self.main_full
         if fused_bwd:
             self.bn_b.backward_res(self.d_out, None if self.last else self.obits, self.d_res if self.stem_res is None else None, self.oh, self.ow)
         elif self.bn_b is not None:
             self.bn_b.backward(g_b)
         else:
-            _hip.call("cpc_relu_mask", g_b.ptr(), act_b.ptr(), g_b.rows * g_b.C, code)
+            _relu_mask(g_b, act_b)
         self.conv_b.backward(self.d_a, mask_input=self.bn_a is None and self.stem is None and self.pool1 == 1)
         if self.stem is not None:          # (block 0: no input gradient, and its residual branch was handled above)
             self.stem.backward(self.d_a)
@@ -1255,9 +1290,9 @@ class _Block:
         # first convolution
         g_a = self.d_a
         if self.pool1 > 1:
-            g_a = unpool(self.a_full, self.d_a_full, self.a_a, self.d_a, self.pool1)
+            g_a = unpool(self.a_full, self.d_a_full, self.d_a, self.pool1)
             if self.bn_a is None:
-                _hip.call("cpc_relu_mask", g_a.ptr(), self.a_full.ptr(), g_a.rows * g_a.C, code)
+                _relu_mask(g_a, self.a_full)
         if self.bn_a is not None:
             self.bn_a.backward(g_a)
         self.conv_a.backward(None if first else self.d_in)
@@ -1267,20 +1302,23 @@ class _Block:
                 if self.rp is not None:
                     self.res_conv.backward(None if first else self.d_rp)
                     if not first:
-                        _hip.call("cpc_maxpool2d_bwd", self.gin.ptr(), self.d_in.ptr(), _desc(self.gin, self.gin.desc), self.d_rp.ptr(),
-                                  _desc(self.rp, self.rp.desc), self.blk.res_pool, 1, self.rp.code)
+                        _maxpool_bwd(self.gin, self.d_in, self.d_rp, self.blk.res_pool, 1)
                 else:
                     self.res_conv.backward(None if first else self.d_in, accumulate=True)
             elif not first:
-                if self.rp is not None:
-                    _hip.call("cpc_maxpool2d_bwd", self.gin.ptr(), self.d_in.ptr(), _desc(self.gin, self.gin.desc), self.d_res.ptr(),
-                              _desc(self.rp, self.rp.desc), self.blk.res_pool, 1, self.rp.code)
+                if self.rp is not None:          # (no projection: the pooled input is the residual operand, d_res its gradient)
+                    _maxpool_bwd(self.gin, self.d_in, self.d_res, self.blk.res_pool, 1)
                 else:
                     _accumulate(self.d_in, self.d_res)
 
 
 class ScalogramCPCEngine(CPCEngine):
     """CPCEngine whose encoder is a ScalogramResidualEncoder fed with (B, C, bins, frames) scalograms."""
+
+    side_job = None       # a callable the caller leaves for the next encoder_forward() (see there)
+    _x_alias = None       # (batch tensor, its version) while x_grid reads the caller's memory in place
+    _gp_sp = None         # softplus-score buffers of the gradient-penalty step, and
+    gp_flat = None        # the penalty's part of the flat gradient: both made by the first such step
 
     def __init__(self, model, in_shape, device, dtype: torch.dtype, gradient_penalty: bool = False):
         """``gradient_penalty``: also provide the gradient with respect to the input scalogram and the tangent pass the
@@ -1380,7 +1418,7 @@ class ScalogramCPCEngine(CPCEngine):
         # the upper blocks' backward passes) the main queue holds short, latency-bound launches.  Measured on configs[2] (30 steps after
         # 15, one box): off 12.08 - 12.17 ms, in front of the step 12.25, after block 0 / 1 / 2 / 3: 12.15 / 12.04 / 12.00 / 11.84, behind
         # the loss kernels 11.86; on a stream of its own at the default priority 11.88 - 12.25.
-        job, self.side_job = getattr(self, "side_job", None), None
+        job, self.side_job = self.side_job, None
         for b in self.blocks:
             b.forward()
         if job is not None:
@@ -1402,7 +1440,7 @@ class ScalogramCPCEngine(CPCEngine):
         return top_t.t
 
     def _backward_encoder(self, x, grad_ready_hook=None):
-        alias = getattr(self, "_x_alias", None)
+        alias = self._x_alias
         if alias is not None and alias[0]._version != alias[1]:
             raise RuntimeError("the scalogram batch was modified in place between the forward and the backward pass: the engine reads it in "
                                "place (no copy) and recomputes its first block from it — pass a tensor you do not write to, or a clone")
@@ -1430,7 +1468,7 @@ class ScalogramCPCEngine(CPCEngine):
 
     def _gp_softplus_buffers(self, all_timesteps):
         key = bool(all_timesteps)
-        if getattr(self, "_gp_sp", None) is not None and self._gp_sp.key == key:
+        if self._gp_sp is not None and self._gp_sp.key == key:
             return
         B, K = self.B, self.K
         n = (B * K) * ((B * K + 7) // 8 * 8) if all_timesteps else K * B * self.ldS
@@ -1449,6 +1487,17 @@ class ScalogramCPCEngine(CPCEngine):
             dst, src = getattr(sp, name + "s"), getattr(sp, name)
             if dst is not src:
                 dst.copy_(src)
+
+    def _gp_score_layout(self, all_timesteps):
+        """What the loss's two score layouts change in a gradient-penalty step (every (b,k,b',k') pair scores, or the pairs of one step k):
+        the score GEMM and the buffer it fills, the (K, rows, cols, ld of W, ld of W^T) of cpc_gp_score_coeff, the contraction of such
+        coefficients with predictions / targets, and the dimensions the linear scores' seeds are summed over."""
+        B, K = self.B, self.K
+        if all_timesteps:
+            R = B * K
+            ldR = (R + 7) // 8 * 8
+            return SimpleNamespace(gemm=self.score_gemm_all, S="S_all", dims=(1, R, R, ldR, ldR), grads=self._score_grads_all, seed_dims=(0, 1))
+        return SimpleNamespace(gemm=self.score_gemm, S="S", dims=(K, B, B, self.ldS, self.ldS), grads=self._score_grads, seed_dims=(0,))
 
     def _gp_step(self, x, softplus, regularization, all_timesteps, factor, global_negatives, after_loss):
         """One train step with the Wasserstein gradient penalty (contrastive_estimation_training.py:141-161):
@@ -1478,7 +1527,7 @@ class ScalogramCPCEngine(CPCEngine):
             # Grid-based context networks (ConvolutionalArModel / ScalogramResidualEncoder contexts: the reference's e22-e26 and its
             # script default e29) run in bf16 too; a GRU or attention context computes in float32 inside the bf16 engine
             # (contexts.Float32Context: their second-order sweeps are float32 kernels).
-            if not isinstance(self.ctx, (ConvArGridContext, ResNetArContext, Float32Context)):
+            if not isinstance(self.ctx, (GridContext, Float32Context)):
                 raise NotImplementedError(f"gradient penalty with bf16 storage: no route for {type(self.ctx).__name__} "
                                           f"(compute_dtype='fp32' runs it)")
         if not hasattr(self.ctx, "tangent"):
@@ -1488,7 +1537,8 @@ class ScalogramCPCEngine(CPCEngine):
         Ltop = self.geo.alloc[-1]
         top = self.act[-1].view(B, Ltop, E)
         dtop = self.dact[-1].view(B, Ltop, E)
-        if getattr(self, "gp_flat", None) is None:
+        lay = self._gp_score_layout(all_timesteps)
+        if self.gp_flat is None:
             self.gp_flat = torch.zeros_like(model._flat_grad)
             self.gp_grad = {n: self.gp_flat[model._offset[n]:model._offset[n] + p_.numel()].view(p_.shape) for n, p_ in model.named_parameters()}
             self.gp_partial = torch.zeros(256, device=self.device, dtype=torch.float32)
@@ -1497,12 +1547,8 @@ class ScalogramCPCEngine(CPCEngine):
         # ---- pass 1: adjoints of S = sum of the scores the loss is built from (all (b,k,b',k') pairs, or the equal-step ones)
         pred3 = self.pred.view(B, K, E)
         tg = top[:, T - K:T, :]
-        if all_timesteps:
-            seed_p = over_ranks(tg.sum((0, 1), keepdim=True)).expand(B, K, E)
-            seed_t = over_ranks(pred3.sum((0, 1), keepdim=True)).expand(B, K, E)
-        else:
-            seed_p = over_ranks(tg.sum(0, keepdim=True)).expand(B, K, E)
-            seed_t = over_ranks(pred3.sum(0, keepdim=True)).expand(B, K, E)
+        seed_p = over_ranks(tg.sum(lay.seed_dims, keepdim=True)).expand(B, K, E)
+        seed_t = over_ranks(pred3.sum(lay.seed_dims, keepdim=True)).expand(B, K, E)
         self.dact[-1].zero_()
         if softplus and gn is not None:
             # softplus scores over the GLOBAL score matrix (engine.GlobalNegatives.gp_softplus_*)
@@ -1513,18 +1559,10 @@ class ScalogramCPCEngine(CPCEngine):
             # softplus scores: the summed scores are sum softplus(s), the seeds carry W1 = sigmoid(s) (cpc_gp_score_coeff)
             self._gp_softplus_buffers(all_timesteps)
             sp = self._gp_sp
-            if all_timesteps:
-                R = B * K
-                ldR = (R + 7) // 8 * 8
-                self.score_gemm_all()
-                _hip.call("cpc_gp_score_coeff", _hip.ptr(self.S_all), None, None, _hip.ptr(sp.W1), _hip.ptr(sp.W1T), 1, R, R, ldR, ldR, 0)
-                self._gp_coeff("W1", "W1T")
-                self._score_grads_all(sp.W1s, sp.W1Ts, self.pred, self.act[-1], self.dpred, self.dact[-1])
-            else:
-                self.score_gemm()
-                _hip.call("cpc_gp_score_coeff", _hip.ptr(self.S), None, None, _hip.ptr(sp.W1), _hip.ptr(sp.W1T), K, B, B, self.ldS, self.ldS, 0)
-                self._gp_coeff("W1", "W1T")
-                self._score_grads(sp.W1s, sp.W1Ts, self.pred, self.act[-1], self.dpred, self.dact[-1])
+            lay.gemm()
+            _hip.call("cpc_gp_score_coeff", _hip.ptr(getattr(self, lay.S)), None, None, _hip.ptr(sp.W1), _hip.ptr(sp.W1T), *lay.dims, 0)
+            self._gp_coeff("W1", "W1T")
+            lay.grads(sp.W1s, sp.W1Ts, self.pred, self.act[-1], self.dpred, self.dact[-1])
         else:
             self.dpred.view(B, K, E).copy_(seed_p)
             dtop[:, T - K:T, :].copy_(seed_t)
@@ -1564,32 +1602,18 @@ class ScalogramCPCEngine(CPCEngine):
             # W2 = softplus''(s) * (tangent of s),  tangent of s = (tangent predictions) targets^T + predictions (tangent targets)^T
             sp = self._gp_sp
             sp.top_a.zero_(), sp.top_b.zero_()
-            if all_timesteps:
-                R = B * K
-                ldR = (R + 7) // 8 * 8
-                self.score_gemm_all(pred=self.pred_t, out=sp.St1)
-                self.score_gemm_all(top=top_t, out=sp.St2)
-                _hip.call("cpc_gp_score_coeff", _hip.ptr(self.S_all), _hip.ptr(sp.St1), _hip.ptr(sp.St2), _hip.ptr(sp.W2), _hip.ptr(sp.W2T),
-                          1, R, R, ldR, ldR, 1)
-                self._gp_coeff("W2", "W2T")
-                self._score_grads_all(sp.W1s, sp.W1Ts, self.pred_t, top_t, sp.pred_a, sp.top_a)
-                self._score_grads_all(sp.W2s, sp.W2Ts, self.pred, self.act[-1], sp.pred_b, sp.top_b)
-            else:
-                self.score_gemm(pred=self.pred_t, out=sp.St1)
-                self.score_gemm(top=top_t, out=sp.St2)
-                _hip.call("cpc_gp_score_coeff", _hip.ptr(self.S), _hip.ptr(sp.St1), _hip.ptr(sp.St2), _hip.ptr(sp.W2), _hip.ptr(sp.W2T),
-                          K, B, B, self.ldS, self.ldS, 1)
-                self._gp_coeff("W2", "W2T")
-                self._score_grads(sp.W1s, sp.W1Ts, self.pred_t, top_t, sp.pred_a, sp.top_a)
-                self._score_grads(sp.W2s, sp.W2Ts, self.pred, self.act[-1], sp.pred_b, sp.top_b)
+            lay.gemm(pred=self.pred_t, out=sp.St1)
+            lay.gemm(top=top_t, out=sp.St2)
+            _hip.call("cpc_gp_score_coeff", _hip.ptr(getattr(self, lay.S)), _hip.ptr(sp.St1), _hip.ptr(sp.St2), _hip.ptr(sp.W2), _hip.ptr(sp.W2T),
+                      *lay.dims, 1)
+            self._gp_coeff("W2", "W2T")
+            lay.grads(sp.W1s, sp.W1Ts, self.pred_t, top_t, sp.pred_a, sp.top_a)
+            lay.grads(sp.W2s, sp.W2Ts, self.pred, self.act[-1], sp.pred_b, sp.top_b)
             add_p = sp.pred_a.view(B, K, E) + sp.pred_b.view(B, K, E)
             add_t = sp.top_a.view(B, Ltop, E)[:, T - K:T, :] + sp.top_b.view(B, Ltop, E)[:, T - K:T, :]
-        elif all_timesteps:
-            add_p = over_ranks(tg_t.sum((0, 1), keepdim=True)).expand(B, K, E)
-            add_t = over_ranks(pred_t3.sum((0, 1), keepdim=True)).expand(B, K, E)
         else:
-            add_p = over_ranks(tg_t.sum(0, keepdim=True)).expand(B, K, E)
-            add_t = over_ranks(pred_t3.sum(0, keepdim=True)).expand(B, K, E)
+            add_p = over_ranks(tg_t.sum(lay.seed_dims, keepdim=True)).expand(B, K, E)
+            add_t = over_ranks(pred_t3.sum(lay.seed_dims, keepdim=True)).expand(B, K, E)
         add_p, add_t = add_p.clone(), add_t.clone()
         self.dact[-1].zero_()
         if gn is not None:
@@ -1620,6 +1644,7 @@ class ScalogramCPCEngine(CPCEngine):
 class _ArBlock:
     def __init__(self, eng, idx, blk, gin: Grid, kernel, stride, pool, cin, cout, batch_norm, residual, bias):
         self.eng, self.idx, self.gin, self.pool, self.stride = eng, idx, gin, pool, stride
+        self._fused_bwd = False       # forward() decides per step (see _Block)
         dev, dt = eng.device, eng.dt
         pre = f"autoregressive_model.module_list.{idx}."
         ci = 1 if pool > 1 else 0
@@ -1684,10 +1709,8 @@ class _ArBlock:
             c.prepare()
 
     def forward(self):
-        code = self.eng.code
         if self.pool > 1:
-            _hip.call("cpc_maxpool2d_fwd", self.gin.ptr(), _desc(self.gin, self.gin.desc), self.xp.ptr(), _desc(self.xp, self.xp.desc),
-                      self.pool, 0, code)
+            _maxpool(self.gin, self.xp, self.pool)
         self.conv.forward()
         # BatchNorm1d + ReLU and the residual add in one pass where nothing else reads the normalised branch (see _Block.forward)
         fuse = (self.bn is not None and self.residual and self.bn.abits is not None and not self.eng.gp_capable and
@@ -1696,34 +1719,29 @@ class _ArBlock:
             self.bn.forward(apply=not fuse)
         if self.residual:
             if self.rp is not None and self.rp is not self.xp:
-                _hip.call("cpc_maxpool2d_fwd", self.gin.ptr(), _desc(self.gin, self.gin.desc), self.rp.ptr(), _desc(self.rp, self.rp.desc),
-                          self.pool * self.stride, 0, code)
+                _maxpool(self.gin, self.rp, self.pool * self.stride)
             if self.res_conv is not None:
                 self.res_conv.forward()
             self._fused_bwd = fuse
             if fuse:
                 self.bn.apply_residual(self.res, self.out, self.oh, 0, 0, 0)
             else:
-                _hip.call("cpc_residual_add", self.main.ptr(), _desc(self.main, self.main.desc), self.res.ptr(), _desc(self.res, self.res.desc),
-                          self.out.ptr(), _desc(self.out, self.out.desc), self.oh, 0, 0, 0, code)
+                _residual_add(self.main, self.res, self.out, self.oh)
 
     def tangent(self):
-        e, code = self.eng, self.eng.code
+        e = self.eng
         T = lambda grid: _twin(e, grid)
         if self.pool > 1:
-            _hip.call("cpc_maxpool2d_select", self.gin.ptr(), T(self.gin).ptr(), _desc(self.gin, self.gin.desc), T(self.xp).ptr(),
-                      _desc(self.xp, self.xp.desc), self.pool, 0, code)
+            _maxpool_select(e, self.gin, self.xp, self.pool)
         self.conv.forward(tangent=True)
         if self.bn is not None:
             self.bn.tangent()
         if self.residual:
             if self.rp is not None and self.rp is not self.xp:
-                _hip.call("cpc_maxpool2d_select", self.gin.ptr(), T(self.gin).ptr(), _desc(self.gin, self.gin.desc), T(self.rp).ptr(),
-                          _desc(self.rp, self.rp.desc), self.pool * self.stride, 0, code)
+                _maxpool_select(e, self.gin, self.rp, self.pool * self.stride)
             if self.res_conv is not None:
                 self.res_conv.forward(tangent=True)
-            _hip.call("cpc_residual_add", T(self.main).ptr(), _desc(self.main, self.main.desc), T(self.res).ptr(),
-                      _desc(self.res, self.res.desc), T(self.out).ptr(), _desc(self.out, self.out.desc), self.oh, 0, 0, 0, code)
+            _residual_add(T(self.main), T(self.res), T(self.out), self.oh)
 
     def gp_grads(self, gp_grad):
         self.conv.gp_wgrad(gp_grad)
@@ -1733,18 +1751,16 @@ class _ArBlock:
             self.bn.gp_terms(self.d_main, gp_grad)
 
     def backward(self):
-        code = self.eng.code
-        fused_bwd = self.residual and getattr(self, "_fused_bwd", False)
+        fused_bwd = self._fused_bwd      # (set by forward() of a block with a residual branch only)
         if self.residual and not fused_bwd:
             # (d_res was zeroed when it was allocated; the cropped add's backward overwrites the same interior every step)
-            _hip.call("cpc_residual_add_bwd", self.d_out.ptr(), self.out.ptr(), _desc(self.out, self.out.desc), self.d_main.ptr(),
-                      _desc(self.d_main, self.d_main.desc), self.d_res.ptr(), _desc(self.d_res, self.d_res.desc), self.oh, 0, 0, 0, code)
+            _residual_add_bwd(self.d_out, self.out, self.d_main, self.d_res, self.oh)
         if fused_bwd:      # the add's backward inside the BatchNorm's passes (no ReLU behind the add in a ConvolutionalArBlock: no output mask)
             self.bn.backward_res(self.d_out, None, self.d_res, self.oh, 0)
         elif self.bn is not None:
             self.bn.backward(self.d_main)
         else:
-            _hip.call("cpc_relu_mask", self.d_main.ptr(), self.main.ptr(), self.d_main.rows * self.d_main.C, code)
+            _relu_mask(self.d_main, self.main)
         self.conv.backward(self.d_xp)                                  # writes the gradient of the (pooled) block input
         shared = self.residual and (self.rp is self.xp or self.rp is None)
         if self.residual and shared:                                   # residual source is the conv input itself
@@ -1753,50 +1769,46 @@ class _ArBlock:
             else:
                 _accumulate(self.d_xp, self.d_res)
         if self.pool > 1:
-            _hip.call("cpc_maxpool2d_bwd", self.gin.ptr(), self.d_in.ptr(), _desc(self.gin, self.gin.desc), self.d_xp.ptr(),
-                      _desc(self.xp, self.xp.desc), self.pool, 0, code)
+            _maxpool_bwd(self.gin, self.d_in, self.d_xp, self.pool, 0)
         if self.residual and not shared:                               # own pooling (stride > 1)
             if self.res_conv is not None:
                 self.res_conv.backward(self.d_rp)
                 src = self.d_rp
             else:
-                src = self.d_res
-            _hip.call("cpc_maxpool2d_bwd", self.gin.ptr(), self.d_in.ptr(), _desc(self.gin, self.gin.desc), src.ptr(),
-                      _desc(self.rp, self.rp.desc), self.pool * self.stride, 1, code)
+                src = self.d_res                                       # (no projection: the pooled input is the residual operand)
+            _maxpool_bwd(self.gin, self.d_in, src, self.pool * self.stride, 1)
 
 
-class ConvArGridContext(Context):
-    """ConvolutionalArModel with batch_norm and / or residual (e.g. ar_conv_architecture_2/3) as the context network."""
+class GridContext(Context):
+    """A context network that runs as a chain of grid blocks: the V visible frames z are copied into the grid ``x0``, the blocks run
+    on it, and c is one position of every item of the last block's output grid.  A subclass builds x0 and the blocks (_build), says
+    where c sits (_c_row) and which channel count sizes the column-sum scratch behind the slabs (_slab_width)."""
 
     ahead_ok = True       # prepare_weights is a pure function of the parameters (ScalogramCPCEngine.prepare_ahead)
 
-    def __init__(self, eng, ar):
-        self.eng, self.ar = eng, ar
-        self.channels = list(ar.channel_count)
-        if self.channels[0] != eng.E or self.channels[-1] != eng.H:
-            raise ValueError("ConvolutionalArModel channel_count does not match enc_size / ar_size")
-        if any(c % 8 for c in self.channels):
-            raise NotImplementedError("ConvolutionalArModel channel counts must be multiples of 8")
+    def _build(self):
+        """-> (x0, blocks), every block on the output grid of the one before."""
+        raise NotImplementedError
+
+    def _c_row(self, grid):
+        """The row of column 0 of ``grid`` that holds c."""
+        raise NotImplementedError
+
+    def _slab_width(self):
+        raise NotImplementedError
 
     def allocate(self):
-        e, ar = self.eng, self.ar
-        self.x0 = Grid(e.B, 1, e.V, e.E, e.device, e.dt)
-        self.blocks = []
-        gin = self.x0
-        for l in range(len(ar.kernel_sizes)):
-            b = _ArBlock(e, l, ar.module_list[l], gin, ar.kernel_sizes[l], ar.strides[l], ar.poolings[l], self.channels[l],
-                         self.channels[l + 1], ar.batch_norm, ar.residual, ar.module_list[l].main_modules[1 if ar.poolings[l] > 1 else 0].bias is not None)
-            self.blocks.append(b)
-            gin = b.out
+        e = self.eng
+        self.x0, self.blocks = self._build()
         self.d_x0 = self.x0.like(e.device)
         d_in = self.d_x0
         for b in self.blocks:
             b.allocate_grads(d_in)
             d_in = b.d_out
-        self.c32 = torch.empty(e.B, self.channels[-1], device=e.device, dtype=torch.float32)
+        self.c32 = torch.empty(e.B, self.blocks[-1].out.C, device=e.device, dtype=torch.float32)
 
     def slab_floats(self):
-        return max(b.slab for b in self.blocks) + self.eng.colsum_blocks * max(self.channels)
+        return max(b.slab for b in self.blocks) + self.eng.colsum_blocks * self._slab_width()
 
     def prepare_weights(self):
         _prepare_convs(self.eng, self, [c for b in self.blocks for c in b.convs()])
@@ -1806,6 +1818,13 @@ class ConvArGridContext(Context):
         t0 = e.T - e.K - e.V
         return buf.view(e.B, e.geo.alloc[-1], e.E)[:, t0:t0 + e.V, :]
 
+    def _c_view(self, grid):
+        return grid.t.view(grid.B, grid.W, grid.Ha, grid.C)[:, 0, self._c_row(grid), :]
+
+    def _c_operand(self, grid, values):
+        """(tensor, element offset, item stride) of c in ``values``, a grid of the geometry of ``grid``."""
+        return values.t, self._c_row(grid) * grid.C, grid.W * grid.Ha * grid.C
+
     def forward(self):
         e = self.eng
         self.x0.t.view(e.B, e.V, e.E).copy_(self._z_rows(e.act[-1]))
@@ -1814,11 +1833,10 @@ class ConvArGridContext(Context):
 
     def c_operand(self):
         out = self.blocks[-1].out
-        return out.t, (out.top + out.H - 1) * out.C, out.Ha * out.C
+        return self._c_operand(out, out)
 
     def c_float(self):
-        out = self.blocks[-1].out
-        self.c32.copy_(out.t.view(out.B, out.Ha, out.C)[:, out.top + out.H - 1, :])
+        self.c32.copy_(self._c_view(self.blocks[-1].out))
         return self.c32
 
     # ---- Wasserstein gradient penalty: tangent of c, penalty parts of the parameter gradients
@@ -1829,7 +1847,7 @@ class ConvArGridContext(Context):
         for b in self.blocks:
             b.tangent()
         out = self.blocks[-1].out
-        return _twin(e, out).t, (out.top + out.H - 1) * out.C, out.Ha * out.C
+        return self._c_operand(out, _twin(e, out))
 
     def gp_grads(self, gp_grad):
         for b in self.blocks:
@@ -1837,98 +1855,76 @@ class ConvArGridContext(Context):
 
     def backward(self, dc):
         e = self.eng
-        last = self.blocks[-1]
-        d = last.d_out
-        # (only the last position carries a gradient; the rest of the grid was zeroed when it was allocated and nothing writes it)
-        d.t.view(d.B, d.Ha, d.C)[:, d.top + d.H - 1, :] = dc.to(d.t.dtype)
+        # (only c's position carries a gradient; the rest of the grid was zeroed when it was allocated and nothing writes it)
+        self._c_view(self.blocks[-1].d_out).copy_(dc)
         for b in reversed(self.blocks):
             b.backward()
         self._z_rows(e.dact[-1]).copy_(self.d_x0.t.view(e.B, e.V, e.E))
 
 
-class ResNetArContext(Context):
+class ConvArGridContext(GridContext):
+    """ConvolutionalArModel with batch_norm and / or residual (e.g. ar_conv_architecture_2/3) as the context network: z (B, E, V) is the
+    grid [B][W = 1][H = V][E], c the LAST row of what is left (audio_model.py:161)."""
+
+    def __init__(self, eng, ar):
+        self.eng, self.ar = eng, ar
+        self.channels = list(ar.channel_count)
+        if self.channels[0] != eng.E or self.channels[-1] != eng.H:
+            raise ValueError("ConvolutionalArModel channel_count does not match enc_size / ar_size")
+        if any(c % 8 for c in self.channels):
+            raise NotImplementedError("ConvolutionalArModel channel counts must be multiples of 8")
+
+    def _build(self):
+        e, ar = self.eng, self.ar
+        x0 = Grid(e.B, 1, e.V, e.E, e.device, e.dt)
+        blocks, gin = [], x0
+        for l in range(len(ar.kernel_sizes)):
+            b = _ArBlock(e, l, ar.module_list[l], gin, ar.kernel_sizes[l], ar.strides[l], ar.poolings[l], self.channels[l],
+                         self.channels[l + 1], ar.batch_norm, ar.residual, ar.module_list[l].main_modules[1 if ar.poolings[l] > 1 else 0].bias is not None)
+            blocks.append(b)
+            gin = b.out
+        return x0, blocks
+
+    def _c_row(self, grid):
+        return grid.top + grid.H - 1
+
+    def _slab_width(self):
+        return max(self.channels)
+
+
+class ResNetArContext(GridContext):
     """ScalogramResidualEncoder used as the autoregressive model (reference configs ar_resnet_architecture_1/2: blocks with
     (1,k) kernels, pooling_1 = 2 with ceil mode, batch norm, residual branches): z (B, E, V) is the grid [B][W = V][H = 1][E];
     the model takes the first remaining time step of the (B, C, T') result (audio_model.py:203-204)."""
-
-    ahead_ok = True       # prepare_weights is a pure function of the parameters (ScalogramCPCEngine.prepare_ahead)
 
     def __init__(self, eng, ar):
         self.eng, self.ar = eng, ar
         if ar.phase:
             raise ValueError("a ScalogramResidualEncoder used as context network must have phase=False")
 
-    def allocate(self):
+    def _build(self):
         e, ar = self.eng, self.ar
         blocks = list(ar.blocks)
         if blocks[0].cfg['in_channels'] != e.E or blocks[-1].cfg['out_channels'] != e.H:
             raise ValueError("context network block channels do not match enc_size / ar_size")
         if blocks[0].cfg['top_padding_1']:
             raise NotImplementedError("top_padding_1 on the first block")
-        self.x0 = Grid(e.B, e.V, 1, e.E, e.device, e.dt)
-        self.blocks, gin = [], self.x0
+        x0 = Grid(e.B, e.V, 1, e.E, e.device, e.dt)
+        built, gin = [], x0
         for i, blk in enumerate(blocks):
             last = i == len(blocks) - 1
             next_top = 0 if last else (blocks[i + 1].cfg['top_padding_1'] or 0)
             b = _Block(e, i, blk, gin, False, last, next_top, prefix="autoregressive_model.", need_input_grad=True)
-            self.blocks.append(b)
+            built.append(b)
             gin = b.out
-        out = self.blocks[-1].out
-        if out.H != 1:
+        if built[-1].out.H != 1:
             raise NotImplementedError("the context network must end with one row")
-        self.d_x0 = self.x0.like(e.device)
-        d_in = self.d_x0
-        for b in self.blocks:
-            b.allocate_grads(d_in)
-            d_in = b.d_out
-        self.c32 = torch.empty(e.B, out.C, device=e.device, dtype=torch.float32)
+        return x0, built
 
-    def slab_floats(self):
-        return max(b.slab for b in self.blocks) + self.eng.colsum_blocks * max(max(b.a_a.C, b.conv_b.cout) for b in self.blocks)
+    def _c_row(self, grid):
+        return grid.top
 
-    def prepare_weights(self):
-        _prepare_convs(self.eng, self, [c for b in self.blocks for c in b.convs()])
+    def _slab_width(self):
+        return max(max(b.a_a.C, b.conv_b.cout) for b in self.blocks)
 
-    def _z_rows(self, buf):
-        e = self.eng
-        t0 = e.T - e.K - e.V
-        return buf.view(e.B, e.geo.alloc[-1], e.E)[:, t0:t0 + e.V, :]
 
-    def forward(self):
-        e = self.eng
-        self.x0.t.view(e.B, e.V, e.E).copy_(self._z_rows(e.act[-1]))
-        for b in self.blocks:
-            b.forward()
-
-    def _first_step(self, grid):
-        return grid.t.view(grid.B, grid.W, grid.Ha, grid.C)[:, 0, grid.top, :]
-
-    def c_operand(self):
-        out = self.blocks[-1].out
-        return out.t, out.top * out.C, out.W * out.Ha * out.C
-
-    # ---- Wasserstein gradient penalty (see ConvArGridContext)
-    def tangent(self, top_t):
-        e = self.eng
-        _twin(e, self.x0).t.view(e.B, e.V, e.E).copy_(self._z_rows(top_t))
-        for b in self.blocks:
-            b.tangent()
-        out = self.blocks[-1].out
-        return _twin(e, out).t, out.top * out.C, out.W * out.Ha * out.C
-
-    def gp_grads(self, gp_grad):
-        for b in self.blocks:
-            b.gp_grads(gp_grad)
-
-    def c_float(self):
-        self.c32.copy_(self._first_step(self.blocks[-1].out))
-        return self.c32
-
-    def backward(self, dc):
-        e = self.eng
-        d = self.blocks[-1].d_out
-        # (only the first time step carries a gradient; the rest of the grid was zeroed when it was allocated and nothing writes it)
-        self._first_step(d).copy_(dc)
-        for b in reversed(self.blocks):
-            b.backward()
-        self._z_rows(e.dact[-1]).copy_(self.d_x0.t.view(e.B, e.V, e.E))

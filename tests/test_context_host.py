@@ -82,9 +82,9 @@ def test_engines_use_the_host_helpers_unchanged():
 
 def test_context_protocol_defaults():
     from cpc_audio_amd.contexts import AttentionContext, ConvArContext, Float32Context, GRUContext
-    from cpc_audio_amd.scalogram_engine import ConvArGridContext, ResNetArContext
+    from cpc_audio_amd.scalogram_engine import ConvArGridContext, GridContext, ResNetArContext
     assert Context.ahead_ok is False and Context.z_scale == 1.0
-    for cls in (GRUContext, ConvArContext, AttentionContext, Float32Context, ConvArGridContext, ResNetArContext):
+    for cls in (GRUContext, ConvArContext, AttentionContext, Float32Context, GridContext, ConvArGridContext, ResNetArContext):
         assert issubclass(cls, Context), cls.__name__
     bare = Context()
     with pytest.raises(NotImplementedError):

@@ -82,7 +82,14 @@ class CpcWaveAugment(C.Structure):
                 ("gain_on", C.c_int), ("gain_lo_db", C.c_float), ("gain_hi_db", C.c_float), ("polarity_threshold", C.c_ulonglong)]
 
 
-_P, _I, _L, _F, _D, _U64, _U32 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_uint
+class CpcGridMask(C.Structure):
+    """cpc_grid_mask's configuration (include/cpc_hip.h, cpc_grid_mask_cfg)."""
+    _fields_ = [("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("clip_offset", C.c_ulonglong), ("protect_last", C.c_int),
+                ("freq_count", C.c_int), ("freq_max", C.c_int), ("time_count", C.c_int), ("time_cap", C.c_int),
+                ("fill_mode", C.c_int), ("fill_value", C.c_float)]
+
+
+_P, _I, _L, _F, _D, _U64, _U32 =C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_uint
 _SIGNATURES = {
     "cpc_abi_version": ([], _I),
     "cpc_gemm_nt": ([C.POINTER(GemmNTArgs), _P], _I),
@@ -223,6 +230,9 @@ _SIGNATURES = {
     "cpc_wave_power": ([_P, _P, _I, _I, _L, _I, _P], _I),
     "cpc_wave_augment": ([_P, _P, _P, _P, _I, _I, _L, _L, C.POINTER(CpcWaveAugment), _P], _I),
     "cpc_mel_pointwise": ([_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P], _I),
+    "cpc_grid_sum_chunks": ([_I], _I),
+    "cpc_grid_sum": ([_P, _P, _I, _I, _L, _I, _P], _I),
+    "cpc_grid_mask": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, C.POINTER(CpcGridMask), _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -651,6 +651,12 @@ class ContrastiveEstimationTrainer:
         # never augment.
         self.augmentation = None
         self.augment_targets = True
+        # Not in the reference: masking on the preprocessed grid ("Grid masking").  grid_masking: None, or a
+        # grid_masking.GridMasking — the scalogram or log-mel grid of batch i of a train() call is masked in place right behind the
+        # preprocessing module, on its stream, with step = continue_training_at_step + i and clip_offset = rank * batch_size (behind
+        # ``augmentation`` where both are set: waveform first, grid second).  Not with use_graph or the gradient penalty.
+        # validate(), calc_test_task_data() and test_task never mask.
+        self.grid_masking = None
         self._ema = None          # the shadow: a flat f32 tensor shaped like model._flat_param
         self._ema_owner = None    # who updates it at present: the latest train() call's FusedAdam or TorchEma
         # Not in the reference: the preprocessing module of the NEXT batch runs on the side stream beside the current step (InputAhead)
@@ -985,6 +991,39 @@ class ContrastiveEstimationTrainer:
             out = aug(batch, next(steps), clip_offset=clip_offset, protect_from=protect(batch.shape[1]))
             yield (out, item[1]) if with_indices else out
 
+    def _check_grid_masking(self):
+        """None without grid masking, else the GridMasking.  TypeError for anything else, ValueError where no grid exists (no
+        preprocessing module, or one that hands the waveform on), NotImplementedError with use_graph or the gradient penalty."""
+        masking = self.grid_masking
+        if masking is None:
+            return None
+        from .grid_masking import GridMasking
+        if not isinstance(masking, GridMasking):
+            raise TypeError(f"grid_masking must be None or a grid_masking.GridMasking, got {type(masking).__name__}")
+        pre = self.preprocessing
+        if (pre is None or isinstance(pre, torch.nn.Identity) or (hasattr(pre, "cqt") and pre.cqt is None)
+                or (hasattr(pre, "mel") and pre.mel is None)):
+            raise ValueError("grid_masking needs a preprocessing module that returns a grid (scalogram_model.PreprocessingModule with a "
+                             "cqt_dict, mel_spectrogram.MelPreprocessingModule with a mel_dict): the waveform has no frequency axis")
+        if self.use_graph:
+            raise NotImplementedError("grid_masking: use_graph replays one captured step, but the mask's step number is a host-side "
+                                      "launch argument that changes every step")
+        if self.wasserstein_gradient_penalty:
+            raise NotImplementedError("grid_masking with wasserstein_gradient_penalty is not verified (the penalty differentiates with "
+                                      "respect to the preprocessed grid)")
+        return masking
+
+    def _masked_input(self, masking, steps, clip_offset):
+        """_model_input followed by the mask, in place and on the stream _model_input ran on: the i-th call of a run masks at step
+        next(``steps``) (the batches are preprocessed in batch order, the one preprocessed ahead included)."""
+        def model_input(batch):
+            x = self._model_input(batch)
+            if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                raise ValueError("grid_masking: the preprocessing module did not return a (B, channels, bins, frames) grid")
+            masking(x.permute(0, 3, 2, 1), next(steps), clip_offset=clip_offset)          # the channels-last buffer behind the view
+            return x
+        return model_input
+
     @staticmethod
     def _world():
         import torch.distributed as dist
@@ -1057,6 +1096,7 @@ class ContrastiveEstimationTrainer:
         bank_kw = self._bank_kw(self._check_negative_bank())
         augmenting = self._check_augmentation()
         aug_steps = itertools.count(int(continue_training_at_step))          # the step of the next batch the augmentation sees
+        masking = self._check_grid_masking()
         max_grad_norm = self._check_grad_clip()
         weight_decay, decay_filter, schedule = self._check_adamw()
         trust = self._check_trust()
@@ -1070,6 +1110,8 @@ class ContrastiveEstimationTrainer:
         run = self._make_optimizer(lr, device, world, int(continue_training_at_step), max_grad_norm,
                                    (weight_decay, decay_filter, schedule), trust, ema, device_temp)
         optimizer, fused = run.optimizer, run.fused
+        if masking is not None:
+            run.model_input = self._masked_input(masking, itertools.count(int(continue_training_at_step)), rank * int(batch_size))
         sampler = FileBatchSampler(index_count_per_file=self.dataset.get_example_count_per_file(),
                                    batch_size=batch_size * world, file_batch_size=self.file_batch_size, drop_last=True,
                                    verbose=self.verbose)
@@ -1092,7 +1134,7 @@ class ContrastiveEstimationTrainer:
                 ahead = None
                 if (fused and not run.graphed and self.preprocessing is not None and self.preprocess_ahead and device.type == "cuda"
                         and switches.preprocess_ahead()):
-                    ahead = InputAhead(self._model_input, device)
+                    ahead = InputAhead(run.model_input, device)
                 batches = self._batches(self.dataset, sampler, device, num_workers, True, rank, world,
                                         with_indices=grouping is not None)
                 if augmenting is not None:          # in front of everything that sees a batch, the one preprocessed ahead included
@@ -1122,7 +1164,7 @@ class ContrastiveEstimationTrainer:
                     else:
                         vals = self._generic_step(batch, batch.shape[0], optimizer, world, max_grad_norm,
                                                   (step_lr if schedule is not None else None, step_lr * weight_decay, run.decayed),
-                                                  ema=run.generic_ema, **groups_kw)
+                                                  ema=run.generic_ema, model_input=run.model_input, **groups_kw)
                     readback.push(self.training_step, vals)
                     if not fused:            # this route has already read the loss (NaN check in front of backward(), as the reference)
                         nan_step = readback.flush()
@@ -1162,11 +1204,13 @@ class ContrastiveEstimationTrainer:
         graphed (use_graph's captured step), sync (GradAllReduce under data parallelism), generic_ema (the generic route's TorchEma),
         decayed (the parameters the generic route decays itself), device / world / clip and the step routes' caches: graph_steps
         ((B, L) -> GraphedStep), glob_neg (id(engine) -> GlobalNegatives), guarded (engines whose sticky NaN flag was cleared for this
-        run).  adamw, trust, ema: what _check_adamw, _check_trust and _check_ema return.  Loads and clears optimizer_state."""
+        run), model_input (batch -> what the model is called with: _model_input, which train() replaces by _masked_input under
+        grid_masking).  adamw, trust, ema: what _check_adamw, _check_trust and _check_ema return.  Loads and clears optimizer_state."""
         (weight_decay, decay_filter, schedule), (trust_ratio, trust_clip), (ema_decay, ema_warmup) = adamw, trust, ema
         fused = self._fused() or self._engine_difference() or self._engine_normalized()
         run = types.SimpleNamespace(fused=fused, graphed=False, sync=None, generic_ema=None, decayed=[], device=device, world=world,
-                                    clip=max_grad_norm is not None, graph_steps={}, glob_neg={}, guarded=set())
+                                    clip=max_grad_norm is not None, graph_steps={}, glob_neg={}, guarded=set(),
+                                    model_input=self._model_input)
         self.model._flatten_parameters(device)
         if fused:
             from .engine import FusedAdam, GradAllReduce
@@ -1244,7 +1288,7 @@ class ContrastiveEstimationTrainer:
                     ahead.submit(batch)
                 _, x_eng = ahead.take()
             else:
-                x_eng = self._model_input(batch)
+                x_eng = run.model_input(batch)
             eng = self.model.engine_for(x_eng)
             if ahead is not None and next_batch is not None:
                 # the engine runs it behind its encoder's forward pass, where its main queue turns latency-bound
@@ -1295,7 +1339,7 @@ class ContrastiveEstimationTrainer:
         return {"negatives": (int(self.num_negatives), int(self.negative_seed), int(self.training_step))}
 
     def _generic_step(self, batch, batch_size, optimizer, world, max_grad_norm=None, adamw=(None, 0.0, ()), negative_groups=None,
-                      ema=None):
+                      ema=None, model_input=None):
         """Any score function / optimizer: model forward and backward through the autograd bridge (HIP), the score function as the
         caller wrote it, the loss and its gradient through the loss kernels (_InfoNCE).  This route reads the loss every step, so
         the NaN guard sits where the reference has it: in front of backward() and optimizer.step() (:124-133).  With max_grad_norm,
@@ -1304,8 +1348,9 @@ class ContrastiveEstimationTrainer:
         adamw = (the step's learning rate under a schedule or None, lr * weight_decay of the step, the parameters that decay): every
         param group gets the rate, and the decay p <- p (1 - lr weight_decay) is applied right before optimizer.step().
         ema: None or the run's engine.TorchEma, updated right behind optimizer.step() with the number of the updates it has seen (the
-        early returns above it — a NaN loss, a gradient norm that is not finite — leave the average where it is)."""
-        predicted_z, targets, _, _ = self.model(self._model_input(batch))
+        early returns above it — a NaN loss, a gradient norm that is not finite — leave the average where it is).
+        model_input: None for _model_input, or the run's own (train() under grid_masking)."""
+        predicted_z, targets, _, _ = self.model((model_input or self._model_input)(batch))
         scores = self.score_function(predicted_z, targets)
         selection = None
         if negative_groups is not None:

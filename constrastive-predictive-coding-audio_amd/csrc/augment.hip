@@ -6,14 +6,12 @@
 // draws for its clips.  No atomics, no LDS beyond the four wave sums of the power pass, every sum in one fixed order.
 #include <cmath>
 #include "cpc_common.h"
+#include "cpc_draws.h"
 #include "cpc_kernels.h"
 #include "../../include/cpc_hip.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr u64 WA_DRAW = 0x632BE59BD9B4E019ull, WA_STEP = 0x9E3779B97F4A7C15ull, WA_IDX = 0xD1B54A32D192ED03ull;
 constexpr int WA_THREADS = 256;
 constexpr int WP_CHUNK = 4096;                        // samples per partial sum of the power pass: 256 threads x 4 pieces x 4 floats
 // Pieces of 4 outputs a lane of the apply pass writes, 1024 samples apart.  A lane's share of the per-clip draws (a dozen 64-bit
@@ -24,17 +22,6 @@ constexpr int WA_TILE = WA_THREADS * 4 * WA_ITERS;    // outputs per workgroup o
 constexpr int WA_NOISE_FIELD = 32;                    // per-sample hashes start behind the per-clip fields
 constexpr float WA_DB = 0.16609640474436813f;         // log2(10) / 20
 constexpr float WA_G = 2.642899791822139e-05f;        // sqrt(3) / 65536
-
-__host__ __device__ __forceinline__ u64 wa_mix(u64 z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ unsigned wa_field(u64 kb, unsigned f) { return (unsigned)(wa_mix(kb + WA_IDX * (u64)f) >> 32); }
-__device__ __forceinline__ int wa_int(unsigned u, int lo, int hi) { return lo + (int)(((u64)u * (u64)(hi - lo + 1)) >> 32); }
-__device__ __forceinline__ float wa_real(unsigned u, float lo, float hi) { return fmaf(hi - lo, (float)u * 0x1p-32f, lo); }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // partial[b][c] = sum of squares of x[b][4096 c .. min(4096 (c + 1), n)).  Thread t: one fma chain over the elements
 // 4 (256 p + t) + j (p outer, j inner; zeros behind n leave the chain's value as it is), the butterfly, the four waves.  VEC only
@@ -164,7 +151,7 @@ __global__ __launch_bounds__(WA_THREADS) void wave_augment_kernel(const float* _
     const int b = blockIdx.y, a = cfg.protect_from;
     const bool live = a > 0;
     WaveClip c;
-    c.kb = wa_mix(cfg.seed + WA_DRAW * cfg.step + WA_STEP * (cfg.clip_offset + (u64)b + 1ull));
+    c.kb = wa_key(cfg.seed, cfg.step, cfg.clip_offset, b);
     c.a = a;
     c.q = 65536;
     if (SPEED && live) c.q = wa_int(wa_field(c.kb, 1), cfg.q_lo, cfg.q_hi);

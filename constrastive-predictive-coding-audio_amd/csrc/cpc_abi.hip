@@ -923,6 +923,33 @@ int cpc_wave_augment(const float* x, float* y, const float* partial, float* para
     return launch_wave_augment(x, y, partial, params_out, B, L, ldx, ldy, cfg, (hipStream_t)stream);
 }
 
+int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
+
+int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {
+    if (!x || !partial || B < 1 || B > 65535 || (Cc != 1 && Cc != 2 && Cc != 4) || n < 1 || n % Cc != 0 || ldb < n) return CPC_EINVAL;
+    return launch_grid_sum(x, partial, B, n, ldb, Cc, (hipStream_t)stream);
+}
+
+int cpc_grid_mask(const float* x, float* y, const float* partial, int* spans_out, float* fill_out, int B, int W, int H, int Cc,
+                  long long ldbx, long long ldby, const CpcGridMask* cfg, void* stream) {
+    if (!x || !y || !cfg || B < 1 || B > 65535 || W < 1 || H < 1 || (Cc != 1 && Cc != 2 && Cc != 4)) return CPC_EINVAL;
+    const long long n = (long long)W * H * Cc;
+    if (n > 0x7FFFFFFFll || ldbx < n || ldby < n) return CPC_EINVAL;
+    if (cfg->protect_last < 0 || cfg->protect_last > W) return CPC_EINVAL;
+    if (cfg->freq_count < 0 || cfg->freq_count > 8 || cfg->time_count < 0 || cfg->time_count > 8 || cfg->freq_max < 0) return CPC_EINVAL;
+    if (cfg->time_cap < 0 || cfg->time_cap > W - cfg->protect_last) return CPC_EINVAL;
+    if (cfg->fill_mode < 0 || cfg->fill_mode > 2 || (cfg->fill_mode == 1 && !std::isfinite(cfg->fill_value))) return CPC_EINVAL;
+    if (cfg->fill_mode == 2 && !partial) return CPC_EINVAL;
+    if (x == y) {
+        if (ldbx != ldby) return CPC_EINVAL;
+    } else {          // the clip ranges of two different buffers must not meet
+        const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+        const uintptr_t xe = xa + 4 * (uintptr_t)((long long)(B - 1) * ldbx + n), ye = ya + 4 * (uintptr_t)((long long)(B - 1) * ldby + n);
+        if (xa < ye && ya < xe) return CPC_EINVAL;
+    }
+    return launch_grid_mask(x, y, partial, spans_out, fill_out, B, W, H, Cc, ldbx, ldby, cfg, (hipStream_t)stream);
+}
+
 int cpc_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
                       float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,
                       float delta_scaling, void* stream) {

@@ -231,6 +231,13 @@ int wave_power_chunks(int n);
 int launch_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, hipStream_t stream);
 int launch_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
                         const cpc_wave_augment_cfg* cfg, hipStream_t stream);
+// Grid masking (gridmask.hip): the per-chunk per-channel sums and the mask pass (copy form for x != y, the in-place form launched over the
+// mask rectangles for x == y); arguments checked by the entry points.
+struct cpc_grid_mask_cfg;
+int grid_sum_chunks(int n);
+int launch_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, hipStream_t stream);
+int launch_grid_mask(const float* x, float* y, const float* partial, int* spans_out, float* fill_out, int B, int W, int H, int Cc,
+                     long long ldbx, long long ldby, const cpc_grid_mask_cfg* cfg, hipStream_t stream);
 // Log-mel front end (mel.hip): power -> mel bands -> log -> optional delta channel; arguments checked by the entry point.
 int launch_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
                          float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,

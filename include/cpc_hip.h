@@ -71,6 +71,8 @@ extern "C" {
  *    receives a gradient at every hidden state (a lower layer of AudioGRUModel(num_layers > 1)).
  *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_mel_pointwise, the log-mel front end behind the
  *    framed DFT GEMM.
+ *    Added later under 9 (backward compatible, entry points added, none changed): masking augmentation on the input grid
+ *    cpc_grid_sum_chunks, cpc_grid_sum, cpc_grid_mask.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -1085,6 +1087,59 @@ int cpc_wave_augment(const float* x, float* y, const float* partial, float* para
 int cpc_mel_pointwise(const float* spec, long long lds, const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
                       float* out, int B, int Tn, int n_freq, int n_mels, int delta, int take_log, float log_offset, float scaling,
                       float delta_scaling, void* stream);
+
+
+/* Masking augmentation on the input grid of the scalogram engine (not in the reference; DESIGN.md, "Grid masking"; after SpecAugment,
+ * Park et al. 2019): frequency bands and time spans of every clip are filled with zero, a constant or the clip's own mean.
+ *   Grid: x is f32; clip b starts at x + b ldb, ldb >= W H Cc; element (t, h, c) of a clip (frame t < W, bin h < H, channel c < Cc) is at
+ *   (t H + h) Cc + c — the channels-last buffer the scalogram and the log-mel front end write.  Cc is 1, 2 or 4.
+ *   Wa = W - protect_last: frames t >= Wa are never changed.  With Wa == 0 nothing is drawn and cpc_grid_mask is the identity.
+ * Randomness: mix, kb = kb(seed, step, clip_offset + b), the integer draw and u_f are those of cpc_wave_augment above; the mask fields are
+ *   f = 0x4D41534B + j.  No field of the waveform augmentation (f < 32) and no noise index (32 + n, n < 2^24) reaches that value, so a
+ *   waveform augmentation and a mask with the same seed are independent.
+ *   frequency mask d < freq_count <= 8:  w_d in [0, min(freq_max, H)] from j = 2 d, f0_d in [0, H - w_d] from j = 2 d + 1; the cells
+ *             h in [f0_d, f0_d + w_d) of every frame t < Wa are masked.
+ *   time mask d < time_count <= 8:  w_d in [0, time_cap] from j = 16 + 2 d, t0_d in [0, Wa - w_d] from j = 17 + 2 d; all H Cc values of
+ *             the frames [t0_d, t0_d + w_d) are masked.  time_cap = min(time_max, floor(time_fraction Wa), Wa) is formed by the caller.
+ *   Masks may overlap.  A masked value of channel c becomes fill[c]: 0.0f (fill_mode 0), fill_value (1), or mean[b][c] (2), the mean of
+ *   channel c over all W H cells of the ORIGINAL clip: (sum over chunk of partial[b][chunk][c], in index order) / float(W H), formed in
+ *   the kernel from what cpc_grid_sum left.
+ * cpc_grid_sum: partial[b][k][c] (f32 [B][cpc_grid_sum_chunks(n)][Cc]) = the sum of channel c over the elements [4096 k,
+ *   min(4096 (k + 1), n)) of clip b, n = W H Cc, cpc_grid_sum_chunks(n) = ceil(n / 4096) (0 for n < 1).  Element e holds channel e % Cc,
+ *   and 4 % Cc == 0, so position j of every aligned piece of four holds channel j % Cc.  One workgroup per (b, k).  Thread t of 256:
+ *   a_j = the chain ((x[e_0j] + x[e_1j]) + x[e_2j]) + x[e_3j] over e_pj = 4096 k + 4 (256 p + t) + j, p = 0 .. 3 (elements at or behind n
+ *   count as 0), for j = 0 .. 3; then the positions of one channel: Cc = 4: s_c = a_c; Cc = 2: s_c = a_c + a_(c + 2); Cc = 1:
+ *   s_0 = (a_0 + a_1) + (a_2 + a_3); then an xor-shuffle butterfly over the wave (offsets 32, 16, .. 1) and (w0 + w1) + (w2 + w3) over
+ *   the four waves.  One fixed order whatever the alignment of the clips, no atomics.  A partial carries at most 3 + log2(4 / Cc) + 6 +
+ *   2 = 13 / 12 / 11 roundings (Cc = 1 / 2 / 4) along any path from an element to the result.
+ *   CPC_EINVAL: x or partial NULL, B outside [1, 65535], Cc not in {1, 2, 4}, n < 1 or not a multiple of Cc, ldb < n.
+ * cpc_grid_mask: one launch (after cpc_grid_sum(x, partial, B, W H Cc, ldbx, Cc) with fill_mode 2).
+ *   y != x: y receives the masked copy in one sweep, x is never written and elements that are not masked are copied bit for bit;
+ *     16-byte loads / stores where x / y and ldbx / ldby allow (16-byte aligned, a multiple of 4), scalar ones otherwise.
+ *   y == x (ldby == ldbx), in place: the kernel is LAUNCHED OVER THE MASK RECTANGLES (one grid row of workgroups per drawn mask and
+ *     clip, sized by the widest mask the configuration can draw; there is no sweep over the grid): only masked cells are written and
+ *     no grid element is read.  A run of masked elements is stored in the pieces of four elements that start at multiples of 4 from
+ *     the clip's start: 16-byte stores for pieces inside the run where y and ldby allow, scalar stores for the run's ends and otherwise.
+ *     With no mask to draw and spans_out == fill_out == NULL nothing is launched.
+ *   The bits are the same whichever loads and stores are used.
+ *   spans_out NULL or int32 [B][32]: eight (f0, w) pairs, then eight (t0, w) pairs, 0 where not drawn.  fill_out NULL or f32 [B][4]: the
+ *   fill value per channel as used (0 for c >= Cc).
+ *   CPC_EINVAL before any launch: x, y or cfg NULL, partial NULL with fill_mode 2, B outside [1, 65535], W or H < 1, Cc not in
+ *   {1, 2, 4}, W H Cc > 2^31 - 1, ldbx or ldby < W H Cc, protect_last outside [0, W], freq_count or time_count outside [0, 8],
+ *   freq_max < 0, time_cap outside [0, Wa], fill_mode outside {0, 1, 2}, fill_value not finite with fill_mode 1, x != y with
+ *   overlapping clip ranges [x, x + (B - 1) ldbx + W H Cc) and [y, ..), x == y with ldbx != ldby.
+ * The calls never throw, allocate or synchronise.  stream is a hipStream_t. */
+typedef struct cpc_grid_mask_cfg {
+    unsigned long long seed, step, clip_offset;
+    int protect_last;
+    int freq_count, freq_max;
+    int time_count, time_cap;
+    int fill_mode; float fill_value;
+} CpcGridMask;
+int cpc_grid_sum_chunks(int n);
+int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream);
+int cpc_grid_mask(const float* x, float* y, const float* partial, int* spans_out, float* fill_out, int B, int W, int H, int Cc,
+                  long long ldbx, long long ldby, const CpcGridMask* cfg, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,13 +5,20 @@ and a synthetic stand-in for AudioDataset that implements the protocol the train
 File I/O (torchaudio / mutagen decoding, reference :16-153) is outside the hot path and not rebuilt.
 The sampler draws from Python's ``random`` in the same call order as the reference, so a given seed (or a given
 global RNG state when seed is None) yields bit-identical index lists.
+
+DeviceAudioDataset is the route for recordings: the 16-bit PCM of every file is read once (the standard library's ``wave``; any other
+decoder hands in arrays) and kept concatenated in HBM, and a batch of overlapping windows is cut out of it by one launch of
+cpc_window_gather.  Its index semantics are the reference's AudioDataset / AudioTestingDataset (:77-127, :155-165, :191-199).
 """
 from __future__ import annotations
 
 import math
 import random
+import wave
+from pathlib import Path
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.utils.data
 
@@ -112,3 +119,204 @@ class TensorAudioDataset(SyntheticAudioDataset):
         self.counts = list(counts) if counts is not None else [data.shape[0]]
         self._item_length = data.shape[1]
         self.device_data = data.to(device) if device is not None else None
+
+
+def _read_wav(path, sampling_rate):
+    """Channel 0 of a 16-bit PCM file as int16 (the reference takes ``data[0, :]`` of what torchaudio decodes)."""
+    try:
+        with wave.open(str(path), "rb") as f:
+            width, rate, channels = f.getsampwidth(), f.getframerate(), f.getnchannels()
+            raw = f.readframes(f.getnframes()) if width == 2 and rate == sampling_rate else b""
+    except (wave.Error, EOFError) as err:
+        raise ValueError(f"{path}: not a PCM WAV file ({err})") from err
+    if width != 2:
+        raise ValueError(f"{path}: {8 * width}-bit samples; only 16-bit PCM is read (decode other formats yourself and pass arrays=)")
+    if rate != sampling_rate:
+        raise ValueError(f"{path}: sampling rate {rate}, the dataset's is {sampling_rate}; there is no resampling")
+    frames = np.frombuffer(raw, dtype="<i2")
+    frames = frames[:len(frames) - len(frames) % channels].reshape(-1, channels)
+    return np.ascontiguousarray(frames[:, 0]).astype(np.int16, copy=False)
+
+
+class DeviceAudioDataset(torch.utils.data.Dataset):
+    """Overlapping windows of ``item_length`` samples, ``unique_length`` apart, over the samples of all files, which are held once:
+    concatenated, as int16 or float32, in HBM (``device``) and / or on the host (``keep_host``, the default without a device).
+
+    Sources: ``location``, a directory searched recursively for ``.wav`` files (sorted; 16-bit PCM at ``sampling_rate``, channel 0;
+    anything else is a ValueError that names the file), or ``arrays``, one 1-D int16 or float32 numpy array or tensor per file.
+    ``storage="int16"`` needs int16 sources and converts in the gather (sample / 32768, exact in float32, what the reference's loader
+    returns); ``storage="float32"`` scales int16 sources once at load.
+
+    Indices as in the reference: example i lies at sample i * unique_length of the files laid end to end (``cross_files=False``: of
+    the files each shortened by item_length, so that the window stays in its file), its file is bisect_left(start_samples, sample) - 1,
+    at least 0: a sample that falls exactly on a later file's start belongs to the file in front of it.  One deviation:
+    with cross_files=False the window is always the item_length samples of that file from the position in it; the reference's
+    load_sample takes the file's length from the shortened start_samples there and can run on into the next file.
+
+    ``dataset[i]`` is the (item_length,) float32 clip, with ``labels=True`` the pair (clip, file index as a 0-d long tensor).
+    ``device_batch(indices)`` is the (B, item_length) float32 batch in HBM, cut by one cpc_window_gather launch; the trainer takes its
+    batches there, with no DataLoader.  A dataset without a device goes through the trainer's DataLoader route."""
+
+    def __init__(self, location=None, item_length=None, unique_length=None, sampling_rate=16000, max_file_count=None,
+                 cross_files=True, device=None, storage="int16", arrays=None, labels=False, keep_host=None):
+        super().__init__()
+        if (location is None) == (arrays is None):
+            raise ValueError("exactly one of location and arrays must be given")
+        if item_length is None or int(item_length) < 1:
+            raise ValueError("item_length must be a positive number of samples")
+        if storage not in ("int16", "float32"):
+            raise ValueError(f"storage must be 'int16' or 'float32', not {storage!r}")
+        self.sampling_rate = sampling_rate
+        self.cross_files = bool(cross_files)
+        self.labels = bool(labels)
+        self.storage = storage
+        self.device = torch.device(device) if device is not None else None
+        keep_host = self.device is None if keep_host is None else bool(keep_host)
+        if self.device is None and not keep_host:
+            raise ValueError("a dataset without a device needs its host copy (keep_host)")
+        if location is not None:
+            self.location = Path(location)
+            files = sorted(self.location.glob("**/*.wav"))
+            if max_file_count is not None:
+                files = files[:max_file_count]
+            self.files = [str(f) for f in files]
+            sources = [_read_wav(f, sampling_rate) for f in self.files]
+        else:
+            self.location, self.files = None, None
+            arrays = list(arrays)
+            if max_file_count is not None:
+                arrays = arrays[:max_file_count]
+            sources = [a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a) for a in arrays]
+        if not sources:
+            raise ValueError("no audio files" + (f" under {self.location}" if self.location is not None else ""))
+        for k, a in enumerate(sources):
+            name = self.files[k] if self.files is not None else f"arrays[{k}]"
+            if a.ndim != 1 or a.dtype not in (np.int16, np.float32):
+                raise ValueError(f"{name}: a file is a 1-D int16 or float32 array, not {a.dtype} with {a.ndim} dimensions")
+            if storage == "int16" and a.dtype != np.int16:
+                raise ValueError(f"{name}: storage='int16' needs int16 samples, not {a.dtype}")
+        self.max_file_count = len(sources)
+        self.file_lengths = [int(a.shape[0]) for a in sources]
+        if storage == "float32":
+            sources = [a.astype(np.float32) * np.float32(1.0 / 32768.0) if a.dtype == np.int16 else a for a in sources]
+        host = torch.from_numpy(np.concatenate(sources))
+        del sources
+        self._scale = 1.0 / 32768.0 if storage == "int16" else 1.0
+        self._store = host.to(self.device) if self.device is not None else None
+        self._host = host if keep_host else None
+        self._item_length = int(item_length)
+        self._unique_length = int(item_length if unique_length is None else unique_length)
+        self.calculate_length()
+
+    @classmethod
+    def from_arrays(cls, arrays, item_length, **kwargs):
+        return cls(arrays=arrays, item_length=item_length, **kwargs)
+
+    @property
+    def item_length(self):
+        return self._item_length
+
+    @item_length.setter
+    def item_length(self, value):
+        self._item_length = int(value)
+        self.calculate_length()
+
+    @property
+    def unique_length(self):
+        return self._unique_length
+
+    @unique_length.setter
+    def unique_length(self, value):
+        self._unique_length = int(value)
+        self.calculate_length()
+
+    def calculate_length(self):
+        """start_samples, the length and the per-example tables (first sample in the store, file), for the current item_length and
+        unique_length; the tables are built vectorised, checked once and uploaded once."""
+        item, unique = self._item_length, self._unique_length
+        if item < 1 or unique < 1:
+            raise ValueError("item_length and unique_length must be positive")
+        lengths = np.asarray(self.file_lengths, dtype=np.int64)
+        store_len = int(lengths.sum())
+        if self.cross_files:
+            counted = lengths
+        else:
+            short = [k for k, n in enumerate(self.file_lengths) if n < item]
+            if short:
+                name = self.files[short[0]] if self.files is not None else f"arrays[{short[0]}]"
+                raise ValueError(f"{name}: {self.file_lengths[short[0]]} samples, shorter than item_length = {item} (cross_files=False)")
+            counted = lengths - item
+        cum = np.concatenate([np.zeros(1, np.int64), np.cumsum(counted)])
+        self.start_samples = [int(v) for v in cum]
+        self._length = max(0, math.floor((self.start_samples[-1] - (item - unique)) / unique))
+        sample_index = np.arange(self._length, dtype=np.int64) * unique
+        file_of = np.maximum(np.searchsorted(cum, sample_index, side="left") - 1, 0)
+        first = np.concatenate([np.zeros(1, np.int64), np.cumsum(lengths)])          # the files as they lie in the store
+        starts = first[file_of] + (sample_index - cum[file_of])
+        if self._length and (int(file_of.max()) >= len(self.file_lengths) or int(starts.min()) < 0 or int(starts.max()) + item > store_len):
+            raise ValueError("window table out of range: a window would leave the stored samples")
+        self._store_len = store_len
+        self._starts = torch.from_numpy(starts)
+        self._file_of = torch.from_numpy(file_of.astype(np.int64))
+        if self.device is not None:
+            self._starts_dev = self._starts.to(self.device)
+            self._file_dev = self._file_of.to(self.device)
+
+    def __len__(self):
+        return self._length
+
+    def get_position(self, idx):
+        """(file index, position in the reference's start_samples numbering) of example idx."""
+        file_index = int(self._file_of[idx])
+        return file_index, idx * self._unique_length - self.start_samples[file_index]
+
+    def get_example_count_per_file(self):
+        unique = self._unique_length
+        counts = [math.ceil(self.start_samples[i] / unique) - math.ceil(self.start_samples[i - 1] / unique)
+                  for i in range(1, len(self.start_samples))]
+        total = sum(counts)
+        if total > self._length:
+            counts[-1] -= total - self._length
+        return counts
+
+    def __getitem__(self, idx):
+        idx = int(idx)
+        if not 0 <= idx < self._length:
+            raise IndexError(f"example {idx} of {self._length}")
+        if self._host is not None:
+            s = int(self._starts[idx])
+            clip = self._host[s:s + self._item_length]
+            clip = clip.to(torch.float32) * self._scale if clip.dtype == torch.int16 else clip.clone()
+        else:
+            clip = self._gather(torch.tensor([idx], dtype=torch.int64))[0][0].cpu()
+        return (clip, self._file_of[idx].clone()) if self.labels else clip
+
+    def _gather(self, idx):
+        """(batch, the indices on the device) for a checked int64 host tensor of example indices."""
+        from . import _hip
+        B, L = int(idx.numel()), self._item_length
+        with torch.cuda.device(self.device):
+            idx_dev = idx.to(self.device)
+            out = torch.empty((B, L), device=self.device, dtype=torch.float32)
+            _hip.call("cpc_window_gather", _hip.ptr(self._store), 1 if self.storage == "int16" else 0, self._store_len,
+                      _hip.ptr(self._starts_dev), self._length, _hip.ptr(idx_dev), _hip.ptr(out), B, L, L, self._scale)
+        return out, idx_dev
+
+    def device_batch(self, indices):
+        """The (B, item_length) float32 batch of the examples ``indices`` (a sequence or an int64 tensor; repeats allowed) in HBM: the
+        range check on the host, one small upload of the indices, one launch.  With labels=True: (batch, file indices on the device)."""
+        if self.device is None:
+            raise RuntimeError("device_batch needs a dataset built with device=")
+        idx = indices.detach().cpu() if isinstance(indices, torch.Tensor) else torch.as_tensor(list(indices))
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1:
+            raise ValueError("indices: a non-empty 1-D sequence of integers (an int64 tensor)")
+        if int(idx.min()) < 0 or int(idx.max()) >= self._length:
+            raise IndexError(f"example indices outside [0, {self._length})")
+        out, idx_dev = self._gather(idx.contiguous())
+        return (out, self._file_dev[idx_dev]) if self.labels else out
+
+    def hbm_bytes(self):
+        """Bytes this dataset holds in HBM: the samples and the two per-example tables."""
+        if self.device is None:
+            return 0
+        return sum(t.numel() * t.element_size() for t in (self._store, self._starts_dev, self._file_dev))

@@ -1033,9 +1033,11 @@ class ContrastiveEstimationTrainer:
 
     def _batches(self, dataset, sampler, device, num_workers, pin_memory, rank, world, with_indices=False):
         """Yields device batches (B, L).  A dataset exposing ``device_data`` (an (N, L) tensor already in HBM) is
-        indexed on the device; anything else goes through a torch DataLoader as in the reference (:87-91).
+        indexed on the device; one exposing ``device_batch`` with its samples in HBM (DeviceAudioDataset(device=...)) cuts each batch
+        there with one launch; anything else goes through a torch DataLoader as in the reference (:87-91).
         with_indices: yields (batch, the example indices of that batch — this rank's slice under data parallelism) instead."""
         resident = getattr(dataset, "device_data", None)
+        gather = getattr(dataset, "device_batch", None) if getattr(dataset, "device", None) is not None else None
         fifo = collections.deque() if with_indices else None
 
         def out(b):
@@ -1055,6 +1057,11 @@ class ContrastiveEstimationTrainer:
         if resident is not None:
             for idx in iter(source):
                 yield out(resident[torch.as_tensor(list(idx), device=resident.device)])
+            return
+        if gather is not None:
+            for idx in iter(source):
+                batch = gather(list(idx))
+                yield out(batch[0] if isinstance(batch, tuple) else batch)          # (a labels=True dataset hands out its labels too)
             return
         loader = torch.utils.data.DataLoader(dataset, batch_sampler=source, num_workers=num_workers, pin_memory=pin_memory)
         if torch.device(device).type != "cuda":
@@ -1468,12 +1475,17 @@ class ContrastiveEstimationTrainer:
         self.model.eval()
         task_data = torch.zeros(num_items, self.ar_size)
         task_labels = torch.zeros(num_items, dtype=torch.long)
-        loader = torch.utils.data.DataLoader(self.test_task_set, batch_size=batch_size, num_workers=num_workers)
+        test_set = self.test_task_set
+        if getattr(test_set, "device_batch", None) is not None and getattr(test_set, "device", None) is not None and test_set.labels:
+            # samples in HBM: the batches a DataLoader would collate, in its order, each cut on the device
+            loader = (test_set.device_batch(range(first, min(first + batch_size, num_items))) for first in range(0, num_items, batch_size))
+        else:
+            loader = torch.utils.data.DataLoader(test_set, batch_size=batch_size, num_workers=num_workers)
         with torch.no_grad():
             for step, (batch, labels) in enumerate(iter(loader)):
                 _, _, _, c = self.model(self._model_input(batch.to(device)))
                 task_data[step * batch_size:step * batch_size + c.shape[0], :] = c.cpu()
-                task_labels[step * batch_size:step * batch_size + c.shape[0]] = labels
+                task_labels[step * batch_size:step * batch_size + c.shape[0]] = labels.cpu()
         self.model.train()
         return task_data.numpy(), task_labels.numpy()
 

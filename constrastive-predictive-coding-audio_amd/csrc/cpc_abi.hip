@@ -923,6 +923,14 @@ int cpc_wave_augment(const float* x, float* y, const float* partial, float* para
     return launch_wave_augment(x, y, partial, params_out, B, L, ldx, ldy, cfg, (hipStream_t)stream);
 }
 
+int cpc_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
+                      const long long* idx, float* out, int B, int L, long long ldo, float scale, void* stream) {
+    if (!store || !starts || !idx || !out || !wave_shape_ok(B, L, ldo) || store_len < L || n_items < 1) return CPC_EINVAL;
+    if ((store_code != 0 && store_code != 1) || !std::isfinite(scale)) return CPC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(store) % (store_code == 1 ? 2 : 4) != 0 || reinterpret_cast<uintptr_t>(out) % 4 != 0) return CPC_EINVAL;
+    return launch_window_gather(store, store_code, store_len, starts, n_items, idx, out, B, L, ldo, scale, (hipStream_t)stream);
+}
+
 int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
 
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {

@@ -231,6 +231,9 @@ int wave_power_chunks(int n);
 int launch_wave_power(const float* x, float* partial, int B, int L, long long ldx, int n, hipStream_t stream);
 int launch_wave_augment(const float* x, float* y, const float* partial, float* params_out, int B, int L, long long ldx, long long ldy,
                         const cpc_wave_augment_cfg* cfg, hipStream_t stream);
+// Device-resident dataset (dataset.hip): a batch of windows cut from the concatenated samples; arguments checked by the entry point.
+int launch_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
+                         const long long* idx, float* out, int B, int L, long long ldo, float scale, hipStream_t stream);
 // Grid masking (gridmask.hip): the per-chunk per-channel sums and the mask pass (copy form for x != y, the in-place form launched over the
 // mask rectangles for x == y); arguments checked by the entry points.
 struct cpc_grid_mask_cfg;

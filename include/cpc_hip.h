@@ -73,6 +73,8 @@ extern "C" {
  *    framed DFT GEMM.
  *    Added later under 9 (backward compatible, entry points added, none changed): masking augmentation on the input grid
  *    cpc_grid_sum_chunks, cpc_grid_sum, cpc_grid_mask.
+ *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_window_gather, the batch of a device-resident
+ *    audio dataset.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -1140,6 +1142,27 @@ int cpc_grid_sum_chunks(int n);
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream);
 int cpc_grid_mask(const float* x, float* y, const float* partial, int* spans_out, float* fill_out, int B, int W, int H, int Cc,
                   long long ldbx, long long ldby, const CpcGridMask* cfg, void* stream);
+
+/* ---- Device-resident audio dataset: a batch of windows cut from the concatenated samples (csrc/dataset.hip; DESIGN.md,
+ * "Device-resident audio dataset").
+ * cpc_window_gather: out[b ldo + t] = scale * float(store[starts[idx[b]] + t]) for b < B, t < L, in one launch.
+ *   store: the samples of every file, one after the other, store_len of them; store_code 0: f32, 1: int16.
+ *   starts: int64 [n_items], the first sample of example i (a device table the dataset builds once).  idx: int64 [B], the example of
+ *   row b; an example may stand in several rows.  out: f32, rows ldo >= L apart; nothing is written between the rows or behind
+ *   the last one.
+ *   A f32 store with scale == 1.0f is copied bit for bit.  An int16 sample times scale = 1 / 32768 is exact in f32.
+ *   Guard: the kernel forms no address outside [store, store + store_len).  A row whose idx[b] is outside [0, n_items), or whose
+ *   window [starts[idx[b]], + L) is not inside [0, store_len], is written as L zeros; callers rule such rows out on the host, the
+ *   guard keeps a wrong index from becoming a fault.
+ *   Access: grid row b is output row b, a lane moves pieces of four consecutive samples; 16-byte stores where out is 16-byte aligned
+ *   and ldo a multiple of 4, scalar stores otherwise and for the last piece of a row whose L is no multiple of 4.  The source of a
+ *   piece is aligned to one sample only (the window starts anywhere).  The grid is sized from B L: workgroups of 4096, 1024 or 256
+ *   outputs, the largest that still gives 1024 workgroups.  The bits do not depend on any of this.
+ *   CPC_EINVAL before any launch: store, starts, idx or out NULL, B outside [1, 65535], L outside [1, 2^24], ldo < L, store_len < L,
+ *   n_items < 1, store_code outside {0, 1}, scale not finite, store not aligned to its element size, out not 4-byte aligned.
+ * The call never throws, allocates or synchronises.  stream is a hipStream_t. */
+int cpc_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
+                      const long long* idx, float* out, int B, int L, long long ldo, float scale, void* stream);
 
 #ifdef __cplusplus
 }

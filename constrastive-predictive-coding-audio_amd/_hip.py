@@ -185,6 +185,9 @@ _SIGNATURES = {
     "cpc_gru_gp_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_gp_bwd": ([_P, _P, _P, _P, _I, _I, _I, _P], _I),
     "cpc_gru_set_streaming": ([_I], _I),
+    "cpc_lstm_tape_elems": ([_I, _I, _I, _I], _L),
+    "cpc_lstm_fwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+    "cpc_lstm_bwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "cpc_nce_workspace_floats": ([_I, _I], _L),
     "cpc_nce_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P], _I),
     "cpc_nce_sampled_workspace_floats": ([_I, _I], _L),

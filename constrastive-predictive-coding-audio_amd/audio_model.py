@@ -1,4 +1,5 @@
-"""Drop-in model surface: AudioEncoder, AudioGRUModel, AudioPredictiveCodingModel (+ activation taps).
+"""Drop-in model surface: AudioEncoder, AudioGRUModel, AudioPredictiveCodingModel (+ activation taps), and AudioLSTMModel, an LSTM
+context network that is not in the reference.
 
 Same constructor arguments, attributes, state_dict keys and forward return values as the reference's
 ``audio_model.py`` (AudioEncoder :14-44, AudioGRUModel :47-77, AudioPredictiveCodingModel :164-219, ActivationWriter :274-284), but ``forward`` runs the hand-written HIP path (``engine.CPCEngine``) instead of ATen
@@ -124,6 +125,47 @@ class AudioGRUModel(nn.Module):
         return standalone_context_forward(self, input, self.hidden_size)
 
 
+class _LSTMCellParams(nn.Module):
+    """weight_ih / weight_hh / bias_ih / bias_hh with nn.LSTMCell's names, shapes (4 * hidden rows, gate order i, f, g, o) and
+    initialisation; no forward."""
+
+    def __init__(self, input_size, hidden_size, bias=True):
+        super().__init__()
+        self.input_size, self.hidden_size = input_size, hidden_size
+        self.weight_ih = nn.Parameter(torch.empty(4 * hidden_size, input_size))
+        self.weight_hh = nn.Parameter(torch.empty(4 * hidden_size, hidden_size))
+        if bias:
+            self.bias_ih = nn.Parameter(torch.empty(4 * hidden_size))
+            self.bias_hh = nn.Parameter(torch.empty(4 * hidden_size))
+        else:
+            self.register_parameter("bias_ih", None)
+            self.register_parameter("bias_hh", None)
+        stdv = 1.0 / math.sqrt(hidden_size) if hidden_size > 0 else 0
+        for w in self.parameters():
+            nn.init.uniform_(w, -stdv, stdv)
+
+
+class AudioLSTMModel(nn.Module):
+    """LSTM context network (not in the reference; the "modified CPC" of Riviere et al. 2020 replaces the GRU by an LSTM):
+    ``forward(input)`` takes (batch, input_size, steps) and returns the last hidden state h_V (batch, hidden_size) of an
+    ``nn.LSTMCell`` (held as ``lstmCell``: its parameter names, shapes and initialisation) stepped over the frames from zero states.
+    ``reset_hidden=False`` carries ``self.hidden = (h, cell)``, two (batch, hidden) float32 tensors, from one call into the next:
+    forward only, as for AudioGRUModel -- a call that starts from a carried pair cannot be differentiated."""
+
+    def __init__(self, input_size, hidden_size, bias=True, reset_hidden=True):
+        super().__init__()
+        self.input_size, self.hidden_size = input_size, hidden_size
+        self.lstmCell = _LSTMCellParams(input_size, hidden_size, bias)
+        self.hidden = None
+        self.reset_hidden = reset_hidden
+
+    def forward(self, input):
+        """(batch, input_size, steps) on the GPU -> last hidden state (batch, hidden_size), differentiable with respect to the
+        input and the parameters (stand-alone calls go through the autograd bridge _ContextForward)."""
+        from .contexts import standalone_context_forward
+        return standalone_context_forward(self, input, self.hidden_size)
+
+
 class ConvolutionalArBlock(nn.Module):
     """[MaxPool1d(pooling, ceil)] -> Conv1d -> [BatchNorm1d] -> ReLU (+ optional residual branch); parameter holder with the
     reference's module indices (audio_model.py:80-136), so ``main_modules.N.weight`` keys line up."""
@@ -213,8 +255,9 @@ class AudioPredictiveCodingModel(nn.Module):
         from .scalogram_model import ScalogramResidualEncoder
         self._scalogram = isinstance(encoder, ScalogramResidualEncoder)
         if not isinstance(encoder, (AudioEncoder, ScalogramResidualEncoder)) or \
-                not isinstance(autoregressive_model, (AudioGRUModel, ConvolutionalArModel, AttentionModel, ScalogramResidualEncoder)):
-            raise NotImplementedError("the HIP path covers AudioEncoder / ScalogramResidualEncoder + AudioGRUModel / "
+                not isinstance(autoregressive_model, (AudioGRUModel, AudioLSTMModel, ConvolutionalArModel, AttentionModel,
+                                                      ScalogramResidualEncoder)):
+            raise NotImplementedError("the HIP path covers AudioEncoder / ScalogramResidualEncoder + AudioGRUModel / AudioLSTMModel / "
                                       "ConvolutionalArModel / AttentionModel (SURVEY.md section 8 rows a1-a10)")
 
     @property

@@ -1,6 +1,6 @@
 """The context networks of the CPC train step, and what they may see of the engine that hosts them.
 
-A context network (``Context``: GRUContext for AudioGRUModel, ConvArContext / scalogram_engine.ConvArGridContext for
+A context network (``Context``: GRUContext for AudioGRUModel, LSTMContext for AudioLSTMModel, ConvArContext / scalogram_engine.ConvArGridContext for
 ConvolutionalArModel, AttentionContext for AttentionModel, scalogram_engine.ResNetArContext for a ScalogramResidualEncoder — the two
 of scalogram_engine share its GridContext base —, Float32Context around the first or the third) turns the frames z = rows [T-K-V, T-K) of the encoder's top buffer into c and, backward, dc into dz in the same rows of the top
 buffer's gradient plus its own parameter gradients.  It is built by make_context() for a ``ContextHost``: engine.CPCEngine and
@@ -399,6 +399,133 @@ class GRUContext(Context):
         _hip.call("cpc_reduce_slabs", _hip.ptr(sl, 4 * H), _hip.ptr(g_bh), 1, 2 * H, nb, 8 * H, 1, 1, 0, 0)
         _hip.call("cpc_reduce_slabs", _hip.ptr(sl, 7 * H), _hip.ptr(g_bh, 2 * H), 1, H, nb, 8 * H, 1, 1, 0, 0)
         _hip.gemm_nt(_hip.ptr(dA, 4 * H), _hip.ptr(lay.w_ih_t), _hip.ptr(self.gp_dz), M, E, 3 * H, 8 * H, 3 * H, E, code)
+
+
+class LSTMContext(Context):
+    """AudioLSTMModel as the context network (nn.LSTMCell stepped over the V frames; DESIGN.md "LSTM context"): one batched
+    input-projection GEMM for all V steps, the persistent LSTM kernels (csrc/lstm.hip) for the recurrence, GEMMs for the weight
+    gradients and for dz.  dG[b][t] = [di | df | dg | do] is the gradient of the input-projection term and of the recurrent term alike,
+    so every parameter gradient is one product over all 4H columns.  Single layer; no gradient penalty (``tangent`` / ``gp_grads`` keep
+    the base class's refusal)."""
+
+    ahead_ok = True       # prepare_weights is a pure function of the parameters (CPCEngine.prepare_ahead)
+    prefix = "autoregressive_model.lstmCell."
+
+    def __init__(self, eng, ar):
+        self.eng = eng
+        self.ar = ar
+        self.H = int(ar.hidden_size)
+        ch = 8 if eng.dt == torch.bfloat16 else 4
+        if ar.input_size != eng.E or self.H != eng.H:
+            raise ValueError("AudioLSTMModel sizes do not match enc_size / ar_size")
+        if self.H < 1 or self.H % (4 * ch) or self.H > 512:
+            raise NotImplementedError(f"HIP LSTM kernel: hidden size must be <= 512 and a multiple of 32 in bf16, of 16 in float32 "
+                                      f"(this engine: {'bf16' if ch == 8 else 'float32'}, hidden size {self.H})")
+        if eng.gp_capable:
+            raise NotImplementedError(self.GP_REASON)
+
+    GP_REASON = ("the gradient penalty through an AudioLSTMModel is not implemented: there is no tangent recurrence and no "
+                 "second-order reverse sweep for the LSTM kernels (AudioGRUModel, AttentionModel and ConvolutionalArModel have them)")
+
+    def allocate(self):
+        e = self.eng
+        B, V, H, In, dev, dt = e.B, e.V, self.H, e.E, e.device, e.dt
+        tape = max(1, int(_hip.lib().cpc_lstm_tape_elems(B, max(V, 1), H, e.code)))
+        self.w_ih = torch.empty(4 * H * In, device=dev, dtype=dt)          # [4H][In]
+        self.w_ih_t = torch.empty(In * 4 * H, device=dev, dtype=dt)        # [In][4H]
+        self.w_hh_frag = torch.empty(4 * H * H, device=dev, dtype=dt)
+        self.w_hh_t_frag = torch.empty(4 * H * H, device=dev, dtype=dt)
+        self.Gi = torch.empty(B * V * 4 * H, device=dev, dtype=dt)
+        self.Hall = torch.empty(B * (V + 1) * H, device=dev, dtype=dt)
+        self.tape = torch.zeros(tape, device=dev, dtype=dt)
+        self.dG = torch.empty(B * V * 4 * H, device=dev, dtype=dt)         # [di | df | dg | do] per (item, step)
+        self.cell = torch.empty(B, H, device=dev, dtype=torch.float32)     # last cell state
+        self.split_ih = e._pick_split(4 * H, In, B * V)
+        self.split_hh = e._pick_split(4 * H, H, B * V)
+        self.ev = torch.cuda.Event()
+        self.scratch = torch.empty(self.slab_floats(), device=dev, dtype=torch.float32)     # side-stream workspace
+
+    def slab_floats(self):
+        e, H = self.eng, self.H
+        return max(e.colsum_blocks * 4 * H, self.split_ih * 4 * H * e.E, self.split_hh * 4 * H * H)
+
+    def prepare_weights(self):
+        H, In, code = self.H, self.eng.E, self.eng.code
+        p = self.eng.model._param
+        w_ih, w_hh = p[self.prefix + "weight_ih"], p[self.prefix + "weight_hh"]
+        _hip.call("cpc_cast2d", _hip.ptr(w_ih), _hip.ptr(self.w_ih), 4 * H, In, In, 1, code)
+        _hip.call("cpc_cast2d", _hip.ptr(w_ih), _hip.ptr(self.w_ih_t), In, 4 * H, 1, In, code)
+        _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(self.w_hh_frag), 4 * H, H, H, 0, code)
+        _hip.call("cpc_prep_frag", _hip.ptr(w_hh), _hip.ptr(self.w_hh_t_frag), H, 4 * H, H, 1, code)
+
+    def _input(self):
+        """The frames [T-K-V, T-K) of the encoder's top buffer: (pointer, item stride in elements)."""
+        e = self.eng
+        return _hip.ptr(e.act[-1], (e.T - e.K - e.V) * e.E), e.geo.alloc[-1] * e.E
+
+    def forward(self):
+        e, H = self.eng, self.H
+        p, code, B, V, In = e.model._param, e.code, e.B, e.V, e.E
+        # reset_hidden=False: the last (h, cell) of the previous call is this call's initial pair
+        carry = not getattr(self.ar, "reset_hidden", True)
+        pair = self.ar.hidden if carry else None
+        if pair is not None:
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError("carried LSTM state must be a pair (h, cell) of (batch, hidden) tensors")
+            for s in pair:
+                if tuple(s.shape) != (B, H) or s.device != e.c.device:
+                    raise ValueError(f"carried LSTM state has shape {tuple(s.shape)} on {s.device}, this call needs {(B, H)} on {e.c.device}")
+            pair = tuple(s.detach().float().contiguous() for s in pair)
+        self.carried = pair is not None
+        x, x_item = self._input()
+        _hip.gemm_nt(x, _hip.ptr(self.w_ih), _hip.ptr(self.Gi), B * V, 4 * H, In, In, In, 4 * H, code,
+                     bias=_hip.ptr(p.get(self.prefix + "bias_ih")), a_rpi=V, a_item=x_item)
+        _hip.call("cpc_lstm_fwd", _hip.ptr(self.Gi), _hip.ptr(self.w_hh_frag), _hip.ptr(p.get(self.prefix + "bias_hh")),
+                  _hip.ptr(pair[0]) if pair else None, _hip.ptr(pair[1]) if pair else None, _hip.ptr(self.Hall), _hip.ptr(self.tape),
+                  _hip.ptr(e.c), _hip.ptr(self.cell), B, V, H, code)
+        self.ar.hidden = (e.c.detach().clone(), self.cell.clone()) if carry else None
+
+    def c_operand(self):
+        """(tensor, element offset, item stride): storage-dtype rows of c, one per item (h_V inside the hidden-state buffer)."""
+        return self.Hall, self.eng.V * self.H, (self.eng.V + 1) * self.H
+
+    def c_float(self):
+        return self.eng.c
+
+    def backward(self, dc):
+        e, H = self.eng, self.H
+        code, B, V, E, K = e.code, e.B, e.V, e.E, e.K
+        Ltop, t0, dtop = e.geo.alloc[-1], e.T - K - V, e.dact[-1]
+        if getattr(self, "carried", False):
+            raise RuntimeError("this LSTM call started from a pair (h, cell) carried over from the previous call (reset_hidden=False): it "
+                               "cannot be differentiated -- autograd could not either (the previous call's graph is gone after its "
+                               "backward()); use reset_hidden=False for inference / streaming, or set model.hidden = None before a train step")
+        if e._gp_phase:
+            raise NotImplementedError(self.GP_REASON)
+        _hip.call("cpc_lstm_bwd", _hip.ptr(dc), _hip.ptr(self.tape), _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
+        # the parameter gradients (short launches, off the critical path dG -> dz -> encoder backward) follow dG on the side stream
+        with e.side(self.ev):
+            self._params()
+        # dz -> rows [t0, t0+V) of the top-layer gradient
+        _hip.gemm_nt(_hip.ptr(self.dG), _hip.ptr(self.w_ih_t), _hip.ptr(dtop, t0 * E), B * V, E, 4 * H, 4 * H, 4 * H, E, code,
+                     c_rpi=V, c_item=Ltop * E, c_valid=V)
+
+    def _params(self):
+        """Parameter gradients from dG (all steps), the frames and the hidden states h_0 .. h_{V-1}, on the current stream."""
+        e, H = self.eng, self.H
+        g, code, B, V, In = e.model._grad, e.code, e.B, e.V, e.E
+        x, x_item = self._input()
+        sl = self.scratch
+        e._tn_to_grad(_hip.ptr(self.dG), x, g[self.prefix + "weight_ih"], B * V, 4 * H, In, 4 * H, In, self.split_ih,
+                      b_rpi=V, b_item=x_item, scratch=sl)
+        e._tn_to_grad(_hip.ptr(self.dG), _hip.ptr(self.Hall), g[self.prefix + "weight_hh"], B * V, 4 * H, H, 4 * H, H, self.split_hh,
+                      b_rpi=V, b_item=(V + 1) * H, scratch=sl)
+        if (self.prefix + "bias_ih") in g:
+            M = B * V
+            nb = min(e.colsum_blocks, max(1, M // 64))
+            _hip.call("cpc_colsum", _hip.ptr(self.dG), _hip.ptr(sl), M, 4 * H, 4 * H, nb, code)
+            _hip.call("cpc_reduce_slabs", _hip.ptr(sl), _hip.ptr(g[self.prefix + "bias_ih"]), 1, 4 * H, nb, 4 * H, 1, 1, 0, 0)
+            _hip.call("cpc_reduce_slabs", _hip.ptr(sl), _hip.ptr(g[self.prefix + "bias_hh"]), 1, 4 * H, nb, 4 * H, 1, 1, 0, 0)
 
 
 class ConvArContext(Context):
@@ -1014,12 +1141,14 @@ class Float32Context(Context):
 
 
 def make_context(eng, ar):
-    from .audio_model import AudioGRUModel, ConvolutionalArModel
+    from .audio_model import AudioGRUModel, AudioLSTMModel, ConvolutionalArModel
     from .attention_model import AttentionModel
     if eng.gp_capable and eng.dt != torch.float32 and isinstance(ar, (AudioGRUModel, AttentionModel)):
         return Float32Context(eng, GRUContext if isinstance(ar, AudioGRUModel) else AttentionContext, ar)
     if isinstance(ar, AudioGRUModel):
         return GRUContext(eng, ar)
+    if isinstance(ar, AudioLSTMModel):          # (never behind Float32Context: the LSTM has no gradient-penalty passes to run in float32)
+        return LSTMContext(eng, ar)
     if isinstance(ar, ConvolutionalArModel):
         # ConvArContext is the lean path for the reference's plain default (no pooling in the first block, pooling in every
         # later one, stride 1); every other configuration runs on the grid kernels

@@ -671,11 +671,14 @@ class ContrastiveEstimationTrainer:
             if score_function not in (linear_score_function, softplus_score_function) or optimizer is not torch.optim.Adam:
                 raise NotImplementedError("the gradient penalty on the HIP path covers linear_score_function / softplus_score_function "
                                           "+ Adam; see DESIGN.md section 8")
-            from .audio_model import AudioGRUModel
+            from .audio_model import AudioGRUModel, AudioLSTMModel
             ar = getattr(model, "autoregressive_model", None)
             if isinstance(ar, AudioGRUModel) and getattr(ar, "num_layers", 1) > 1:
                 from .contexts import GRUContext
                 raise NotImplementedError(GRUContext.GP_STACK_REASON)
+            if isinstance(ar, AudioLSTMModel):
+                from .contexts import LSTMContext
+                raise NotImplementedError(LSTMContext.GP_REASON)
             model.gradient_penalty_engine = True      # engines built from now on also give the gradient w.r.t. the scalogram
         if self.verbose:
             print("use score function", self.score_function)

@@ -676,6 +676,19 @@ int cpc_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA
     return launch_gru_gp_bwd(dc, tape, W, dA, B, V, H, (hipStream_t)stream);
 }
 
+long long cpc_lstm_tape_elems(int B, int V, int H, int dtype) { return lstm_tape_elems(B, V, H, dtype); }
+
+int cpc_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const float* h0, const float* c0, void* Hall, void* tape,
+                 float* h_out, float* cell_out, int B, int V, int H, int dtype, void* stream) {
+    if (!Gi || !Wfrag || !Hall || !tape || !h_out || !cell_out) return CPC_EINVAL;
+    return launch_lstm_fwd(Gi, Wfrag, bhh, h0, c0, Hall, tape, h_out, cell_out, B, V, H, dtype, (hipStream_t)stream);
+}
+
+int cpc_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype, void* stream) {
+    if (!dh_last || !tape || !WTfrag || !dG) return CPC_EINVAL;
+    return launch_lstm_bwd(dh_last, tape, WTfrag, dG, B, V, H, dtype, (hipStream_t)stream);
+}
+
 extern int g_gru_force_streaming;
 int cpc_gru_set_streaming(int on) {
     const int old = g_gru_force_streaming;

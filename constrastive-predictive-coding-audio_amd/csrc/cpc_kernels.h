@@ -143,6 +143,11 @@ int launch_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* 
 int launch_gru_gp_fwd(const float* Gi, const float* GiT, const float* WT, const float* bhh, float* tape, float* ct_out, int B,
                       int V, int H, hipStream_t stream);
 int launch_gru_gp_bwd(const float* dc, const float* tape, const float* W, float* dA, int B, int V, int H, hipStream_t stream);
+long long lstm_tape_elems(int B, int V, int H, int dtype);
+int launch_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const float* h0, const float* c0, void* Hall, void* tape,
+                    float* h_out, float* cell_out, int B, int V, int H, int dtype, hipStream_t stream);
+int launch_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
+                    hipStream_t stream);
 int launch_prep_frag(const float* src, void* dst, int R, int Kd, long long ld, int transpose, int dtype, hipStream_t stream);
 int launch_nce_lse_merge(const float* pm, const float* ps, int nparts, int ncols, int softplus, float nrows, float* lse, float* colp,
                          hipStream_t stream);

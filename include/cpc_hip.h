@@ -75,6 +75,8 @@ extern "C" {
  *    cpc_grid_sum_chunks, cpc_grid_sum, cpc_grid_mask.
  *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_window_gather, the batch of a device-resident
  *    audio dataset.
+ *    Added later under 9 (backward compatible, entry points added, none changed): the LSTM recurrence cpc_lstm_tape_elems, cpc_lstm_fwd,
+ *    cpc_lstm_bwd (AudioLSTMModel).
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -616,6 +618,31 @@ int cpc_gru_bwd(const float* dc, const void* tape, const void* WTfrag, void* dG,
  * a bad ld_h with dHs given.  (Added under ABI 9: no existing entry point changed.) */
 int cpc_gru_bwd_steps(const float* dc, const void* dHs, long long ld_h, const void* tape, const void* WTfrag, void* dG, int B, int V,
                       int H, int dtype, void* stream);
+
+/* AudioLSTMModel's recurrence (torch.nn.LSTMCell stepped over the V frames; not in the reference) as one persistent launch per
+ * direction.  Gate order i, f, g, o.  With a = Gi[:, t] + h_{t-1} W_hh^T + b_hh:
+ *   i = sigmoid(a_i), f = sigmoid(a_f), g = tanh(a_g), o = sigmoid(a_o), cell_t = f cell_{t-1} + i g, h_t = o tanh(cell_t).
+ * H: a multiple of 32 (bf16) or 16 (f32), at most 512 (weight-streaming kernels: 4 waves per workgroup up to H = 256, 8 above).
+ *   Gi       T   [B][V][4H]  = x_t W_ih^T + b_ih for all steps (cpc_gemm_nt)
+ *   Wfrag    T   cpc_prep_frag(weight_hh [4H][H], R = 4H, Kd = H);  bhh f32 [4H] or NULL (zeros)
+ *   h0, c0   f32 [B][H] initial hidden and cell state, each NULL = zeros (AudioLSTMModel(reset_hidden=False) carries the pair)
+ *   Hall     T   [B][V+1][H] hidden states, Hall[:,0] = h0 (rounded to T)
+ *   tape     T   cpc_lstm_tape_elems(B,V,H,dtype) elements, [B][V][6][H]: i, f, g, o, cell_{t-1}, tanh(cell_t), each rounded to T;
+ *                private to the fwd/bwd kernel pair
+ *   h_out, cell_out f32 [B][H] the last hidden and cell state (the f32 masters; h_out is what AudioLSTMModel.forward returns).
+ * The masters of h and cell are f32 for the whole sequence; what is rounded to T is the copy of h the matrix product reads, Hall
+ * and the tape.  A run of V steps therefore equals, bit for bit, the same data run in pieces with (h_out, cell_out) handed on as (h0, c0).
+ * cpc_lstm_bwd: dh_last f32 [B][H], the gradient at h_V -> dG T [B][V][4H] = [d a_i | d a_f | d a_g | d a_o], the gradient with respect
+ * to Gi and to h W_hh^T + b_hh alike.  WTfrag = cpc_prep_frag(weight_hh, R = H, Kd = 4H, ld = H, transpose = 1).  Per step, with
+ * tc = tanh(cell_t):  d a_o = dh tc o(1-o);  dct = dcell + dh o (1 - tc^2);  d a_i = dct g i(1-i);  d a_f = dct cell_{t-1} f(1-f);
+ * d a_g = dct i (1 - g^2);  dcell <- dct f;  dh <- dG[:, t] W_hh (from the values as rounded to T).
+ * Rows of items >= B are neither read nor written.  cpc_lstm_tape_elems returns CPC_EINVAL for arguments the kernels refuse.
+ * CPC_EINVAL before any launch: a NULL pointer other than bhh / h0 / c0, B < 1, V < 1, an H outside the rule above, a dtype other
+ * than f32 / bf16.  (Added under ABI 9: no existing entry point changed.) */
+long long cpc_lstm_tape_elems(int B, int V, int H, int dtype);
+int cpc_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const float* h0, const float* c0, void* Hall, void* tape,
+                 float* h_out, float* cell_out, int B, int V, int H, int dtype, void* stream);
+int cpc_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype, void* stream);
 
 /* The Wasserstein gradient penalty through AudioGRUModel (contrastive_estimation_training.py:144-158: loss.backward() through
  * torch.autograd.grad(..., create_graph=True), here for the GRUCell loop of audio_model.py:66-77).  f32 only, H <= 512.

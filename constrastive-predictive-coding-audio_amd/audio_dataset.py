@@ -9,6 +9,7 @@ global RNG state when seed is None) yields bit-identical index lists.
 DeviceAudioDataset is the route for recordings: the 16-bit PCM of every file is read once (the standard library's ``wave``; any other
 decoder hands in arrays) and kept concatenated in HBM, and a batch of overlapping windows is cut out of it by one launch of
 cpc_window_gather.  Its index semantics are the reference's AudioDataset / AudioTestingDataset (:77-127, :155-165, :191-199).
+With convert=True it takes PCM files of any rate, width and channel count and converts them on the device at load (resampling.py).
 """
 from __future__ import annotations
 
@@ -138,6 +139,36 @@ def _read_wav(path, sampling_rate):
     return np.ascontiguousarray(frames[:, 0]).astype(np.int16, copy=False)
 
 
+def _read_wav_frames(path):
+    """(frames [n, channels], rate) of a PCM WAV file of any rate, 8, 16, 24 or 32 bits and up to 8 channels, for convert=True: 16-bit
+    samples as int16, the other widths as float32 in [-1, 1) (8-bit WAV is unsigned, the wider ones are signed little-endian)."""
+    try:
+        with wave.open(str(path), "rb") as f:
+            width, rate, channels = f.getsampwidth(), f.getframerate(), f.getnchannels()
+            raw = f.readframes(f.getnframes()) if width in (1, 2, 3, 4) and 1 <= channels <= 8 else b""
+    except (wave.Error, EOFError) as err:
+        raise ValueError(f"{path}: not a PCM WAV file ({err})") from err
+    if width not in (1, 2, 3, 4):
+        raise ValueError(f"{path}: {8 * width}-bit samples; 8-, 16-, 24- and 32-bit PCM are read")
+    if not 1 <= channels <= 8:
+        raise ValueError(f"{path}: {channels} channels; up to 8 are read")
+    count = len(raw) // (width * channels) * channels
+    raw = raw[:count * width]
+    if width == 2:
+        samples = np.frombuffer(raw, dtype="<i2").astype(np.int16, copy=False)
+    elif width == 1:
+        samples = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - np.float32(128.0)) * np.float32(1.0 / 128.0)
+    elif width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        value = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        value -= (value & 0x800000) << 1
+        samples = value.astype(np.float32) * np.float32(1.0 / 8388608.0)          # 24 bits are exact in float32
+    else:
+        samples = (np.frombuffer(raw, dtype="<i4").astype(np.float64) * (1.0 / 2147483648.0)).astype(np.float32)
+        samples = np.minimum(samples, np.float32(1.0 - 2.0 ** -24))                # the rounding of 2^31 - 1 must not reach 1.0
+    return np.ascontiguousarray(samples.reshape(-1, channels)), int(rate)
+
+
 class DeviceAudioDataset(torch.utils.data.Dataset):
     """Overlapping windows of ``item_length`` samples, ``unique_length`` apart, over the samples of all files, which are held once:
     concatenated, as int16 or float32, in HBM (``device``) and / or on the host (``keep_host``, the default without a device).
@@ -153,12 +184,22 @@ class DeviceAudioDataset(torch.utils.data.Dataset):
     with cross_files=False the window is always the item_length samples of that file from the position in it; the reference's
     load_sample takes the file's length from the shortened start_samples there and can run on into the next file.
 
+    ``convert=True`` (opt-in; every default above stays) takes files as they come: WAV of 8-, 16-, 24- or 32-bit PCM, up to 8 channels,
+    any sampling rate; arrays ``(frames,)`` or ``(frames, channels)`` at ``array_rates`` (one number or one per array).  16-bit sources
+    are uploaded as they are, interleaved, the other widths as float32 in [-1, 1); the files of one (rate, channels, sample type) are
+    downmixed (``channels="first"`` or ``"mean"``), resampled to ``sampling_rate`` and stored as ``storage`` by cpc_resample
+    (resampling.py) in chunks of at most ``convert_chunk_bytes`` of source, so that peak HBM is the store plus one chunk.
+    ``file_lengths`` are then the converted lengths, ceil(frames new / orig), and everything behind the store is as without it; a host
+    copy is read back from the store.  Without a device only width and channel conversion run (numpy); a file at another rate is a
+    ValueError, because resampling runs on the device.  IEEE-float WAV and other containers: a ValueError that names the file.
+
     ``dataset[i]`` is the (item_length,) float32 clip, with ``labels=True`` the pair (clip, file index as a 0-d long tensor).
     ``device_batch(indices)`` is the (B, item_length) float32 batch in HBM, cut by one cpc_window_gather launch; the trainer takes its
     batches there, with no DataLoader.  A dataset without a device goes through the trainer's DataLoader route."""
 
     def __init__(self, location=None, item_length=None, unique_length=None, sampling_rate=16000, max_file_count=None,
-                 cross_files=True, device=None, storage="int16", arrays=None, labels=False, keep_host=None):
+                 cross_files=True, device=None, storage="int16", arrays=None, labels=False, keep_host=None, convert=False,
+                 channels="first", array_rates=None, convert_chunk_bytes=256 << 20):
         super().__init__()
         if (location is None) == (arrays is None):
             raise ValueError("exactly one of location and arrays must be given")
@@ -166,6 +207,14 @@ class DeviceAudioDataset(torch.utils.data.Dataset):
             raise ValueError("item_length must be a positive number of samples")
         if storage not in ("int16", "float32"):
             raise ValueError(f"storage must be 'int16' or 'float32', not {storage!r}")
+        if channels not in ("first", "mean"):
+            raise ValueError(f"channels must be 'first' or 'mean', not {channels!r}")
+        if not convert and (channels != "first" or array_rates is not None):
+            raise ValueError("channels='mean' and array_rates need convert=True")
+        if int(convert_chunk_bytes) < 1:
+            raise ValueError("convert_chunk_bytes must be positive")
+        self.convert = bool(convert)
+        self.channels = channels
         self.sampling_rate = sampling_rate
         self.cross_files = bool(cross_files)
         self.labels = bool(labels)
@@ -180,15 +229,34 @@ class DeviceAudioDataset(torch.utils.data.Dataset):
             if max_file_count is not None:
                 files = files[:max_file_count]
             self.files = [str(f) for f in files]
-            sources = [_read_wav(f, sampling_rate) for f in self.files]
+            if convert:
+                read = [_read_wav_frames(f) for f in self.files]
+                sources, rates = [a for a, _ in read], [r for _, r in read]
+            else:
+                sources = [_read_wav(f, sampling_rate) for f in self.files]
         else:
             self.location, self.files = None, None
             arrays = list(arrays)
+            if array_rates is None or np.isscalar(array_rates):
+                rates = [int(sampling_rate if array_rates is None else array_rates)] * len(arrays)
+            else:
+                rates = [int(r) for r in array_rates]
+                if len(rates) != len(arrays):
+                    raise ValueError(f"array_rates has {len(rates)} entries for {len(arrays)} arrays")
             if max_file_count is not None:
-                arrays = arrays[:max_file_count]
+                arrays, rates = arrays[:max_file_count], rates[:max_file_count]
             sources = [a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a) for a in arrays]
         if not sources:
             raise ValueError("no audio files" + (f" under {self.location}" if self.location is not None else ""))
+        self._item_length = int(item_length)
+        self._unique_length = int(item_length if unique_length is None else unique_length)
+        self._scale = 1.0 / 32768.0 if storage == "int16" else 1.0
+        if convert:
+            host = self._load_converted(sources, rates, int(convert_chunk_bytes), keep_host)
+            del sources
+            self._host = host if keep_host else None
+            self.calculate_length()
+            return
         for k, a in enumerate(sources):
             name = self.files[k] if self.files is not None else f"arrays[{k}]"
             if a.ndim != 1 or a.dtype not in (np.int16, np.float32):
@@ -201,12 +269,91 @@ class DeviceAudioDataset(torch.utils.data.Dataset):
             sources = [a.astype(np.float32) * np.float32(1.0 / 32768.0) if a.dtype == np.int16 else a for a in sources]
         host = torch.from_numpy(np.concatenate(sources))
         del sources
-        self._scale = 1.0 / 32768.0 if storage == "int16" else 1.0
         self._store = host.to(self.device) if self.device is not None else None
         self._host = host if keep_host else None
-        self._item_length = int(item_length)
-        self._unique_length = int(item_length if unique_length is None else unique_length)
         self.calculate_length()
+
+    def _load_converted(self, sources, rates, chunk_bytes, keep_host):
+        """convert=True: sets file_lengths and the store from sources of any rate, channel count and sample type, and returns the host
+        copy (None where none is asked for).  With a device, the files of one (rate, channels, sample type) go through cpc_resample in
+        chunks of at most chunk_bytes of source (a longer file goes alone), each straight into its place in the store; without one,
+        width and channel conversion run in numpy and a file at another rate is refused."""
+        from . import resampling
+        name = lambda k: self.files[k] if self.files is not None else f"arrays[{k}]"
+        for k, a in enumerate(sources):
+            if a.ndim == 1:
+                sources[k] = a = a.reshape(-1, 1)
+            if a.ndim != 2 or not 1 <= a.shape[1] <= 8 or a.dtype not in (np.int16, np.float32):
+                raise ValueError(f"{name(k)}: a file is an int16 or float32 array (frames,) or (frames, channels <= 8), not {a.dtype} "
+                                 f"with shape {a.shape}")
+            if rates[k] < 1:
+                raise ValueError(f"{name(k)}: sampling rate {rates[k]}")
+        self.max_file_count = len(sources)
+        to_int16 = self.storage == "int16"
+        mix = resampling.MIX_MEAN if self.channels == "mean" else resampling.MIX_FIRST
+
+        def scales(dtype):          # (in_scale, out_scale): int16 sources count in units of 1 / 32768, float sources in units of 1
+            if dtype == np.int16:
+                return (1.0, 1.0) if to_int16 else (1.0 / 32768.0, 1.0)
+            return (1.0, 32768.0) if to_int16 else (1.0, 1.0)
+
+        self.convert_launches = 0          # cpc_resample launches this load made
+        if self.device is None:
+            converted = []
+            for k, a in enumerate(sources):
+                if rates[k] != self.sampling_rate:
+                    raise ValueError(f"{name(k)}: sampling rate {rates[k]}, the dataset's is {self.sampling_rate}; resampling runs on "
+                                     f"the device (pass device=)")
+                x = a[:, 0].astype(np.float32)
+                if mix == resampling.MIX_MEAN:
+                    for c in range(1, a.shape[1]):
+                        x = x + a[:, c].astype(np.float32)
+                    x = x / np.float32(a.shape[1])
+                in_scale, out_scale = scales(a.dtype)
+                x = (x * np.float32(in_scale)) * np.float32(out_scale)
+                converted.append(np.rint(np.clip(x, -32768.0, 32767.0)).astype(np.int16) if to_int16 else x)
+            self.file_lengths = [int(x.shape[0]) for x in converted]
+            self._store = None
+            return torch.from_numpy(np.concatenate(converted))
+
+        plans, groups = {}, {}
+        self.file_lengths = []
+        for k, a in enumerate(sources):
+            if rates[k] not in plans:
+                try:
+                    plans[rates[k]] = resampling.plan_for(rates[k], self.sampling_rate)
+                except ValueError as err:
+                    raise ValueError(f"{name(k)}: {err}") from err
+            self.file_lengths.append(plans[rates[k]].output_length(a.shape[0]))
+            groups.setdefault((rates[k], a.shape[1], a.dtype.str), []).append(k)
+        first = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.asarray(self.file_lengths, dtype=np.int64))])
+        store = torch.empty(int(first[-1]), dtype=torch.int16 if to_int16 else torch.float32, device=self.device)
+
+        def flush(members):
+            frames = np.asarray([sources[k].shape[0] for k in members], dtype=np.int64)
+            begin = np.concatenate([np.zeros(1, np.int64), np.cumsum(frames)[:-1]])
+            out = np.asarray([self.file_lengths[k] for k in members], dtype=np.int64)
+            keep = out > 0
+            if not keep.any():
+                return
+            a0 = sources[members[0]]
+            in_scale, out_scale = scales(a0.dtype)
+            chunk = torch.from_numpy(np.concatenate([sources[k] for k in members])).to(self.device)
+            segments = np.stack([begin, frames, first[np.asarray(members)], out], axis=1)[keep]
+            resampling.convert_segments(chunk, a0.shape[1], mix, plans[rates[members[0]]], segments, store, in_scale, out_scale)
+            self.convert_launches += 1
+
+        for members in groups.values():
+            chunk, size = [], 0
+            for k in members:
+                if chunk and size + sources[k].nbytes > chunk_bytes:
+                    flush(chunk)
+                    chunk, size = [], 0
+                chunk.append(k)
+                size += sources[k].nbytes
+            flush(chunk)
+        self._store = store
+        return store.cpu() if keep_host else None
 
     @classmethod
     def from_arrays(cls, arrays, item_length, **kwargs):

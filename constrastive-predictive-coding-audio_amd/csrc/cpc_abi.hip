@@ -944,6 +944,25 @@ int cpc_window_gather(const void* store, int store_code, long long store_len, co
     return launch_window_gather(store, store_code, store_len, starts, n_items, idx, out, B, L, ldo, scale, (hipStream_t)stream);
 }
 
+int cpc_resample(const void* src, int src_code, long long src_frames_total, int C, int mix, float in_scale, const float* taps, int L,
+                 int M, int W, const long long* segs, const long long* tile_first, int nseg, long long ntiles, void* dst, int dst_code,
+                 long long dst_total, float out_scale, void* stream) {
+    if (!src || !taps || !segs || !tile_first || !dst || C < 1 || C > 8) return CPC_EINVAL;
+    if ((mix != 0 && mix != 1) || (src_code != 0 && src_code != 1) || (dst_code != 0 && dst_code != 1)) return CPC_EINVAL;
+    if (L < 1 || L > (1 << 20) || M < 1 || M > (1 << 20) || W < 0 || W > (1 << 20)) return CPC_EINVAL;
+    if ((long long)L * (2ll * W + 1) > (1ll << 24) || resample_span_floats(L, M, W) > 16384) return CPC_EINVAL;
+    if (nseg < 1 || ntiles < 1 || ntiles > (1ll << 23)) return CPC_EINVAL;
+    if (src_frames_total < 1 || src_frames_total > (1ll << 40) || dst_total < 1 || dst_total > (1ll << 40)) return CPC_EINVAL;
+    if (!std::isfinite(in_scale) || !std::isfinite(out_scale)) return CPC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(src) % (src_code == 1 ? 2 : 4) != 0 || reinterpret_cast<uintptr_t>(dst) % (dst_code == 1 ? 2 : 4) != 0)
+        return CPC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(taps) % 4 != 0 || reinterpret_cast<uintptr_t>(segs) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(tile_first) % 8 != 0)
+        return CPC_EINVAL;
+    return launch_resample(src, src_code, src_frames_total, C, mix, in_scale, taps, L, M, W, segs, tile_first, nseg, ntiles, dst, dst_code,
+                           dst_total, out_scale, (hipStream_t)stream);
+}
+
 int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
 
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {

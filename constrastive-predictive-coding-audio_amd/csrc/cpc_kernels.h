@@ -239,6 +239,12 @@ int launch_wave_augment(const float* x, float* y, const float* partial, float* p
 // Device-resident dataset (dataset.hip): a batch of windows cut from the concatenated samples; arguments checked by the entry point.
 int launch_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
                          const long long* idx, float* out, int B, int L, long long ldo, float scale, hipStream_t stream);
+// Load-time conversion (resample.hip): downmix, polyphase resampling and the store for a list of segments; arguments checked by the
+// entry point.  resample_span_floats: the LDS floats a tile's input span can need.
+long long resample_span_floats(int L, int M, int W);
+int launch_resample(const void* src, int src_code, long long src_frames_total, int C, int mix, float in_scale, const float* taps, int L,
+                    int M, int W, const long long* segs, const long long* tile_first, int nseg, long long ntiles, void* dst, int dst_code,
+                    long long dst_total, float out_scale, hipStream_t stream);
 // Grid masking (gridmask.hip): the per-chunk per-channel sums and the mask pass (copy form for x != y, the in-place form launched over the
 // mask rectangles for x == y); arguments checked by the entry points.
 struct cpc_grid_mask_cfg;

@@ -77,6 +77,8 @@ extern "C" {
  *    audio dataset.
  *    Added later under 9 (backward compatible, entry points added, none changed): the LSTM recurrence cpc_lstm_tape_elems, cpc_lstm_fwd,
  *    cpc_lstm_bwd (AudioLSTMModel).
+ *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_resample, downmix and rational resampling of
+ *    audio files when a device-resident dataset is loaded.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -1190,6 +1192,39 @@ int cpc_grid_mask(const float* x, float* y, const float* partial, int* spans_out
  * The call never throws, allocates or synchronises.  stream is a hipStream_t. */
 int cpc_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
                       const long long* idx, float* out, int B, int L, long long ldo, float scale, void* stream);
+
+/* ---- Load-time conversion: channel downmix, rational resampling and the f32 / int16 store for a list of segments (files) in one
+ * launch (csrc/resample.hip; DESIGN.md, "Resampling and downmix at load").
+ * cpc_resample: for every segment s with N = segs[4 s + 1] source frames and every n < segs[4 s + 3],
+ *     x[i]  = in_scale * (mix == 0 ? f[i][0] : (f[i][0] + ... + f[i][C - 1]) / C)   for 0 <= i < N, 0 otherwise
+ *     y[n]  = sum_{t = 0 .. 2 W} taps[t L + p] * x[i0 + t - W],   i0 = (n M) div L,  p = (n M) mod L
+ *     dst[segs[4 s + 2] + n] = out_scale * y[n]
+ *   where f[i][c] = src[(segs[4 s] + i) C + c].  The channel sum runs in channel order in f32; the sum over t runs in t order in f32.
+ *   Frames outside [0, N) of the segment count as zero: no sample of a neighbouring segment enters.
+ *   src: interleaved frames of C channels, src_frames_total of them, the segments back to back or apart; src_code 0: f32, 1: int16.
+ *   dst: dst_total elements; dst_code 0: f32, 1: int16.  The int16 store writes the same f32 value out_scale * y[n], rounded half to
+ *   even and saturated to [-32768, 32767]; both stores form that value by the same operations.
+ *   taps: f32 [2 W + 1][L], the TRANSPOSE of the L x (2 W + 1) polyphase table the caller designs (taps[t L + p] is the table's
+ *   [p][t]); the kernel knows nothing of windows or cut-offs.  W = 0, L = M = 1, taps = {1} is the identity: downmix and convert only.
+ *   segs: int64 [nseg][4] on the device: first source frame, source frames, first output, output count (ceil(N L / M) for a whole
+ *   file; any count is served, outputs whose taps lie behind the segment read zeros).  tile_first: int64 [nseg] on the device, the
+ *   first tile of segment s when every segment is cut into tiles of CPC_RESAMPLE_TILE outputs, tile_first[0] = 0, non-decreasing;
+ *   ntiles: their total, the grid.  A workgroup finds its segment by a uniform search in tile_first.
+ *   Guard: the kernel forms no address outside [src, src + src_frames_total C) or [dst, dst + dst_total).  A segment whose entries
+ *   leave [0, src_frames_total] or [0, dst_total], or are negative, is skipped: nothing of it is read or written; a tile that a wrong
+ *   tile_first places outside its segment is skipped too.  Callers build right tables; the guard keeps a wrong one from becoming a
+ *   fault.
+ *   Access: a workgroup of 256 lanes stages the downmixed span of its tile, at most (CPC_RESAMPLE_TILE - 1) M div L + 2 W + 2 floats,
+ *   in LDS once; a lane makes four outputs 256 apart; stores are one element per lane, consecutive lanes consecutive outputs.
+ *   CPC_EINVAL before any launch: src, taps, segs, tile_first or dst NULL, C outside [1, 8], mix, src_code or dst_code outside {0, 1},
+ *   L or M outside [1, 2^20], W < 0, L (2 W + 1) > 2^24, the span above > 16384 floats (64 KiB of LDS), nseg < 1, ntiles outside
+ *   [1, 2^23], src_frames_total or dst_total outside [1, 2^40], in_scale or out_scale not finite, src or dst not aligned to its
+ *   element size, taps not 4-byte aligned, segs or tile_first not 8-byte aligned.
+ * The call never throws, allocates or synchronises.  stream is a hipStream_t. */
+#define CPC_RESAMPLE_TILE 1024
+int cpc_resample(const void* src, int src_code, long long src_frames_total, int C, int mix, float in_scale, const float* taps, int L,
+                 int M, int W, const long long* segs, const long long* tile_first, int nseg, long long ntiles, void* dst, int dst_code,
+                 long long dst_total, float out_scale, void* stream);
 
 #ifdef __cplusplus
 }

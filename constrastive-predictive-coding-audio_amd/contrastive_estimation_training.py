@@ -470,13 +470,17 @@ class _StepReadback:
 
 class _NanRollback:
     """The host learns of a NaN loss host_sync_lag steps late; the steps launched meanwhile change nothing on the device that Adam
-    owns (their updates are skipped there), but their forward passes move the BatchNorm running statistics, and the host-side
-    step count advances.  Both are put back to where the reference leaves them (it returns inside the NaN step, after that step's
-    forward pass, :124-133): the buffers are snapshotted at the START of every step (one multi-tensor copy) and the snapshot of
-    step `nan + 1` is restored.  What cannot be taken back: the sampler has handed out the later batches.  The generic route reads
-    every step's loss at once and snapshots nothing."""
+    owns (every stateful launch — the update, the average, the trust table, the learnable temperature's step — is skipped there
+    under the sticky flag; DESIGN.md, "What the NaN guard holds still"), but their forward passes move the BatchNorm running
+    statistics, a scheduled temperature's tick overwrites its device value, and the host-side counts advance.  All of that is put
+    back to where the reference leaves it (it returns inside the NaN step, after that step's forward pass, :124-133): at the START
+    of every step the buffers are snapshotted (one multi-tensor copy per dtype), a scheduled DeviceTemperature's tstate is copied
+    (8 floats), and the host values are noted — the optimizer's t and lr, the trainer's last_lr, the temperature's step.  restore()
+    takes the statistics of step `nan + 1` and everything else of step `nan`.  What cannot be taken back: the sampler has handed out
+    the later batches; the negative bank is emptied instead (_nan_return).  The generic route reads every step's loss at once, before
+    anything is updated: it snapshots no buffer and notes only last_lr, which train() has already set to the NaN step's rate."""
 
-    def __init__(self, trainer, optimizer, fused):
+    def __init__(self, trainer, optimizer, fused, device_temp=None):
         self.trainer, self.optimizer, self.fused = trainer, optimizer, fused
         # (grouped by dtype, copied one dtype at a time: a mixed list — float32 statistics and int64 counters — takes _foreach_copy_'s
         # per-tensor route, 40 device-to-device copies and 0.13 ms per configs[2] step; a uniform list is one multi-tensor kernel)
@@ -488,6 +492,10 @@ class _NanRollback:
         self.ring, self.ring_pos, self.snaps = [], 0, {}          # snaps: step -> (ring slot or None, the optimizer's t)
         if fused and self.bufs:          # the ring exists before the loop: no allocation inside the hot loop; models without BatchNorm keep none
             self.ring = [self._slot() for _ in range(_ring_depth(trainer))]
+        # host: step -> what else the host held at the start of that step; temp_ring: tstate copies of a scheduled temperature (its
+        # tick is no update: it is not skipped under the flag, so the steps behind a NaN loss leave their own values there)
+        self.temp, self.host = device_temp, {}
+        self.temp_ring, self.temp_pos = [], 0
 
     def _slot(self):
         return [[torch.empty_like(b) for b in group] for group in self.bufs]
@@ -498,9 +506,10 @@ class _NanRollback:
             torch._foreach_copy_(d, s)
 
     def snapshot(self, step):
-        if not self.fused:
-            return
         depth = _ring_depth(self.trainer)
+        if not self.fused:          # nothing runs behind a NaN step there; last_lr is still the rate of a step that was not applied
+            self.host = {step: {"lr": None, "last_lr": getattr(self.trainer, "last_lr", None), "temp_step": None, "tstate": None}}
+            return
         dst = None
         if self.bufs:
             while len(self.ring) < depth:          # (host_sync_interval / host_sync_lag raised while training)
@@ -509,17 +518,39 @@ class _NanRollback:
             self.ring_pos += 1
             self._copy(dst, self.bufs)
         self.snaps[step] = (dst, getattr(self.optimizer, "t", None))
+        temp, tslot = self.temp, None
+        if temp is not None and temp.mode == "scheduled":
+            while len(self.temp_ring) < depth:
+                self.temp_ring.append(torch.empty_like(temp.tstate))
+            tslot = self.temp_ring[self.temp_pos % depth]
+            self.temp_pos += 1
+            tslot.copy_(temp.tstate)
+        self.host[step] = {"lr": getattr(self.optimizer, "lr", None), "last_lr": getattr(self.trainer, "last_lr", None),
+                           "temp_step": None if temp is None else temp.step, "tstate": tslot}
         for old_step in [k for k in self.snaps if k < step - depth + 1]:
             del self.snaps[old_step]
+            self.host.pop(old_step, None)
 
     def restore(self, step):
-        """After a NaN loss at ``step``: the statistics of the start of step + 1, the optimizer's count of the start of ``step``."""
+        """After a NaN loss at ``step``: the statistics of the start of step + 1; the optimizer's count and rate, the trainer's
+        last_lr and the temperature's step (a scheduled one's device value too) of the start of ``step``."""
         later = self.snaps.get(step + 1)
         if later is not None and later[0] is not None:          # statistics as they were after the NaN step's own forward pass
             self._copy(self.bufs, later[0])
         here = self.snaps.get(step)
         if here is not None and here[1] is not None and hasattr(self.optimizer, "t"):
             self.optimizer.t = here[1]                          # no update has happened since the start of the NaN step
+        host = self.host.get(step)
+        if host is None:
+            return
+        if host["lr"] is not None and hasattr(self.optimizer, "lr"):
+            self.optimizer.lr = host["lr"]                      # (state_dict() exports it as the rate of the latest step)
+        if hasattr(self.trainer, "last_lr"):
+            self.trainer.last_lr = host["last_lr"]
+        if self.temp is not None:
+            self.temp.step = host["temp_step"]
+            if host["tstate"] is not None:
+                self.temp.tstate.copy_(host["tstate"])
 
 
 class ContrastiveEstimationTrainer:
@@ -1129,7 +1160,7 @@ class ContrastiveEstimationTrainer:
             grouping = (grouping[0], file_group_ids(self.dataset.get_example_count_per_file()))
         self.training_step = continue_training_at_step
         readback = _StepReadback(self, optimizer, run.clip, fused, device.type == "cuda", device_temp, temp_route)
-        rollback = _NanRollback(self, optimizer, fused)
+        rollback = _NanRollback(self, optimizer, fused, device_temp)
         # A full collection of Python's cyclic garbage collector walks every tracked object of the process (38 - 43 ms with the module
         # trees of a model alive) and lands in whichever step crosses its allocation threshold — a GPU that is only a few steps of work
         # ahead of the host idles through it.  What is alive now stays alive for the whole run: collect once and freeze it, later
@@ -1199,7 +1230,10 @@ class ContrastiveEstimationTrainer:
         return None
 
     def _nan_return(self, step, readback, rollback):
-        """Leaves train() after a NaN loss at ``step``: BatchNorm's statistics and the step counts as the reference leaves them."""
+        """Leaves train() after a NaN loss at ``step`` with the run where a clean run of ``step`` steps leaves it ("What the
+        NaN guard holds still"): the device state was never touched (skip flag), BatchNorm's statistics, the optimizer's count and rate,
+        last_lr and the temperature's place are put back (_NanRollback), training_step is the NaN step, and the bank is emptied — the
+        one thing that is reset, not restored.  last_grad_norm stays the NaN step's, which is what is reported below."""
         rollback.restore(step)
         self.training_step = step          # the reference leaves train() inside step `step`, before its update (:124-133)
         self.reset_negative_bank()         # (its latest rows come from the NaN step and the ones launched behind it)
@@ -1316,8 +1350,11 @@ class ContrastiveEstimationTrainer:
         # (engine.CPCEngine.prepare_ahead; under data parallelism Adam follows each reduced gradient piece)
         optimizer.after_update = eng.prepare_ahead
         # NaN guard on the device (reference :124-133 returns before backward() / optimizer.step()): the loss
-        # kernel raises the engine's sticky flag, every Adam launch of this and of later steps is a no-op while it
-        # is up, and the host leaves train() when the step's indicator arrives (host_sync_lag steps later)
+        # kernel — whichever the route takes: dense, sampled, grouped, banked, all-timesteps or the fused chain's finalize —
+        # raises the engine's sticky flag; every stateful launch of this and of later steps (Adam / AdamW / LAMB with its trust
+        # table, cpc_ema, cpc_temperature_step) is a no-op while it is up, and the host leaves train() when the step's indicator
+        # arrives (host_sync_lag steps later); what is no update and so is not skipped — BatchNorm's statistics, a scheduled
+        # temperature's tick, the host's counts — is _NanRollback's to put back
         self._clear_nan_flag_once(run, eng)
         optimizer.skip_flag = eng.nan_flag()
         if run.clip:

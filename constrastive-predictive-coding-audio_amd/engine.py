@@ -2154,7 +2154,10 @@ class FusedAdam:
         # single-process training so that the operand copies of the next step are rebuilt off the critical path
         self.after_update = None
         # skip_flag: one-element device tensor (CPCEngine.nan_flag()); while it is non-zero every update is a no-op on the device
-        # — the reference's NaN guard returns before backward() / optimizer.step() (contrastive_estimation_training.py:124-133)
+        # — the reference's NaN guard returns before backward() / optimizer.step() (contrastive_estimation_training.py:124-133).
+        # Every launch that owns state takes it: _update, _update_lamb, _update_ema, _update_temperature (learnable); a launch added
+        # here without it is what tests/test_nan_guard_routes_gpu.py's controls stand for.  self.lr and self.t are host values: the
+        # trainer's _NanRollback puts them back
         self.skip_flag = None
         # device_step: the step count lives on the device (cpc_adam_dev), so the call's arguments never change and the step
         # can be part of a captured hipGraph

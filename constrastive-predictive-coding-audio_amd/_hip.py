@@ -188,6 +188,8 @@ _SIGNATURES = {
     "cpc_lstm_tape_elems": ([_I, _I, _I, _I], _L),
     "cpc_lstm_fwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "cpc_lstm_bwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+    "cpc_lstm_bwd_steps": ([_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+    "cpc_anchor_target_grad": ([_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P], _I),
     "cpc_nce_workspace_floats": ([_I, _I], _L),
     "cpc_nce_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P], _I),
     "cpc_nce_sampled_workspace_floats": ([_I, _I], _L),

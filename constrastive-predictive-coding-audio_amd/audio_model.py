@@ -224,15 +224,34 @@ class ConvolutionalArModel(nn.Module):
         return standalone_context_forward(self, x, self.ar_size)
 
 
+def check_anchors(prediction_anchors, anchor_stride, visible_steps):
+    """(A, s) as ints, or ValueError: ints (no bools), A >= 1, s >= 1, (A - 1) s <= visible_steps - 1."""
+    for name, v in (("prediction_anchors", prediction_anchors), ("anchor_stride", anchor_stride)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if prediction_anchors > 1 and (prediction_anchors - 1) * anchor_stride > int(visible_steps) - 1:
+        raise ValueError(f"prediction_anchors = {prediction_anchors} with anchor_stride = {anchor_stride} puts the first anchor "
+                         f"{(prediction_anchors - 1) * anchor_stride} steps before the last; at most visible_steps - 1 = "
+                         f"{int(visible_steps) - 1}")
+    return prediction_anchors, anchor_stride
+
+
 class AudioPredictiveCodingModel(nn.Module):
     """encoder -> (targets, z) -> autoregressive context c -> W_k c predictions (reference audio_model.py:164-219).
 
     ``compute_dtype``: "bf16" (default; bf16 storage, f32 accumulate — BASELINE config 2) or "fp32" (exact-f32 MFMA,
-    the parity mode)."""
+    the parity mode).
+    ``prediction_anchors`` = A, ``anchor_stride`` = s ("Prediction anchors"): predictions from the A hidden states
+    h_{V - (A-1-a) s}, a < A, of the one recurrence, each against its own K target frames; ``forward`` then returns predicted_z
+    (B, A K, E) and targets (B, E, A K), head a K + k being step k of anchor a.  The last anchor is the model without anchors; they add
+    no parameter."""
+
+    prediction_anchors, anchor_stride = 1, 1          # (class-level: a model unpickled from before the keywords existed has one anchor)
 
     def __init__(self, encoder, autoregressive_model, enc_size, ar_size, visible_steps=100, prediction_steps=12,
-                 activation_register=None, compute_dtype="bf16"):
+                 activation_register=None, compute_dtype="bf16", prediction_anchors=1, anchor_stride=1):
         super().__init__()
+        self.prediction_anchors, self.anchor_stride = check_anchors(prediction_anchors, anchor_stride, visible_steps)
         self.enc_size = enc_size
         self.ar_size = ar_size
         self.visible_steps = visible_steps
@@ -314,6 +333,8 @@ class AudioPredictiveCodingModel(nn.Module):
         shape = tuple(int(v) for v in length) if self._scalogram else int(length)
         gp = bool(getattr(self, "gradient_penalty_engine", False)) and self._scalogram
         key = (int(batch_size), shape, self.compute_dtype, str(device), gp)
+        if self.prediction_anchors > 1:
+            key += (self.prediction_anchors, self.anchor_stride)
         eng = self._engines.get(key)
         if eng is None or self._flat_param is None or any(
                 p.data_ptr() != self._param[n].data_ptr() for n, p in self.named_parameters()):
@@ -382,6 +403,11 @@ class _CPCForward(torch.autograd.Function):
     def backward(ctx, d_pred, d_targets, d_z, d_c):
         eng = ctx.eng
         B, E, K, V, T = eng.B, eng.E, eng.K, eng.V, eng.T
+        if getattr(eng, "A", 1) > 1:          # stacked heads: d_pred -> dpred, d_targets -> dT (summed into the top rows by backward())
+            eng.anchor_bridge_grads(d_pred, d_targets)
+            eng.backward(ctx.xin, add_dc=d_c, add_dz=d_z)
+            grads = [eng.model._grad[n].clone() for n, _ in eng.model.named_parameters()]
+            return (None, None, *grads)
         dtop = eng.dact[-1].view(B, eng.geo.alloc[-1], E)
         if d_pred is None:
             eng.dpred.zero_()

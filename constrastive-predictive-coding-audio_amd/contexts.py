@@ -144,6 +144,9 @@ class Context:
 
     ahead_ok = False      # True: prepare_weights is a pure function of the parameters (CPCEngine.prepare_ahead)
     z_scale = 1.0         # what the network multiplies z by in place (AttentionModel: sqrt(C))
+    anchors_ok = False    # True: backward() accepts gradients at earlier hidden states (``anchor_dHs``; GRUContext, LSTMContext)
+    anchor_dHs = None     # prediction anchors: storage-dtype [B][V][H], row (b, t) the gradient that reaches h_{t+1} from the predictor;
+                          # owned and filled by the engine (CPCEngine._alloc_head), read by backward() of the top recurrent layer
 
     def tangent(self, top_t):
         raise NotImplementedError(f"{type(self).__name__} has no tangent pass: no gradient penalty through this context network")
@@ -163,6 +166,7 @@ class GRUContext(Context):
     (item, step) (cpc_gru_bwd_steps)."""
 
     ahead_ok = True       # prepare_weights is a pure function of the parameters (CPCEngine.prepare_ahead)
+    anchors_ok = True
 
     def __init__(self, eng, ar):
         self.eng = eng
@@ -285,7 +289,10 @@ class GRUContext(Context):
         # encoder's gradient-ready hook runs on that stream behind all of them.
         for l in range(self.L - 1, -1, -1):
             lay = self.layers[l]
-            if l == self.L - 1:
+            if l == self.L - 1 and self.anchor_dHs is not None:          # prediction anchors: gradients at earlier states of the top layer
+                _hip.call("cpc_gru_bwd_steps", _hip.ptr(dc), _hip.ptr(self.anchor_dHs), C.c_longlong(H), _hip.ptr(lay.tape),
+                          _hip.ptr(lay.w_hh_t_frag), _hip.ptr(lay.dG), B, V, H, code)
+            elif l == self.L - 1:
                 _hip.call("cpc_gru_bwd", _hip.ptr(dc), _hip.ptr(lay.tape), _hip.ptr(lay.w_hh_t_frag), _hip.ptr(lay.dG), B, V, H, code)
             else:
                 _hip.call("cpc_gru_bwd_steps", None, _hip.ptr(self.dH), C.c_longlong(H), _hip.ptr(lay.tape), _hip.ptr(lay.w_hh_t_frag),
@@ -409,6 +416,7 @@ class LSTMContext(Context):
     the base class's refusal)."""
 
     ahead_ok = True       # prepare_weights is a pure function of the parameters (CPCEngine.prepare_ahead)
+    anchors_ok = True
     prefix = "autoregressive_model.lstmCell."
 
     def __init__(self, eng, ar):
@@ -502,7 +510,11 @@ class LSTMContext(Context):
                                "backward()); use reset_hidden=False for inference / streaming, or set model.hidden = None before a train step")
         if e._gp_phase:
             raise NotImplementedError(self.GP_REASON)
-        _hip.call("cpc_lstm_bwd", _hip.ptr(dc), _hip.ptr(self.tape), _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
+        if self.anchor_dHs is not None:          # prediction anchors: gradients at earlier hidden states
+            _hip.call("cpc_lstm_bwd_steps", _hip.ptr(dc), _hip.ptr(self.anchor_dHs), C.c_longlong(H), _hip.ptr(self.tape),
+                      _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
+        else:
+            _hip.call("cpc_lstm_bwd", _hip.ptr(dc), _hip.ptr(self.tape), _hip.ptr(self.w_hh_t_frag), _hip.ptr(self.dG), B, V, H, code)
         # the parameter gradients (short launches, off the critical path dG -> dz -> encoder backward) follow dG on the side stream
         with e.side(self.ev):
             self._params()

@@ -841,6 +841,38 @@ class ContrastiveEstimationTrainer:
                                       f"temperature, not {self.optimizer!r} with {sf!r}")
         return slots_back
 
+    def _check_anchors(self):
+        """Up-front checks of the model's prediction_anchors (before any GPU work).  With A > 1 the engine route with
+        softplus_score_function or linear_score_function and in-batch negatives is supported; it composes with what is orthogonal to
+        the loss (clipping, AdamW and schedule, LAMB, EMA, waveform augmentation, a device-resident dataset).  NotImplementedError for
+        everything that indexes K heads per item or has no stacked-head form."""
+        A = int(getattr(self.model, "prediction_anchors", 1))
+        if A <= 1:
+            return
+        what = f"prediction_anchors = {A}"
+        if self.score_over_all_timesteps:
+            raise NotImplementedError(f"{what}: score_over_all_timesteps contrasts the (item, step) pairs of ONE anchor's K steps; no "
+                                      "all-timesteps loss over stacked anchors exists")
+        if self.num_negatives is not None:
+            raise NotImplementedError(f"{what}: num_negatives — the sampler's draws are keyed by the K prediction steps, not by A K heads")
+        if self.negative_groups is not None:
+            raise NotImplementedError(f"{what}: negative_groups — the grouped loss is not stacked over anchors")
+        if self.negative_bank is not None:
+            raise NotImplementedError(f"{what}: negative_bank — the bank's rows are [B][K][E] predictions of one anchor")
+        if self.global_negatives:
+            raise NotImplementedError(f"{what}: global_negatives — the gathered loss is built for K heads per item")
+        if self.wasserstein_gradient_penalty:
+            raise NotImplementedError(f"{what}: wasserstein_gradient_penalty — its tangent passes differentiate c = h_V alone")
+        sf = self.score_function
+        if sf is difference_score_function or isinstance(sf, NormalizedScoreFunction):
+            raise NotImplementedError(f"{what}: difference and normalized scores are not stacked over anchors; use "
+                                      "softplus_score_function or linear_score_function")
+        if not self._fused():
+            raise NotImplementedError(f"{what} runs on the engine route only: optimizer=torch.optim.Adam with linear_score_function or "
+                                      f"softplus_score_function, not {self.optimizer!r} with {sf!r} (the generic route scores K heads)")
+        if self.use_graph:
+            raise NotImplementedError(f"{what}: use_graph — no captured step with anchors exists")
+
     def reset_negative_bank(self):
         """Empties the bank: the next step is the in-batch step again, the ones after it fill the bank anew."""
         if self._bank is not None:
@@ -1132,6 +1164,7 @@ class ContrastiveEstimationTrainer:
         """Same contract as the reference's train (:74-176): returns ``prof`` (None unless profile=True) when max_steps is
         reached, None on a NaN loss or when the epochs are exhausted.  ``batch_size`` is the per-process batch; under
         torch.distributed the sampler draws batch_size * world_size indices and every rank takes its slice."""
+        self._check_anchors()
         self._check_negatives(batch_size)
         grouping = self._check_negative_groups()
         bank_kw = self._bank_kw(self._check_negative_bank())
@@ -1476,6 +1509,10 @@ class ContrastiveEstimationTrainer:
         ws = torch.empty(int(_hip.lib().cpc_nce_eval_workspace_floats(batch_size, K)), device=device, dtype=torch.float32)
         kernel_scores = (self.score_function in (softplus_score_function, linear_score_function, difference_score_function)
                          or isinstance(self.score_function, NormalizedScoreFunction))
+        if int(getattr(self.model, "prediction_anchors", 1)) > 1 and (all_t or self.score_function not in (softplus_score_function,
+                                                                                                             linear_score_function)):
+            raise NotImplementedError("validate() with prediction_anchors > 1 scores the last anchor's K heads with "
+                                      "softplus_score_function or linear_score_function, score_over_all_timesteps=False")
         self.model.eval()
         done = 0
         with torch.no_grad():

@@ -689,6 +689,19 @@ int cpc_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, voi
     return launch_lstm_bwd(dh_last, tape, WTfrag, dG, B, V, H, dtype, (hipStream_t)stream);
 }
 
+int cpc_lstm_bwd_steps(const float* dh_last, const void* dHs, long long ld_h, const void* tape, const void* WTfrag, void* dG, int B,
+                       int V, int H, int dtype, void* stream) {
+    if (!tape || !WTfrag || !dG || (!dh_last && !dHs)) return CPC_EINVAL;
+    return launch_lstm_bwd(dh_last, tape, WTfrag, dG, B, V, H, dtype, (hipStream_t)stream, dHs, ld_h);
+}
+
+int cpc_anchor_target_grad(const float* dT, void* dtop, long long item_stride, int A, int B, int K, int E, int first_row, int stride,
+                           int row_lo, int row_hi, int accumulate, int dtype, void* stream) {
+    if (!dT || !dtop) return CPC_EINVAL;
+    return launch_anchor_target_grad(dT, dtop, item_stride, A, B, K, E, first_row, stride, row_lo, row_hi, accumulate, dtype,
+                                     (hipStream_t)stream);
+}
+
 extern int g_gru_force_streaming;
 int cpc_gru_set_streaming(int on) {
     const int old = g_gru_force_streaming;

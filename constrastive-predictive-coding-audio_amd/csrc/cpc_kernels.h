@@ -147,7 +147,9 @@ long long lstm_tape_elems(int B, int V, int H, int dtype);
 int launch_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const float* h0, const float* c0, void* Hall, void* tape,
                     float* h_out, float* cell_out, int B, int V, int H, int dtype, hipStream_t stream);
 int launch_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
-                    hipStream_t stream);
+                    hipStream_t stream, const void* dHs = nullptr, long long ld_h = 0);
+int launch_anchor_target_grad(const float* dT, void* dtop, long long item, int A, int B, int K, int E, int first_row, int stride,
+                              int row_lo, int row_hi, int accumulate, int dtype, hipStream_t stream);
 int launch_prep_frag(const float* src, void* dst, int R, int Kd, long long ld, int transpose, int dtype, hipStream_t stream);
 int launch_nce_lse_merge(const float* pm, const float* ps, int nparts, int ncols, int softplus, float nrows, float* lse, float* colp,
                          hipStream_t stream);

@@ -161,9 +161,13 @@ __global__ __launch_bounds__(64 * NW) void lstm_fwd_kernel(const T* __restrict__
 }
 
 // WTfrag: fragment-ordered W_hh^T ([H][4H] logical: rows = hidden unit, k = gate column).
-template <typename T, int NW>
+// STEPS (cpc_lstm_bwd_steps: predictions from several context steps): a gradient arrives at every hidden state,
+// dHs[(b V + t) ld_h + j] at h_{t+1}, and joins dh at the top of step t; dh_last may then be NULL (zeros).  STEPS == false is
+// cpc_lstm_bwd's code: dHs / ld_h are not read.
+template <typename T, int NW, bool STEPS>
 __device__ __forceinline__ void lstm_bwd_steps(unsigned char* smem, const float* __restrict__ dh_last, const T* __restrict__ tape,
-                                               const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+                                               const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H,
+                                               const T* __restrict__ dHs, long long ld_h) {
     constexpr int CH = Elem<T>::CH;
     const int rowb = 4 * H * (int)sizeof(T) + 16;
     unsigned char* gcur = smem;                            // gate-gradient tile [16][4H] (+16 B pad per row)
@@ -182,7 +186,7 @@ __device__ __forceinline__ void lstm_bwd_steps(unsigned char* smem, const float*
         const int jt = wave + NW * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { dh[q][e] = 0.f; dcell[q][e] = 0.f; }
-        if (jt < ntile && b_ok) {
+        if (jt < ntile && b_ok && (!STEPS || dh_last)) {
             const f32x4 v = *(const f32x4*)(dh_last + (long long)b * H + jt * 16 + fg * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dh[q][e] = v[e];
@@ -200,6 +204,11 @@ __device__ __forceinline__ void lstm_bwd_steps(unsigned char* smem, const float*
                     const T* gp = tape + (((long long)b * V + t) * LSTM_SLOTS) * H + j;
                     i4 = load4(gp); f4 = load4(gp + H); g4 = load4(gp + 2 * H); o4 = load4(gp + 3 * H);
                     cp4 = load4(gp + 4 * H); tc4 = load4(gp + 5 * H);
+                    if constexpr (STEPS) {          // rows of items >= B and columns [H, ld_h) are not read
+                        const f32x4 ds = load4(dHs + ((long long)b * V + t) * ld_h + j);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dh[q][e] += ds[e];
+                    }
                 }
                 f32x4 di4, df4, dg4, do4;
 #pragma unroll
@@ -250,11 +259,12 @@ __device__ __forceinline__ void lstm_bwd_steps(unsigned char* smem, const float*
     }
 }
 
-template <typename T, int NW>
+template <typename T, int NW, bool STEPS>
 __global__ __launch_bounds__(64 * NW) void lstm_bwd_kernel(const float* __restrict__ dh_last, const T* __restrict__ tape,
-                                                           const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H) {
+                                                           const T* __restrict__ WTfrag, T* __restrict__ dG, int B, int V, int H,
+                                                           const T* __restrict__ dHs, long long ld_h) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LstmLds<T, 64 * NW>::BWD];
-    lstm_bwd_steps<T, NW>(smem, dh_last, tape, WTfrag, dG, B, V, H);
+    lstm_bwd_steps<T, NW, STEPS>(smem, dh_last, tape, WTfrag, dG, B, V, H, dHs, ld_h);
 }
 
 constexpr int LSTM_LDS_LIMIT = 160 * 1024;          // LDS of one gfx950 CU
@@ -291,17 +301,23 @@ int launch_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const f
     return CPC_OK;
 }
 
+// dHs == NULL: cpc_lstm_bwd's kernels.  Otherwise the STEPS instantiations of the same body, chosen the same way.
 int launch_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype,
-                    hipStream_t stream) {
+                    hipStream_t stream, const void* dHs, long long ld_h) {
     if (!lstm_ok(B, V, H, dtype)) return CPC_EINVAL;
+    if (!dHs && !dh_last) return CPC_EINVAL;
+    if (dHs && (ld_h < H || ld_h % (dtype == CPC_DTYPE_BF16 ? 8 : 4))) return CPC_EINVAL;
     const dim3 grid((B + 15) / 16);
-#define LSTM_B(T, NW) \
-    hipLaunchKernelGGL((lstm_bwd_kernel<T, NW>), grid, dim3(64 * NW), 0, stream, dh_last, (const T*)tape, (const T*)WTfrag, (T*)dG, B, V, H)
+#define LSTM_B(T, NW, STEPS) \
+    hipLaunchKernelGGL((lstm_bwd_kernel<T, NW, STEPS>), grid, dim3(64 * NW), 0, stream, dh_last, (const T*)tape, (const T*)WTfrag, \
+                       (T*)dG, B, V, H, (const T*)dHs, ld_h)
+#define LSTM_BS(T, NW) do { if (dHs) LSTM_B(T, NW, true); else LSTM_B(T, NW, false); } while (0)
     if (H > 256) {
-        if (dtype == CPC_DTYPE_BF16) LSTM_B(bf16_t, 8); else LSTM_B(float, 8);
+        if (dtype == CPC_DTYPE_BF16) LSTM_BS(bf16_t, 8); else LSTM_BS(float, 8);
     } else {
-        if (dtype == CPC_DTYPE_BF16) LSTM_B(bf16_t, 4); else LSTM_B(float, 4);
+        if (dtype == CPC_DTYPE_BF16) LSTM_BS(bf16_t, 4); else LSTM_BS(float, 4);
     }
+#undef LSTM_BS
 #undef LSTM_B
     CPC_CHECK_LAUNCH();
     return CPC_OK;

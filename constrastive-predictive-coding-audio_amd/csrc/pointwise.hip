@@ -912,3 +912,94 @@ int launch_sign_bits(const void* x, unsigned char* bits, long long n, int dtype,
     CPC_CHECK_LAUNCH();
     return CPC_OK;
 }
+
+// ------------------------------------------------------------------------------------------- prediction anchors: target gradients
+// cpc_anchor_target_grad: the top-layer gradient rows that the target windows of A anchors share.  dT f32 [A][B][K][E] holds every
+// anchor's d loss / d targets; the window of anchor a covers top rows [first_row + a stride, first_row + a stride + K).  A gather per
+// output row: a thread owns one 16-byte piece (CH channels) of one row r in [row_lo, row_hi) of one item and sums, in f32 and with a
+// ascending, the pieces dT[a][b][r - first_row - a stride] of the windows that cover r — the anchors a in [a_lo, a_hi], worked out
+// from the arguments alone, so the order of the sum is fixed and nothing is atomic.  ACC adds the stored row first-to-last behind the
+// sum (one rounding); a row no window covers is written as zeros (ACC == 0) or not touched (ACC).  Channels on the lanes: a wave reads
+// 64 consecutive 16- or 32-byte pieces of a dT row per anchor and writes 1 KiB of the output row.
+template <typename T, bool ACC>
+__global__ __launch_bounds__(256) void anchor_target_grad_kernel(const float* __restrict__ dT, T* __restrict__ dtop, long long item,
+                                                                 int A, int B, int K, int E, long long first_row, long long stride,
+                                                                 int row_lo, int nrows) {
+    constexpr int CH = Elem<T>::CH;
+    const int pieces = E / CH;
+    const long long total = (long long)B * nrows * pieces;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int p = (int)(i % pieces);
+        const long long br = i / pieces;
+        const int r = row_lo + (int)(br % nrows);
+        const int b = (int)(br / nrows);
+        // anchors with 0 <= r - first_row - a stride < K
+        const long long rel = (long long)r - first_row;
+        long long a_hi = rel >= 0 ? rel / stride : -1;
+        const long long need = rel - (K - 1);                       // a stride >= need
+        long long a_lo = need <= 0 ? 0 : (need + stride - 1) / stride;
+        if (a_hi > A - 1) a_hi = A - 1;
+        T* out = dtop + (long long)b * item + (long long)r * E + p * CH;
+        if (a_lo > a_hi) {
+            if constexpr (!ACC) {
+                if constexpr (CH == 8) *(uint4*)out = make_uint4(0u, 0u, 0u, 0u);
+                else *(f32x4*)out = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            continue;
+        }
+        float acc[CH];
+#pragma unroll
+        for (int e = 0; e < CH; ++e) acc[e] = 0.f;
+        for (long long a = a_lo; a <= a_hi; ++a) {
+            const long long k = rel - a * stride;
+            const float* src = dT + (((long long)a * B + b) * K + k) * E + p * CH;
+#pragma unroll
+            for (int q = 0; q < CH / 4; ++q) {
+                const f32x4 v = *(const f32x4*)(src + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[4 * q + e] += v[e];
+            }
+        }
+        if constexpr (CH == 8) {
+            bf16x8 o;
+            if constexpr (ACC) {
+                const bf16x8 old = *(const bf16x8*)out;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += (float)old[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (bf16_t)acc[e];
+            *(bf16x8*)out = o;
+        } else {
+            f32x4 o;
+            if constexpr (ACC) {
+                const f32x4 old = *(const f32x4*)out;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += old[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = acc[e];
+            *(f32x4*)out = o;
+        }
+    }
+}
+
+int launch_anchor_target_grad(const float* dT, void* dtop, long long item, int A, int B, int K, int E, int first_row, int stride,
+                              int row_lo, int row_hi, int accumulate, int dtype, hipStream_t stream) {
+    if (dtype != CPC_DTYPE_BF16 && dtype != CPC_DTYPE_F32) return CPC_EINVAL;
+    const int ch = dtype == CPC_DTYPE_BF16 ? 8 : 4;
+    if (!dT || !dtop || A < 1 || B < 1 || K < 1 || stride < 1 || E < 1 || E % ch) return CPC_EINVAL;
+    if (row_lo < 0 || row_hi <= row_lo || first_row < 0) return CPC_EINVAL;
+    if (item % ch || item < (long long)row_hi * E) return CPC_EINVAL;          // 16-byte pieces; the items' row ranges do not overlap
+    const int nrows = row_hi - row_lo;
+    const long long total = (long long)B * nrows * (E / ch);
+    const int blocks = (int)min((long long)2048, (total + 255) / 256);          // 256 CUs x 8 blocks; the rest by the grid stride
+#define ATG(T, ACC) \
+    hipLaunchKernelGGL((anchor_target_grad_kernel<T, ACC>), dim3(blocks), dim3(256), 0, stream, dT, (T*)dtop, item, A, B, K, E, \
+                       (long long)first_row, (long long)stride, row_lo, nrows)
+    if (dtype == CPC_DTYPE_BF16) { if (accumulate) ATG(bf16_t, true); else ATG(bf16_t, false); }
+    else { if (accumulate) ATG(float, true); else ATG(float, false); }
+#undef ATG
+    CPC_CHECK_LAUNCH();
+    return CPC_OK;
+}

@@ -413,10 +413,40 @@ class EncoderGeometry:
         self.frames = self.valid[-1]
 
 
+ANCHOR_LOSS_REASON = ("prediction_anchors > 1 runs the equal-step InfoNCE loss over the whole batch with softplus or linear scores: "
+                      "score_over_all_timesteps, sampled / grouped / banked / global negatives and difference / normalized scores index "
+                      "K heads per item and are not stacked over anchors")
+
+
+def check_anchor_context(model, scalogram=False):
+    """prediction_anchors > 1 needs every hidden state of a recurrence: AudioGRUModel / AudioLSTMModel in the waveform engine."""
+    A = int(getattr(model, "prediction_anchors", 1))
+    if A <= 1:
+        return
+    from .audio_model import AudioGRUModel, AudioLSTMModel
+    ar = model.autoregressive_model
+    if scalogram:
+        raise NotImplementedError(f"prediction_anchors = {A}: the scalogram / grid engines expose the context c at the last position only; "
+                                  "anchors are on the waveform engine with an AudioGRUModel or AudioLSTMModel")
+    if not isinstance(ar, (AudioGRUModel, AudioLSTMModel)):
+        raise NotImplementedError(f"prediction_anchors = {A}: {type(ar).__name__} exposes the context c at the last position only (no "
+                                  "hidden state per visible step to predict from); anchors need an AudioGRUModel or AudioLSTMModel")
+
+
 class CPCEngine(ContextHost):
+    A, s = 1, 1                 # prediction anchors and their stride (set by __init__; ScalogramCPCEngine keeps 1)
+
+    @property
+    def AK(self):
+        """Heads of the loss: K prediction steps of each of the A anchors."""
+        return self.A * self.K
+
     def __init__(self, model, batch_size: int, length: int, device, dtype: torch.dtype):
         enc, ar = model.encoder, model.autoregressive_model
+        check_anchor_context(model)          # (refused before anything is allocated or launched)
         super().__init__(model, device, dtype, batch_size, enc.channel_count[-1], model.ar_size, model.prediction_steps, model.visible_steps)
+        # prediction anchors (DESIGN.md, "Prediction anchors"): A hidden states of the one recurrence predict, s steps apart; AK heads
+        self.A, self.s = int(getattr(model, "prediction_anchors", 1)), int(getattr(model, "anchor_stride", 1))
         self.L = int(length)
         self.strides = list(enc.strides)
         self.kernels = list(enc.kernel_sizes)
@@ -562,7 +592,30 @@ class CPCEngine(ContextHost):
         if self.ctx is not None:
             self.ctx.allocate()
             need.append(self.ctx.slab_floats())
+        if self.A > 1:
+            need.append(self._alloc_anchors())
         self.slabs = torch.empty(max(need), device=dev, dtype=f32)
+
+    def _alloc_anchors(self):
+        """Prediction anchors: the head's buffers again for AK heads ([B][AK][E] predictions, AK score blocks), every anchor's target
+        gradients dT f32 [A][B][K][E], the B A rows of dc, and the top recurrent layer's dHs [B][V][H] — zeroed once here; the same A - 1
+        rows per item are rewritten every step.  Returns the floats the split-K slabs of the dc GEMM need."""
+        dev, dt, f32 = self.device, self.dt, torch.float32
+        B, H, E, K, V, A, AK = self.B, self.H, self.E, self.K, self.V, self.A, self.AK
+        if self.ctx is None or not self.ctx.anchors_ok:
+            raise NotImplementedError(f"prediction_anchors = {A}: {type(self.ctx).__name__} exposes c at the last position only")
+        self.pred = torch.empty(B * AK * E, device=dev, dtype=dt)
+        self.dpred = torch.zeros(B * AK * E, device=dev, dtype=dt)
+        self.S = torch.zeros(AK * B * self.ldS, device=dev, dtype=f32)
+        self.dS = torch.zeros(AK * B * self.ldS, device=dev, dtype=dt)
+        self.dST = torch.zeros(AK * B * self.ldS, device=dev, dtype=dt)
+        self.nce_ws = torch.empty(int(_hip.lib().cpc_nce_workspace_floats(B, AK)), device=dev, dtype=f32)
+        self.dT = torch.zeros(A * B * K * E, device=dev, dtype=f32)
+        self.dcA = torch.zeros(B * A, H, device=dev, dtype=f32)
+        self.ctx.anchor_dHs = torch.zeros(B * V * H, device=dev, dtype=dt)
+        # step index t of dHs that anchor a < A - 1 writes: its context is h_{V - d_a} = the state after step t = V - d_a - 1
+        self._anchor_steps = torch.tensor([V - (A - 1 - a) * self.s - 1 for a in range(A - 1)], device=dev, dtype=torch.long)
+        return _ceil_div(max(K * E, 1), 256) * B * A * H
 
     # ---------------------------------------------------------------------------------- weight layouts
     def prepare_weights(self):
@@ -750,8 +803,13 @@ class CPCEngine(ContextHost):
         code, B, H, E, K = self.code, self.B, self.H, self.E, self.K
         self.ctx.forward()
         ct, coff, cstride = self.ctx.c_operand()
-        _hip.gemm_nt(_hip.ptr(ct, coff), _hip.ptr(self.w_p), _hip.ptr(self.pred), B, K * E, H, H, H, K * E, code,
-                     a_rpi=1, a_item=cstride)
+        if self.A > 1:          # B A rows straight out of the hidden states: row (b, a) = h_{V - (A-1-a) s}; pred [B][AK][E]
+            A, s = self.A, self.s
+            _hip.gemm_nt(_hip.ptr(ct, coff - (A - 1) * s * H), _hip.ptr(self.w_p), _hip.ptr(self.pred), B * A, K * E, H, s * H, H, K * E,
+                         code, a_rpi=A, a_item=cstride)
+        else:
+            _hip.gemm_nt(_hip.ptr(ct, coff), _hip.ptr(self.w_p), _hip.ptr(self.pred), B, K * E, H, H, H, K * E, code,
+                         a_rpi=1, a_item=cstride)
         ev = getattr(self, "_tl_pending", None)
         if ev is not None:          # the target rows of the encoder (side stream, see encoder_forward) are complete from here on
             torch.cuda.current_stream().wait_event(ev)
@@ -772,6 +830,10 @@ class CPCEngine(ContextHost):
 
     _tl_in_forward = False
 
+    def _anchor_rows(self):
+        """First target row of every anchor: T - K - d_a, d_a = (A - 1 - a) s."""
+        return [self.T - self.K - (self.A - 1 - a) * self.s for a in range(self.A)]
+
     # views of the forward results in the reference's shapes (storage dtype, no copies)
     def view_top(self):
         return self.act[-1].view(self.B, self.geo.alloc[-1], self.E)
@@ -780,8 +842,11 @@ class CPCEngine(ContextHost):
         """(predicted_z (B,K,E), targets (B,E,K), z (B,E,V), c (B,H)) as float32 tensors in the reference's shapes."""
         top = self.view_top()
         T, K, V = self.T, self.K, self.V
-        pred = self.pred.view(self.B, K, self.E).float()
-        targets = top[:, T - K:T, :].float().transpose(1, 2)
+        pred = self.pred.view(self.B, self.AK, self.E).float()
+        if self.A > 1:          # head a K + k: frame T - K - d_a + k
+            targets = torch.cat([top[:, r:r + K, :] for r in self._anchor_rows()], 1).float().transpose(1, 2)
+        else:
+            targets = top[:, T - K:T, :].float().transpose(1, 2)
         z = top[:, T - K - V:T - K, :].float().transpose(1, 2)
         zs = self.ctx.z_scale       # AttentionModel rescales z in place (attention_model.py:30)
         if zs != 1.0:
@@ -829,7 +894,20 @@ class CPCEngine(ContextHost):
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         pred = self.pred if pred is None else pred
         top = self.act[-1] if top is None else top
-        _hip.gemm_nt(_hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(self.S if out is None else out), B, B, E, K * E, Ltop * E, ld,
+        out = self.S if out is None else out
+        if self.A > 1:
+            # heads a K + k against rows T - K - d_a + k.  Stride == K: the windows tile rows [T - AK, T), one launch over AK heads;
+            # otherwise today's launch per anchor at its head offset into pred (ld = AK E) and its own first target row
+            AK = self.AK
+            if self.s == K:
+                _hip.gemm_nt(_hip.ptr(pred), _hip.ptr(top, (T - AK) * E), _hip.ptr(out), B, B, E, AK * E, Ltop * E, ld,
+                             code, a_batch=E, b_batch=E, c_batch=B * ld, batch=AK, flags=_hip.GEMM_OUT_F32)
+            else:
+                for a, r in enumerate(self._anchor_rows()):
+                    _hip.gemm_nt(_hip.ptr(pred, a * K * E), _hip.ptr(top, r * E), _hip.ptr(out, a * K * B * ld), B, B, E, AK * E, Ltop * E,
+                                 ld, code, a_batch=E, b_batch=E, c_batch=B * ld, batch=K, flags=_hip.GEMM_OUT_F32)
+            return 2.0 * AK * B * B * E
+        _hip.gemm_nt(_hip.ptr(pred), _hip.ptr(top, (T - K) * E), _hip.ptr(out), B, B, E, K * E, Ltop * E, ld,
                      code, a_batch=E, b_batch=E, c_batch=B * ld, batch=K, flags=_hip.GEMM_OUT_F32)
         return 2.0 * K * B * B * E
 
@@ -891,6 +969,8 @@ class CPCEngine(ContextHost):
         All on the current stream: the target-row lane of backward() starts from those rows behind the event it records there.
         ``temperature``: already checked by the caller (nce_forward_backward / nce_all_forward_backward)."""
         selection = select_negatives(self.B, negatives, negative_groups, all_timesteps, None, negative_bank, kind, temperature)
+        if self.A > 1 and (all_timesteps or selection is not None or kind not in ("softplus", "linear")):
+            raise NotImplementedError(ANCHOR_LOSS_REASON)
         pred, top, dpred, dtop = self.pred, self.act[-1], self.dpred, self.dact[-1]
         if kind == "normalized":
             if isinstance(temperature, DeviceTemperature):
@@ -990,7 +1070,7 @@ class CPCEngine(ContextHost):
         if all_timesteps:
             _hip.call("cpc_nce_loss_all", P(S), P(ST), P(dS), P(dST), out, P(self.nce_all_ws), B, K, self.ldS_all, softplus, reg, code)
         elif selection is None:
-            _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), out, P(self.nce_ws), B, K, self.ldS, softplus, reg, code)
+            _hip.call("cpc_nce_loss", P(S), P(dS), P(dST), out, P(self.nce_ws), B, self.AK, self.ldS, softplus, reg, code)
         elif selection[0] == "sampled":
             if getattr(self, "nce_sampled_ws", None) is None:
                 self.nce_sampled_ws = torch.empty(int(_hip.lib().cpc_nce_sampled_workspace_floats(B, K)), device=self.device,
@@ -1019,6 +1099,9 @@ class CPCEngine(ContextHost):
         code, B, E, K = self.code, self.B, self.E, self.K
         Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
         rows = B if rows is None else rows
+        if self.A > 1:
+            self._score_grads_anchors(W, WT, pred, top, out_pred)
+            return
         # out_pred[b][k][:] = sum_b' W[k][b][b'] * targets[b'][k][:]
         _hip.gemm_tn(_hip.ptr(WT), _hip.ptr(top, (T - K) * E), _hip.ptr(out_pred), B, B, E, ld, Ltop * E, K * E, code,
                      a_batch=B * ld, b_batch=E, c_batch=E, batch=K)
@@ -1038,6 +1121,43 @@ class CPCEngine(ContextHost):
         else:
             _hip.call("cpc_reduce_slabs", _hip.ptr(slabs), _hip.ptr(slabs, nsplit * n), B, K * E, nsplit, L(n), 1, L(1), L(K * E), L(0))
             out_top[:B * Ltop * E].view(B, Ltop, E)[:, T - K:T, :].copy_(slabs[nsplit * n:(nsplit + 1) * n].view(B, K, E))
+
+    def _score_grads_anchors(self, W, WT, pred, top, out_pred):
+        """_score_grads over AK heads.  The prediction side is the same contraction per anchor (one launch where the windows tile);
+        the target side goes to dT f32 [A][B][K][E], because the windows of different anchors may share top rows: one gather
+        (cpc_anchor_target_grad) then makes rows [T-K, T) of the top-layer gradient final, before backward() is issued — the invariant
+        both target lanes rest on (_bwd_lane); backward() adds the rows below T-K behind the context network's dz."""
+        code, B, E, K, AK = self.code, self.B, self.E, self.K, self.AK
+        Ltop, T, ld = self.geo.alloc[-1], self.T, self.ldS
+        if self.s == K:
+            _hip.gemm_tn(_hip.ptr(WT), _hip.ptr(top, (T - AK) * E), _hip.ptr(out_pred), B, B, E, ld, Ltop * E, AK * E, code,
+                         a_batch=B * ld, b_batch=E, c_batch=E, batch=AK)
+        for a, r in enumerate(self._anchor_rows()):
+            if self.s != K:
+                _hip.gemm_tn(_hip.ptr(WT, a * K * B * ld), _hip.ptr(top, r * E), _hip.ptr(out_pred, a * K * E), B, B, E, ld, Ltop * E,
+                             AK * E, code, a_batch=B * ld, b_batch=E, c_batch=E, batch=K)
+            _hip.gemm_tn(_hip.ptr(W, a * K * B * ld), _hip.ptr(pred, a * K * E), _hip.ptr(self.dT, a * B * K * E), B, B, E, ld, AK * E,
+                         K * E, code, a_batch=B * ld, b_batch=E, c_batch=E, batch=K, flags=_hip.GEMM_OUT_F32)
+        self._anchor_target_rows(T - K, T, 0)
+
+    def _anchor_target_rows(self, lo, hi, accumulate):
+        """Rows [lo, hi) of the top-layer gradient from dT (cpc_anchor_target_grad): written, or added to what is there."""
+        _hip.call("cpc_anchor_target_grad", _hip.ptr(self.dT), _hip.ptr(self.dact[-1]), C.c_longlong(self.geo.alloc[-1] * self.E),
+                  self.A, self.B, self.K, self.E, self._anchor_rows()[0], self.s, lo, hi, accumulate, self.code)
+
+    def anchor_bridge_grads(self, d_pred, d_targets):
+        """The autograd bridge with anchors: d predicted_z (B, AK, E) into dpred, d targets (B, E, AK) into dT, and rows [T-K, T) of the
+        top-layer gradient from it; backward() does the rest.  None: zeros."""
+        B, E, K, A = self.B, self.E, self.K, self.A
+        if d_pred is None:
+            self.dpred.zero_()
+        else:
+            self.dpred.view(B, self.AK, E).copy_(d_pred)
+        if d_targets is None:
+            self.dT.zero_()
+        else:
+            self.dT.view(A, B, K, E).copy_(d_targets.reshape(B, E, A, K).permute(2, 0, 3, 1))
+        self._anchor_target_rows(self.T - K, self.T, 0)
 
     def _score_grads_all(self, W, WT, pred, top, out_pred, out_top):
         """The same for the all-timesteps branch: W [(b,k)][(b',k')] and its transpose.
@@ -1106,7 +1226,14 @@ class CPCEngine(ContextHost):
         temperature = check_temperature(temperature, kind)
         pred, top = self._norm_operands(temperature) if kind == "normalized" else (self.pred, self.act[-1])
         S, ld = (self._all_scores(), self.ldS_all) if all_timesteps else (self.S, self.ldS)
-        self._scores(kind, all_timesteps, pred, top, S)
+        if self.A > 1:          # the last anchor's K heads (today's model): the numbers stay comparable across anchor settings
+            if all_timesteps or kind not in ("softplus", "linear"):
+                raise NotImplementedError(ANCHOR_LOSS_REASON)
+            code, B, E, K, T = self.code, self.B, self.E, self.K, self.T
+            _hip.gemm_nt(_hip.ptr(pred, (self.A - 1) * K * E), _hip.ptr(top, (T - K) * E), _hip.ptr(S), B, B, E, self.AK * E,
+                         self.geo.alloc[-1] * E, ld, code, a_batch=E, b_batch=E, c_batch=B * ld, batch=K, flags=_hip.GEMM_OUT_F32)
+        else:
+            self._scores(kind, all_timesteps, pred, top, S)
         _hip.call("cpc_nce_eval", _hip.ptr(S), _hip.ptr(sums), _hip.ptr(workspace), self.B, self.K, ld, 1 if kind == "softplus" else 0,
                   1 if all_timesteps else 0, 1)
 
@@ -1241,7 +1368,13 @@ class CPCEngine(ContextHost):
         # gradient is issued later, inside the first side-stream block of the encoder's backward pass (no event of its own)
         ct, coff, cstride = self.ctx.c_operand()
 
+        A, s = self.A, self.s
+
         def dwp_call():
+            if A > 1:          # over the B A rows (b, a): dpred [B A][K E], c_a straight out of the hidden states
+                _hip.gemm_tn(_hip.ptr(self.dpred), _hip.ptr(ct, coff - (A - 1) * s * H), _hip.ptr(g["prediction_model.weight"]), B * A,
+                             K * E, H, K * E, s * H, H, code, b_rpi=A, b_item=cstride, flags=_hip.GEMM_OUT_F32)
+                return
             _hip.gemm_tn(_hip.ptr(self.dpred), _hip.ptr(ct, coff), _hip.ptr(g["prediction_model.weight"]), B, K * E, H,
                          K * E, H, H, code, b_rpi=1, b_item=cstride, flags=_hip.GEMM_OUT_F32)
         if self.use_aux and n > 1:
@@ -1250,14 +1383,22 @@ class CPCEngine(ContextHost):
             dwp_call()
         # (a B x H output with a K*E-long reduction: split the reduction over workgroups, sum the slabs in fixed order)
         ke = K * E
-        ksplit = ke // 256 if (ke % 256 == 0 and ke >= 1024 and self.slabs.numel() >= (ke // 256) * B * H) else 1
+        R = B * A              # rows of dc: one per (item, anchor)
+        dc_rows = self.dcA if A > 1 else self.dc
+        ksplit = ke // 256 if (ke % 256 == 0 and ke >= 1024 and self.slabs.numel() >= (ke // 256) * R * H) else 1
         if ksplit > 1:
-            _hip.gemm_nt(_hip.ptr(self.dpred), _hip.ptr(self.w_p_t), _hip.ptr(self.slabs), B, H, 256, ke, ke, H, code,
-                         a_batch=256, b_batch=256, c_batch=B * H, batch=ksplit, flags=_hip.GEMM_OUT_F32)
-            _hip.call("cpc_reduce_slabs", _hip.ptr(self.slabs), _hip.ptr(self.dc), B, H, ksplit, B * H, 1, 1, H, 0)
+            _hip.gemm_nt(_hip.ptr(self.dpred), _hip.ptr(self.w_p_t), _hip.ptr(self.slabs), R, H, 256, ke, ke, H, code,
+                         a_batch=256, b_batch=256, c_batch=R * H, batch=ksplit, flags=_hip.GEMM_OUT_F32)
+            _hip.call("cpc_reduce_slabs", _hip.ptr(self.slabs), _hip.ptr(dc_rows), R, H, ksplit, R * H, 1, 1, H, 0)
         else:
-            _hip.gemm_nt(_hip.ptr(self.dpred), _hip.ptr(self.w_p_t), _hip.ptr(self.dc), B, H, ke, ke, ke, H, code,
+            _hip.gemm_nt(_hip.ptr(self.dpred), _hip.ptr(self.w_p_t), _hip.ptr(dc_rows), R, H, ke, ke, ke, H, code,
                          flags=_hip.GEMM_OUT_F32)
+        if A > 1:
+            # the last anchor's row stays the f32 dc; the earlier anchors' rows go, rounded to the storage type, into the rows of the top
+            # recurrent layer's dHs they own (two strided copies; every other row of dHs stays zero)
+            rows = self.dcA.view(B, A, H)
+            self.dc.copy_(rows[:, A - 1, :])
+            self.ctx.anchor_dHs.view(B, V, H).index_copy_(1, self._anchor_steps, rows[:, :A - 1, :].to(self.dt))
         if add_dc is not None:
             self.dc.add_(add_dc)
         lanes_ok = self.use_aux and self.fuse_c1 and switches.wgrad_stream() and self._gp_phase == 0
@@ -1265,6 +1406,8 @@ class CPCEngine(ContextHost):
         if self._bl_active is not None:
             self._backward_target_rows(x, self._bl_active)
         self.ctx.backward(self.dc)      # parameter gradients of the context network + dz into rows [t0, t0+V) of dtop
+        if A > 1:          # the earlier anchors' target gradients below row T-K, added to the dz just written there
+            self._anchor_target_rows(T - K - (A - 1) * s, T - K, 1)
         if add_dz is not None:
             dtop.view(B, Ltop, E)[:, t0:t0 + V, :].add_(add_dz.transpose(1, 2), alpha=self.ctx.z_scale)
         self._backward_encoder(x, grad_ready_hook)
@@ -1279,7 +1422,11 @@ class CPCEngine(ContextHost):
         every layer above the first, the data gradient at positions >= n_(l-1) of layer l-1 depends on output-gradient rows >= n_l only
         (n_l as in _target_lane_rows): GEMM rows [n_l + 1, L_alloc) of every data gradient — the part of the backward pass behind the TARGET
         frames, whose top-layer gradient is final once the loss kernels are — run on the side stream beside the GRU's backward recurrence
-        (_backward_target_rows); the main stream's launches after the recurrence cover rows [0, n_l + 1).  The weight gradients stay
+        (_backward_target_rows); the main stream's launches after the recurrence cover rows [0, n_l + 1).
+        INVARIANT both target lanes rest on: rows >= T-K of the top-layer gradient are final before the context network's backward pass
+        is issued.  Prediction anchors keep it: the loss chain (or the autograd bridge) ends with the gather of every anchor's target
+        gradient into rows [T-K, T) (_anchor_target_rows, overwrite), and what the earlier anchors add lies below row T-K and is added
+        on the main stream behind the context network's dz (backward()), in front of the main lane's data gradients.  The weight gradients stay
         one launch per layer: split at row n_l the same way (two slab sets, one reduction) they cost the step 0.37 ms — the chip is full
         once the recurrence has ended, and the second slab set is pure extra traffic (round 4, A/B of this lane: 4.52 off, 4.49 on,
         4.89 with the weight gradients split).  Tried on top of this and removed again: the recurrence itself in two step
@@ -1484,6 +1631,9 @@ class CPCEngine(ContextHost):
         if kind == "normalized" and global_negatives is not None:
             raise NotImplementedError("normalized scores under global negatives are not on the HIP path: the trainer takes the generic "
                                       "route there (contrastive_estimation_training.NormalizedScoreFunction)")
+        if self.A > 1 and (all_timesteps or global_negatives is not None or negatives is not None or negative_groups is not None
+                           or negative_bank is not None or kind not in ("softplus", "linear")):
+            raise NotImplementedError(ANCHOR_LOSS_REASON)
         tkw = {} if temperature is None else {"temperature": temperature}
         self.forward(x)
         if global_negatives is not None:

@@ -25,7 +25,7 @@ import torch
 
 from . import _hip, switches
 from .contexts import Context, ContextHost, Float32Context, _ceil_div, make_context
-from .engine import CPCEngine, check_negative_bank_supported, check_negatives_supported, check_temperature, score_kind
+from .engine import CPCEngine, check_anchor_context, check_negative_bank_supported, check_negatives_supported, check_temperature, score_kind
 
 
 class Grid:
@@ -1325,6 +1325,7 @@ class ScalogramCPCEngine(CPCEngine):
         Wasserstein gradient penalty needs (loss_and_grads(..., gradient_penalty=factor))."""
         enc, ar = model.encoder, model.autoregressive_model
         B, Cin, Hin, Win = (int(v) for v in in_shape)
+        check_anchor_context(model, scalogram=True)          # prediction anchors: waveform engine only
         # (the waveform encoder's constructor, CPCEngine.__init__, does not apply: the shared part of the two is ContextHost's)
         ContextHost.__init__(self, model, device, dtype, B, model.enc_size, model.ar_size, model.prediction_steps, model.visible_steps)
         self.gp_capable = bool(gradient_penalty)

@@ -79,6 +79,9 @@ extern "C" {
  *    cpc_lstm_bwd (AudioLSTMModel).
  *    Added later under 9 (backward compatible, one entry point added, none changed): cpc_resample, downmix and rational resampling of
  *    audio files when a device-resident dataset is loaded.
+ *    Added later under 9 (backward compatible, entry points added, none changed): prediction anchors — cpc_lstm_bwd_steps, the LSTM
+ *    backward sweep with a gradient at every hidden state, and cpc_anchor_target_grad, the anchors' target-gradient windows summed
+ *    into the top-layer gradient.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -645,6 +648,33 @@ long long cpc_lstm_tape_elems(int B, int V, int H, int dtype);
 int cpc_lstm_fwd(const void* Gi, const void* Wfrag, const float* bhh, const float* h0, const float* c0, void* Hall, void* tape,
                  float* h_out, float* cell_out, int B, int V, int H, int dtype, void* stream);
 int cpc_lstm_bwd(const float* dh_last, const void* tape, const void* WTfrag, void* dG, int B, int V, int H, int dtype, void* stream);
+/* The same sweep with a gradient at EVERY hidden state (predictions from several context steps, "prediction anchors"): the LSTM
+ * counterpart of cpc_gru_bwd_steps, with its contract.
+ *   dHs      T   rows of H elements, row (b, t) at element (b V + t) ld_h: the gradient that reaches h_{t+1} = Hall[b][t+1] from
+ *                outside the recurrence.  ld_h >= H and a multiple of 8 (bf16) / 4 (f32) elements, the base 16-byte aligned; columns
+ *                [H, ld_h) and the rows of items >= B are never read.  NULL: the call IS cpc_lstm_bwd (same kernels, same bits;
+ *                dh_last is then required).
+ *   dh_last  f32 [B][H] the gradient at the last hidden state, or NULL = zeros; the last state receives dh_last + dHs[:, V-1].
+ * Step t starts from d = dh + dHs[b][t].  tape, WTfrag, dG and the supported H / dtype are cpc_lstm_bwd's.
+ * CPC_EINVAL before any launch: NULL tape / WTfrag / dG, dh_last and dHs both NULL, B < 1, V < 1, an H or dtype cpc_lstm_bwd refuses,
+ * a bad ld_h with dHs given.  (Added under ABI 9: no existing entry point changed.) */
+int cpc_lstm_bwd_steps(const float* dh_last, const void* dHs, long long ld_h, const void* tape, const void* WTfrag, void* dG, int B,
+                       int V, int H, int dtype, void* stream);
+
+/* Prediction anchors: the target-gradient windows of A anchors summed into the top-layer gradient.
+ *   dT    f32 [A][B][K][E]: d loss / d targets of every anchor; the window of anchor a covers top rows
+ *         [first_row + a stride, first_row + a stride + K)
+ *   dtop  T   row r of item b at element b item_stride + r E (item_stride a multiple of 8 (bf16) / 4 (f32) and >= row_hi E, the base
+ *         16-byte aligned)
+ * For every item and every row r in [row_lo, row_hi): dtop[b][r][:] = sum over the anchors a with 0 <= r - first_row - a stride < K of
+ * dT[a][b][r - first_row - a stride][:], in f32 with a ascending, plus the stored row when accumulate != 0, rounded once.  A row of the
+ * range that no window covers is written as zeros (accumulate == 0) or left alone (accumulate != 0).  Nothing outside [row_lo, row_hi)
+ * of the B items is touched.  A gather per output row: no atomics, the order of every sum fixed by the arguments.
+ * CPC_EINVAL before any launch: a NULL pointer; A, B or K < 1; stride < 1; E not a positive multiple of 8 (bf16) / 4 (f32); row_lo < 0,
+ * row_hi <= row_lo or first_row < 0; a bad item_stride; a dtype other than f32 / bf16.  (Added under ABI 9: no existing entry point
+ * changed.) */
+int cpc_anchor_target_grad(const float* dT, void* dtop, long long item_stride, int A, int B, int K, int E, int first_row, int stride,
+                           int row_lo, int row_hi, int accumulate, int dtype, void* stream);
 
 /* The Wasserstein gradient penalty through AudioGRUModel (contrastive_estimation_training.py:144-158: loss.backward() through
  * torch.autograd.grad(..., create_graph=True), here for the GRUCell loop of audio_model.py:66-77).  f32 only, H <= 512.

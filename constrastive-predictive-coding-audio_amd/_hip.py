@@ -240,6 +240,9 @@ _SIGNATURES = {
     "cpc_grid_mask": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, C.POINTER(CpcGridMask), _P], _I),
     "cpc_window_gather": ([_P, _I, _L, _P, _L, _P, _P, _I, _I, _L, _F, _P], _I),
     "cpc_resample": ([_P, _I, _L, _I, _I, _F, _P, _I, _I, _I, _P, _P, _I, _L, _P, _I, _L, _F, _P], _I),
+    "cpc_stream_gather": ([_P, _I, _L, _P, _P, _I, _I, _L, _F, _I, _L, _I, _P], _I),
+    "cpc_feature_emit": ([_P, _P, _L, _P, _L, _I, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _I, _P, _P, _P, _P], _I),
+    "cpc_stream_carry": ([_P, _P, _P, _I, _I, _I, _L, _I, _I, _L, _I, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -462,6 +462,16 @@ class DeviceAudioDataset(torch.utils.data.Dataset):
         out, idx_dev = self._gather(idx.contiguous())
         return (out, self._file_dev[idx_dev]) if self.labels else out
 
+    def file_ranges(self):
+        """[(first sample in the store, length)] of every file, in file order: where each recording lies, whatever item_length,
+        unique_length and cross_files are (feature_extraction.FeatureExtractor reads whole files)."""
+        first = 0
+        out = []
+        for n in self.file_lengths:
+            out.append((first, int(n)))
+            first += int(n)
+        return out
+
     def hbm_bytes(self):
         """Bytes this dataset holds in HBM: the samples and the two per-example tables."""
         if self.device is None:

@@ -364,6 +364,12 @@ class AudioPredictiveCodingModel(nn.Module):
         eng.encoder_forward(xin)
         return eng.view_top()[:, :eng.T, :].float().transpose(1, 2)
 
+    def extract_features(self, source, files=None, **kw):
+        """z and c of every frame of every recording of ``source`` (a DeviceAudioDataset with a device, or a sequence of 1-D arrays):
+        feature_extraction.FeatureExtractor(self, **kw).extract(source, files), the extractor kept per keyword set."""
+        from .feature_extraction import extract_features
+        return extract_features(self, source, files, **kw)
+
     def forward(self, x):
         """x (B, 1, L) -> (predicted_z (B,K,E), targets (B,E,K), z (B,E,V), c (B,H)), autograd-connected to the
         parameters (targets are not detached, as in the reference audio_model.py:197)."""

@@ -1544,6 +1544,13 @@ class ContrastiveEstimationTrainer:
         with self._ema_weights(use_ema):
             return self._calc_test_task_data(batch_size, num_workers)
 
+    def extract_features(self, source, use_ema=False, **kw):
+        """model.extract_features(source, **kw): z and c of every frame of every recording; use_ema=True: from the averaged weights,
+        which take the model's place for the call as in validate() (the raw weights are back afterwards, bit for bit; ValueError
+        when no average exists)."""
+        with self._ema_weights(use_ema):
+            return self.model.extract_features(source, **kw)
+
     def _calc_test_task_data(self, batch_size=64, num_workers=1):
         if self.test_task_set is None:
             print("No test task set")

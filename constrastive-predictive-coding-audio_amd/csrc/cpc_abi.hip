@@ -976,6 +976,59 @@ int cpc_resample(const void* src, int src_code, long long src_frames_total, int 
                            dst_total, out_scale, (hipStream_t)stream);
 }
 
+// (the extents every table row of the feature-extraction calls is checked against)
+static bool stream_extents_ok(long long store_len, int L, int Tc, long long total_frames, int n_rec) {
+    return store_len >= 1 && L >= 1 && L <= (1 << 24) && Tc >= 1 && total_frames >= 0 && n_rec >= 1;
+}
+static bool aligned_to(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
+int cpc_stream_gather(const void* store, int store_code, long long store_len, const long long* table, float* out, int R, int L,
+                      long long ldo, float scale, int Tc, long long total_frames, int n_rec, void* stream) {
+    if (!store || !table || !out || R < 1 || R > 65535 || !stream_extents_ok(store_len, L, Tc, total_frames, n_rec) || ldo < L)
+        return CPC_EINVAL;
+    if ((store_code != 0 && store_code != 1) || !std::isfinite(scale)) return CPC_EINVAL;
+    if (!aligned_to(store, store_code == 1 ? 2 : 4) || !aligned_to(out, 4) || !aligned_to(table, 8)) return CPC_EINVAL;
+    const StreamExtents ext = {store_len, total_frames, L, Tc, n_rec};
+    return launch_stream_gather(store, store_code, table, ext, out, R, ldo, scale, (hipStream_t)stream);
+}
+
+int cpc_feature_emit(const long long* table, const void* top, long long top_item, const void* hall, long long hall_item, int src_dtype,
+                     void* z_out, void* c_out, int out_dtype, int R, int Tc, int E, int H, long long store_len, int L,
+                     long long total_frames, int n_rec, double* partial, double* acc_z, double* acc_c, void* stream) {
+    if (!table || (!z_out && !c_out) || (z_out && !top) || (c_out && !hall)) return CPC_EINVAL;
+    if ((src_dtype != CPC_DTYPE_F32 && src_dtype != CPC_DTYPE_BF16) || (out_dtype != CPC_DTYPE_F32 && out_dtype != CPC_DTYPE_BF16))
+        return CPC_EINVAL;
+    if (R < 1 || R > 65535 || !stream_extents_ok(store_len, L, Tc, total_frames, n_rec) || Tc > (1 << 20)) return CPC_EINVAL;
+    const int ch = src_dtype == CPC_DTYPE_BF16 ? 8 : 4;
+    if (E < 0 || H < 0 || E % ch || H % ch || E > 65536 || H > 65536) return CPC_EINVAL;
+    if (z_out && (E < ch || top_item < (long long)Tc * E || top_item % ch || !aligned_to(top, 16) || !aligned_to(z_out, 16)))
+        return CPC_EINVAL;
+    if (c_out && (H < ch || hall_item < ((long long)Tc + 1) * H || hall_item % ch || !aligned_to(hall, 16) || !aligned_to(c_out, 16)))
+        return CPC_EINVAL;
+    if (partial) {
+        if (!aligned_to(partial, 16) || (z_out && (!acc_z || !aligned_to(acc_z, 8))) || (c_out && (!acc_c || !aligned_to(acc_c, 8))))
+            return CPC_EINVAL;
+    }
+    if (!aligned_to(table, 8)) return CPC_EINVAL;
+    const StreamExtents ext = {store_len, total_frames, L, Tc, n_rec};
+    return launch_feature_emit(table, ext, top, top_item, hall, hall_item, src_dtype, z_out, c_out, out_dtype, R, E, H, partial, acc_z,
+                               acc_c, (hipStream_t)stream);
+}
+
+int cpc_stream_carry(const long long* table, const float* const* src, float* const* dst, int nstate, int R, int H, long long store_len,
+                     int L, int Tc, long long total_frames, int n_rec, void* stream) {
+    if (!table || !src || !dst || nstate < 1 || nstate > CPC_STREAM_MAX_STATES) return CPC_EINVAL;
+    if (R < 1 || R > 65535 || H < 4 || H > 65536 || H % 4 || !stream_extents_ok(store_len, L, Tc, total_frames, n_rec)) return CPC_EINVAL;
+    if (!aligned_to(table, 8)) return CPC_EINVAL;
+    for (int i = 0; i < nstate; ++i) {
+        if (!src[i] || !dst[i] || !aligned_to(src[i], 16) || !aligned_to(dst[i], 16)) return CPC_EINVAL;
+        for (int j = 0; j < nstate; ++j)
+            if (dst[i] == src[j]) return CPC_EINVAL;
+    }
+    const StreamExtents ext = {store_len, total_frames, L, Tc, n_rec};
+    return launch_stream_carry(table, ext, src, dst, nstate, R, H, (hipStream_t)stream);
+}
+
 int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
 
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {

@@ -241,6 +241,19 @@ int launch_wave_augment(const float* x, float* y, const float* partial, float* p
 // Device-resident dataset (dataset.hip): a batch of windows cut from the concatenated samples; arguments checked by the entry point.
 int launch_window_gather(const void* store, int store_code, long long store_len, const long long* starts, long long n_items,
                          const long long* idx, float* out, int B, int L, long long ldo, float scale, hipStream_t stream);
+// Whole-recording feature extraction (stream.hip): the extents a table row is checked against, and the three launches; arguments
+// checked by the entry points.
+struct StreamExtents {
+    long long store_len, total_frames;
+    int L, Tc, n_rec;
+};
+int launch_stream_gather(const void* store, int store_code, const long long* table, const StreamExtents& ext, float* out, int R,
+                         long long ldo, float scale, hipStream_t stream);
+int launch_feature_emit(const long long* table, const StreamExtents& ext, const void* top, long long top_item, const void* hall,
+                        long long hall_item, int src_dtype, void* z_out, void* c_out, int out_dtype, int R, int E, int H, double* partial,
+                        double* acc_z, double* acc_c, hipStream_t stream);
+int launch_stream_carry(const long long* table, const StreamExtents& ext, const float* const* src, float* const* dst, int nstate, int R,
+                        int H, hipStream_t stream);
 // Load-time conversion (resample.hip): downmix, polyphase resampling and the store for a list of segments; arguments checked by the
 // entry point.  resample_span_floats: the LDS floats a tile's input span can need.
 long long resample_span_floats(int L, int M, int W);

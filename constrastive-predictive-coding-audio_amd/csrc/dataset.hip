@@ -9,26 +9,10 @@
 #include "cpc_common.h"
 #include "cpc_draws.h"
 #include "cpc_kernels.h"
+#include "cpc_pieces.h"
 #include "../../include/cpc_hip.h"
 
 namespace {
-
-constexpr int WG_PIECE = 4;                           // outputs per piece: one 16-byte store
-
-// Four consecutive samples from an address aligned to one sample only.
-template <typename T> struct WgPiece { T v[WG_PIECE]; };
-template <typename T>
-__device__ __forceinline__ WgPiece<T> wg_load(const T* src) {
-    WgPiece<T> p;
-    __builtin_memcpy(&p, src, sizeof(p));
-    return p;
-}
-
-// COPY: the f32 store with scale 1, moved bit for bit (a multiplication by 1 would quiet a signalling NaN).
-template <typename T, bool COPY>
-__device__ __forceinline__ float wg_value(T s, float scale) {
-    return COPY ? (float)s : (float)s * scale;
-}
 
 // Workgroup (blockIdx.x, blockIdx.y): outputs [tile blockIdx.x, +tile) of row blockIdx.y, tile = 4 ITERS blockDim.x; a lane ITERS pieces
 // of 4, blockDim.x pieces apart.  The row reads the store only where its whole window [s, s + L) lies inside it, and is zeros otherwise.

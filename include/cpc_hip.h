@@ -82,6 +82,8 @@ extern "C" {
  *    Added later under 9 (backward compatible, entry points added, none changed): prediction anchors — cpc_lstm_bwd_steps, the LSTM
  *    backward sweep with a gradient at every hidden state, and cpc_anchor_target_grad, the anchors' target-gradient windows summed
  *    into the top-layer gradient.
+ *    Added later under 9 (backward compatible, entry points added, none changed): whole-recording feature extraction —
+ *    cpc_stream_gather, cpc_feature_emit, cpc_stream_carry.
  * 8 (round 4): the fused all-timesteps score path (cpc_score_lse, cpc_nce_lse_merge, cpc_nce_fused_grad(_blocks), cpc_nce_fused_finalize); cpc_reduce_conv_w2d; cpc_accumulate; the row-range launches cpc_conv1_fwd_rows, cpc_conv_dgrad_rows, cpc_conv_dgrad_conv1_rows, cpc_conv1_fused_reduce_tiles.
  * 7 (round 3, second half): cpc_gemm_nt_args grew the second row level (a_rpi2 / c_rpi2), k_ranges and the gathered-row taps (k_taps,
  * k_tap_stride, k_tap_stride_a); new entry points cpc_conv_w_prep_group / _plan / _batch, cpc_bn_apply_residual, cpc_bn_bwd_reduce_res / _apply_res, cpc_stem_residual_bn_add,
@@ -1255,6 +1257,74 @@ int cpc_window_gather(const void* store, int store_code, long long store_len, co
 int cpc_resample(const void* src, int src_code, long long src_frames_total, int C, int mix, float in_scale, const float* taps, int L,
                  int M, int W, const long long* segs, const long long* tile_first, int nseg, long long ntiles, void* dst, int dst_code,
                  long long dst_total, float out_scale, void* stream);
+
+/* ---- Whole-recording feature extraction: z and c of every frame of every recording, in chunks (csrc/stream.hip; DESIGN.md,
+ * "Whole-recording feature extraction").  R recordings ("streams") advance side by side, Tc frames per step.  The host lays out every
+ * step up front as an int64 table [n_steps][R][6] on the device; each of the three calls of step j is given block j, `table`, whose
+ * row r says what stream r does in that step:
+ *     [0] first_sample   first sample of the step's window in the store
+ *     [1] n_samples      samples of the window, (n_frames - 1) downsampling + receptive field, or 0
+ *     [2] n_frames       frames the step makes for the recording, at most Tc
+ *     [3] out_row        row of the feature stores that takes the first of them
+ *     [4] rec            the recording, 0 <= rec < n_rec, or -1: an idle row
+ *     [5] keep           1: the stream's next step continues this recording
+ * GUARD (all three calls; the extents are arguments of each): a row with rec outside [0, n_rec), n_samples outside [0, L], a window
+ * [first_sample, + n_samples) that is not inside [0, store_len], n_frames outside [0, Tc] or rows [out_row, + n_frames) that are not
+ * inside [0, total_frames] is treated as idle: nothing of it is read, nothing is written for it beyond what an idle row gets (zeros
+ * from cpc_stream_gather and cpc_stream_carry, nothing from cpc_feature_emit).  No address outside the stated extents is formed.
+ * Callers build right tables; the guard keeps a wrong one from becoming a fault.  One thing the guard cannot see is left to the
+ * caller: within one block no two rows name the same recording (cpc_feature_emit's accumulators are added to without atomics).
+ *
+ * cpc_stream_gather: out[r ldo + t] = scale * float(store[first_sample + t]) for t < n_samples, exact zeros for n_samples <= t < L;
+ *   an idle row is L zeros.  store, store_code, scale, the unaligned source / aligned destination access and the bit-exactness rules
+ *   (an f32 store with scale == 1.0f is copied bit for bit; int16 times 1 / 32768 is exact) are cpc_window_gather's.  Nothing is
+ *   written between the rows or behind the last one.
+ *   CPC_EINVAL before any launch: store, table or out NULL, R outside [1, 65535], L outside [1, 2^24], ldo < L, store_len < 1,
+ *   Tc < 1, total_frames < 0, n_rec < 1, store_code outside {0, 1}, scale not finite, store not aligned to its element size, out
+ *   not 4-byte aligned, table not 8-byte aligned.
+ *
+ * cpc_feature_emit: for every row that is not idle and every t < n_frames
+ *     z_out[(out_row + t) E + e] = (U) top [r top_item  + t E + e]          e < E   (the encoder's top rows of the stream)
+ *     c_out[(out_row + t) H + h] = (U) hall[r hall_item + (t + 1) H + h]    h < H   (row 0 of a stream's hidden states is the state
+ *                                                                                    the step started from, row t + 1 the one after frame t)
+ *   top, hall: the storage type src_dtype; z_out, c_out: out_dtype (CPC_F32 / CPC_BF16).  Equal types are copied bit for bit, f32 to
+ *   bf16 rounds to nearest even, bf16 to f32 is exact.  z_out or c_out may be NULL: that kind is then neither read nor written (top /
+ *   hall may be NULL with it).  Nothing but those rows is written.
+ *   Pooling (partial != NULL): acc_z f64 [n_rec][2][E] and acc_c f64 [n_rec][2][H] (required for the kinds given) gain, for the row's
+ *   recording and every channel, the sum (row 0) and the sum of squares (row 1) over the step's frames of the source values widened
+ *   to f32.  partial: f64 scratch of R ceil(Tc / CPC_EMIT_FRAMES) 2 (E + H) elements, rewritten by every call.  A first launch leaves
+ *   per (stream, block of CPC_EMIT_FRAMES frames, channel) the sums taken in frame order; a second adds the blocks of a stream to
+ *   the accumulators in block order.  Every addition is in f64 and every square is exact (an f32 value squared has 48 bits): squares
+ *   rounded to f32 would cost sqrt(E[x^2] - mean^2) half its digits.  No atomics: the order of every sum is fixed by the arguments, so a call sequence gives
+ *   the same bits every time.  The caller zeroes the accumulators before the first step and turns them into mean and deviation after
+ *   the last.
+ *   Access: grid row r is stream r; a lane moves 16 bytes of a source row (4 f32 / 8 bf16 channels), neighbouring lanes neighbouring
+ *   pieces, and walks the CPC_EMIT_FRAMES frames of its block.
+ *   CPC_EINVAL before any launch: table NULL, z_out and c_out both NULL, z_out without top or c_out without hall, src_dtype or
+ *   out_dtype outside {CPC_F32, CPC_BF16}, R outside [1, 65535], Tc outside [1, 2^20], E (with z_out) or H (with c_out) outside
+ *   [ch, 65536] or, given at all, negative or no multiple of ch = 4 (f32) / 8 (bf16) source elements, top_item < Tc E or hall_item <
+ *   (Tc + 1) H or either no multiple of ch, L outside [1, 2^24], store_len < 1, total_frames < 0, n_rec < 1, a pointer of top, hall,
+ *   z_out, c_out or partial that is not 16-byte aligned, an accumulator that is missing with partial or not 8-byte aligned, table
+ *   not 8-byte aligned.
+ *
+ * cpc_stream_carry: dst[i][r H + h] = keep(r) ? src[i][r H + h] : 0 for i < nstate state arrays f32 [R][H] (a GRU's c_out of every
+ *   layer; an LSTM's h_out and cell_out), keep(r) = row r is not idle and its entry [5] is 1.  src, dst: HOST arrays of nstate device
+ *   pointers, read by the call.  dst is the next step's h0 / c0 and never a buffer the recurrence writes; this is the only place
+ *   where a stream's state is reset: the state a recording's last, short chunk leaves behind, computed on zero-filled samples, goes
+ *   no further.
+ *   CPC_EINVAL before any launch: table, src or dst NULL, nstate outside [1, CPC_STREAM_MAX_STATES], an array pointer NULL or not
+ *   16-byte aligned, a dst that is also a src, R outside [1, 65535], H outside [4, 65536] or no multiple of 4, L outside [1, 2^24],
+ *   store_len < 1, Tc < 1, total_frames < 0, n_rec < 1, table not 8-byte aligned.
+ * The calls never throw, allocate or synchronise.  stream is a hipStream_t.  (Added under ABI 9: no existing entry point changed.) */
+#define CPC_EMIT_FRAMES 32
+#define CPC_STREAM_MAX_STATES 8
+int cpc_stream_gather(const void* store, int store_code, long long store_len, const long long* table, float* out, int R, int L,
+                      long long ldo, float scale, int Tc, long long total_frames, int n_rec, void* stream);
+int cpc_feature_emit(const long long* table, const void* top, long long top_item, const void* hall, long long hall_item, int src_dtype,
+                     void* z_out, void* c_out, int out_dtype, int R, int Tc, int E, int H, long long store_len, int L,
+                     long long total_frames, int n_rec, double* partial, double* acc_z, double* acc_c, void* stream);
+int cpc_stream_carry(const long long* table, const float* const* src, float* const* dst, int nstate, int R, int H, long long store_len,
+                     int L, int Tc, long long total_frames, int n_rec, void* stream);
 
 #ifdef __cplusplus
 }

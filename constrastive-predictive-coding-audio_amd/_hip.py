@@ -243,6 +243,10 @@ _SIGNATURES = {
     "cpc_stream_gather": ([_P, _I, _L, _P, _P, _I, _I, _L, _F, _I, _L, _I, _P], _I),
     "cpc_feature_emit": ([_P, _P, _L, _P, _L, _I, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _I, _P, _P, _P, _P], _I),
     "cpc_stream_carry": ([_P, _P, _P, _I, _I, _I, _L, _I, _I, _L, _I, _P], _I),
+    "cpc_kmeans_assign": ([_P, _I, _L, _I, _L, _P, _P, _I, _P, _P, _P], _I),
+    "cpc_kmeans_scratch_bytes": ([_L, _I, _I], _L),
+    "cpc_kmeans_update": ([_P, _I, _L, _I, _L, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P], _I),
+    "cpc_kmeans_cnorm": ([_P, _P, _I, _I, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1029,6 +1029,46 @@ int cpc_stream_carry(const long long* table, const float* const* src, float* con
     return launch_stream_carry(table, ext, src, dst, nstate, R, H, (hipStream_t)stream);
 }
 
+// (the shape limits the three k-means calls share)
+static bool kmeans_shape_ok(const void* x, int dtype, long long N, int D, long long ldx, int K) {
+    if (!x || (dtype != CPC_DTYPE_F32 && dtype != CPC_DTYPE_BF16)) return false;
+    if (N < 1 || N > 0x7FFFFFFFll || D < 16 || D > 512 || D % 16 || K < 2 || K > 1024) return false;
+    const int ch = dtype == CPC_DTYPE_BF16 ? 8 : 4;
+    return ldx >= D && ldx % ch == 0 && aligned_to(x, 16);
+}
+
+int cpc_kmeans_assign(const void* x, int dtype, long long N, int D, long long ldx, const float* centers, const float* cnorm, int K,
+                      int* labels, float* dist, void* stream) {
+    if (!kmeans_shape_ok(x, dtype, N, D, ldx, K) || !centers || !cnorm || !labels) return CPC_EINVAL;
+    if (!aligned_to(centers, 16) || !aligned_to(cnorm, 4) || !aligned_to(labels, 4) || !aligned_to(dist, 4)) return CPC_EINVAL;
+    return launch_kmeans_assign(x, dtype, N, D, ldx, centers, cnorm, K, labels, dist, (hipStream_t)stream);
+}
+
+long long cpc_kmeans_scratch_bytes(long long N, int K, int D) {
+    if (N < 1 || N > 0x7FFFFFFFll || D < 16 || D > 512 || D % 16 || K < 2 || K > 1024) return CPC_EINVAL;
+    return kmeans_scratch_bytes(N, K, D);
+}
+
+int cpc_kmeans_update(const void* x, int dtype, long long N, int D, long long ldx, const int* labels, const float* dist,
+                      const float* centers_old, int K, void* scratch, long long scratch_bytes, float* centers_new, float* cnorm,
+                      int* counts, double* inertia, void* stream) {
+    if (!kmeans_shape_ok(x, dtype, N, D, ldx, K) || !labels || !centers_old || !scratch || !centers_new || !cnorm || !counts)
+        return CPC_EINVAL;
+    if ((dist == nullptr) != (inertia == nullptr)) return CPC_EINVAL;
+    if (scratch_bytes < kmeans_scratch_bytes(N, K, D) || !aligned_to(scratch, 16)) return CPC_EINVAL;
+    if (!aligned_to(labels, 4) || !aligned_to(dist, 4) || !aligned_to(centers_old, 4) || !aligned_to(centers_new, 4) ||
+        !aligned_to(cnorm, 4) || !aligned_to(counts, 4) || !aligned_to(inertia, 8))
+        return CPC_EINVAL;
+    return launch_kmeans_update(x, dtype, N, D, ldx, labels, dist, centers_old, K, scratch, centers_new, cnorm, counts, inertia,
+                                (hipStream_t)stream);
+}
+
+int cpc_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, void* stream) {
+    if (!centers || !cnorm || D < 16 || D > 512 || D % 16 || K < 2 || K > 1024) return CPC_EINVAL;
+    if (!aligned_to(centers, 4) || !aligned_to(cnorm, 4)) return CPC_EINVAL;
+    return launch_kmeans_cnorm(centers, cnorm, K, D, (hipStream_t)stream);
+}
+
 int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
 
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {

@@ -254,6 +254,15 @@ int launch_feature_emit(const long long* table, const StreamExtents& ext, const 
                         double* acc_z, double* acc_c, hipStream_t stream);
 int launch_stream_carry(const long long* table, const StreamExtents& ext, const float* const* src, float* const* dst, int nstate, int R,
                         int H, hipStream_t stream);
+// K-means over feature rows (kmeans.hip): the fused distance / argmin pass, the sorted update and the centre norms; arguments checked
+// by the entry points.  kmeans_scratch_bytes: what the update's sort and partial sums need for (N, K, D).
+long long kmeans_scratch_bytes(long long N, int K, int D);
+int launch_kmeans_assign(const void* x, int dtype, long long N, int D, long long ldx, const float* centers, const float* cnorm, int K,
+                         int* labels, float* dist, hipStream_t stream);
+int launch_kmeans_update(const void* x, int dtype, long long N, int D, long long ldx, const int* labels, const float* dist,
+                         const float* centers_old, int K, void* scratch, float* centers_new, float* cnorm, int* counts, double* inertia,
+                         hipStream_t stream);
+int launch_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, hipStream_t stream);
 // Load-time conversion (resample.hip): downmix, polyphase resampling and the store for a list of segments; arguments checked by the
 // entry point.  resample_span_floats: the LDS floats a tile's input span can need.
 long long resample_span_floats(int L, int M, int W);

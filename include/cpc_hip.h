@@ -1326,6 +1326,46 @@ int cpc_feature_emit(const long long* table, const void* top, long long top_item
 int cpc_stream_carry(const long long* table, const float* const* src, float* const* dst, int nstate, int R, int H, long long store_len,
                      int L, int Tc, long long total_frames, int n_rec, void* stream);
 
+/* ---- K-means units over feature rows (csrc/kmeans.hip; DESIGN.md, "K-means units").  x: N rows of D values of the storage type
+ * dtype (CPC_F32 / CPC_BF16) at a row stride of ldx >= D elements; centers f32 [K][D]; cnorm f32 [K], the squared norms of the centres.
+ * Shared limits, CPC_EINVAL before any launch otherwise: x NULL or not 16-byte aligned, dtype outside {CPC_F32, CPC_BF16}, N outside
+ * [1, 2^31 - 1], D outside [16, 512] or no multiple of 16, K outside [2, 1024], ldx < D or no multiple of 4 (f32) / 8 (bf16) elements
+ * (rows are read 16 bytes at a time).  Offsets that grow with N ldx are 64-bit.
+ *
+ * cpc_kmeans_assign: labels[n] = the k with the smallest v(n, k) = cnorm[k] - 2 x_n . c_k, the lowest such k where several compare
+ *   equal as the kernel computes them; dist[n] = max(v(n, labels[n]) + |x_n|^2, 0) with |x_n|^2 computed by the kernel; dist may be
+ *   NULL and is then not written.  All arithmetic is f32: bf16 rows are widened (exact), centres are never rounded, x_n . c_k is an
+ *   f32-input MFMA chain (one rounding per product, as an fmaf chain in a fixed order of the columns), v one more fmaf.  A row
+ *   holding a NaN or an infinity gets the label -1 and the distance NaN; no other row is touched by it.  The N x K values v exist in
+ *   registers only: the call writes the N labels and, if asked, the N distances, nothing else.
+ *   CPC_EINVAL also for centers, cnorm or labels NULL, centers not 16-byte aligned, cnorm, labels or dist not 4-byte aligned.
+ *
+ * cpc_kmeans_update: from x, labels int32 [N] and the old centres,
+ *     counts[k]        int32, the rows with label k
+ *     centers_new[k]   f32 [D], their mean (an f64 sum rounded once), or centers_old[k] bit for bit where counts[k] == 0
+ *     cnorm[k]         f32, |centers_new[k]|^2 (an f64 sum of exact squares, rounded once; cpc_kmeans_cnorm gives the same bits)
+ *     *inertia         f64, the sum of dist[n] over the rows with a label in [0, K)      (dist and inertia: both given or both NULL)
+ *   A label outside [0, K), -1 included, is skipped: no address is formed from it.  centers_new may be centers_old itself.
+ *   Determinism: the rows are sorted by label with a stable counting sort (integer atomics in LDS for the histograms only), each
+ *   cluster's rows are summed in pieces of a fixed length and the pieces are added in order; every floating-point sum is f64 and its
+ *   order is fixed by (N, K, D) and the labels.  Two calls on the same inputs give the same bits.
+ *   scratch: cpc_kmeans_scratch_bytes(N, K, D) bytes, 16-byte aligned, rewritten by every call.
+ *   CPC_EINVAL also for labels, centers_old, scratch, centers_new, cnorm or counts NULL, one of dist / inertia without the other,
+ *   scratch_bytes below cpc_kmeans_scratch_bytes(N, K, D), scratch not 16-byte aligned, inertia not 8-byte aligned, another pointer
+ *   not 4-byte aligned.
+ *
+ * cpc_kmeans_scratch_bytes: the scratch size for (N, K, D), or CPC_EINVAL for a shape outside the limits above.
+ * cpc_kmeans_cnorm: cnorm[k] = |centers[k]|^2 as cpc_kmeans_update computes it (for an initial codebook).  CPC_EINVAL for a NULL or
+ *   misaligned pointer, D or K outside the limits.
+ * The calls never throw, allocate or synchronise.  stream is a hipStream_t.  (Added under ABI 9: no existing entry point changed.) */
+int cpc_kmeans_assign(const void* x, int dtype, long long N, int D, long long ldx, const float* centers, const float* cnorm, int K,
+                      int* labels, float* dist, void* stream);
+long long cpc_kmeans_scratch_bytes(long long N, int K, int D);
+int cpc_kmeans_update(const void* x, int dtype, long long N, int D, long long ldx, const int* labels, const float* dist,
+                      const float* centers_old, int K, void* scratch, long long scratch_bytes, float* centers_new, float* cnorm,
+                      int* counts, double* inertia, void* stream);
+int cpc_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,9 @@ _SIGNATURES = {
     "cpc_kmeans_scratch_bytes": ([_L, _I, _I], _L),
     "cpc_kmeans_update": ([_P, _I, _L, _I, _L, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P], _I),
     "cpc_kmeans_cnorm": ([_P, _P, _I, _I, _P], _I),
+    "cpc_frame_distance": ([_P, _I, _L, _I, _L, _L, _I, _L, _I, _I, _P, _L, _P], _I),
+    "cpc_dtw": ([_P, _I, _L, _I, _L, _P, _L, _I, _P, _P, _P, _P], _I),
+    "cpc_abx_count": ([_P, _L, _P, _L, _P, _P], _I),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

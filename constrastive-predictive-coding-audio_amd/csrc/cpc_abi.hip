@@ -1069,6 +1069,32 @@ int cpc_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, void* str
     return launch_kmeans_cnorm(centers, cnorm, K, D, (hipStream_t)stream);
 }
 
+// (the store limits the frame-distance and DTW calls share with the k-means calls, and the metric)
+static bool dtw_store_ok(const void* x, int dtype, long long N, int D, long long ldx, int metric) {
+    return kmeans_shape_ok(x, dtype, N, D, ldx, 2) && metric >= 0 && metric <= 2;
+}
+
+int cpc_frame_distance(const void* x, int dtype, long long N, int D, long long ldx, long long a_first, int La, long long b_first, int Lb,
+                       int metric, float* out, long long ldo, void* stream) {
+    if (!dtw_store_ok(x, dtype, N, D, ldx, metric) || !out || !aligned_to(out, 4)) return CPC_EINVAL;
+    if (La < 1 || La > 128 || Lb < 1 || Lb > 128 || a_first < 0 || a_first > N - La || b_first < 0 || b_first > N - Lb || ldo < Lb)
+        return CPC_EINVAL;
+    return launch_frame_distance(x, dtype, D, ldx, a_first, La, b_first, Lb, metric, out, ldo, (hipStream_t)stream);
+}
+
+int cpc_dtw(const void* x, int dtype, long long N, int D, long long ldx, const long long* pairs, long long P, int metric, float* dist,
+            float* cost, int* path_len, void* stream) {
+    if (!dtw_store_ok(x, dtype, N, D, ldx, metric) || !pairs || !dist || P < 1 || P > 0x7FFFFFFFll) return CPC_EINVAL;
+    if (!aligned_to(pairs, 8) || !aligned_to(dist, 4) || !aligned_to(cost, 4) || !aligned_to(path_len, 4)) return CPC_EINVAL;
+    return launch_dtw(x, dtype, N, D, ldx, pairs, P, metric, dist, cost, path_len, (hipStream_t)stream);
+}
+
+int cpc_abx_count(const float* dist, long long n_dist, const long long* tasks, long long T, long long* out, void* stream) {
+    if (!dist || !tasks || !out || n_dist < 1 || T < 1 || T > 0x7FFFFFFFll) return CPC_EINVAL;
+    if (!aligned_to(dist, 4) || !aligned_to(tasks, 8) || !aligned_to(out, 8)) return CPC_EINVAL;
+    return launch_abx_count(dist, n_dist, tasks, T, out, (hipStream_t)stream);
+}
+
 int cpc_grid_sum_chunks(int n) { return grid_sum_chunks(n); }
 
 int cpc_grid_sum(const float* x, float* partial, int B, int n, long long ldb, int Cc, void* stream) {

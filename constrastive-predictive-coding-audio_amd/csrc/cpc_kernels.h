@@ -263,6 +263,13 @@ int launch_kmeans_update(const void* x, int dtype, long long N, int D, long long
                          const float* centers_old, int K, void* scratch, float* centers_new, float* cnorm, int* counts, double* inertia,
                          hipStream_t stream);
 int launch_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, hipStream_t stream);
+// ABX discriminability (dtw.hip): the frame distances of one pair of segments, the batched DTW over a pair table and the triple counts
+// over a task table; arguments checked by the entry points (the table rows by the kernels).
+int launch_frame_distance(const void* x, int dtype, int D, long long ldx, long long a_first, int La, long long b_first, int Lb, int metric,
+                          float* out, long long ldo, hipStream_t stream);
+int launch_dtw(const void* x, int dtype, long long N, int D, long long ldx, const long long* pairs, long long P, int metric, float* dist,
+               float* cost, int* path_len, hipStream_t stream);
+int launch_abx_count(const float* dist, long long n_dist, const long long* tasks, long long T, long long* out, hipStream_t stream);
 // Load-time conversion (resample.hip): downmix, polyphase resampling and the store for a list of segments; arguments checked by the
 // entry point.  resample_span_floats: the LDS floats a tile's input span can need.
 long long resample_span_floats(int L, int M, int W);

@@ -1366,6 +1366,59 @@ int cpc_kmeans_update(const void* x, int dtype, long long N, int D, long long ld
                       int* counts, double* inertia, void* stream);
 int cpc_kmeans_cnorm(const float* centers, float* cnorm, int K, int D, void* stream);
 
+/* ---- ABX discriminability: frame distances, batched DTW and the triple count (csrc/dtw.hip; DESIGN.md, "ABX discriminability").
+ * x is the feature store as the k-means calls take it: N rows of D values of the storage type dtype at a row stride of ldx >= D
+ * elements.  Shared limits, CPC_EINVAL before any launch otherwise: x NULL or not 16-byte aligned, dtype outside {CPC_F32, CPC_BF16},
+ * N outside [1, 2^31 - 1], D outside [16, 512] or no multiple of 16, ldx < D or no multiple of 4 (f32) / 8 (bf16) elements, metric
+ * outside {0, 1, 2}.  Offsets that grow with N ldx or with P are 64-bit.
+ *
+ * The frame distance of two rows a, b.  All arithmetic is f32, bf16 rows are widened (exact).  dot = a . b is an f32-input MFMA chain:
+ * an fmaf chain, one rounding per product, over the columns in the order (8 s + e, 8 s + 4 + e) for s = 0 .. D/8 - 1, e = 0 .. 3.
+ * |a|^2 (and |b|^2) = S0 + S1, S0 the fmaf chain over the columns 8 s + e and S1 the one over the columns 8 s + 4 + e, in ascending
+ * order each.  None of these orders depends on where the rows sit in a tile, on La, Lb or P.
+ *     metric 0 (angular)            acosf(cos) / (float)pi          cos = clamp(dot / (sqrtf(|a|^2) sqrtf(|b|^2)), -1, 1)
+ *     metric 1 (cosine)             1 - cos
+ *     metric 2 (squared Euclidean)  max(fmaf(-2, dot, |a|^2 + |b|^2), 0)
+ * cpc_dtw uses, for every cell, exactly the bits cpc_frame_distance writes for the same two rows: one device function forms both.
+ *
+ * cpc_frame_distance: out[i * ldo + j] (f32) = the distance of row a_first + i to row b_first + j, 0 <= i < La, 0 <= j < Lb.
+ *   It is there for inspection and applies no rule for bad rows: where a row holds a NaN or an infinity, overflows its squared norm or
+ *   (metrics 0 and 1) has the norm 0, the cells of that row hold whatever the f32 arithmetic above gives (a NaN from 0 / 0, a clamped
+ *   value), and cpc_dtw does not use them.  CPC_EINVAL also for La or Lb outside [1, 128], a segment outside [0, N), out NULL or not
+ *   4-byte aligned, ldo < Lb.
+ *
+ * cpc_dtw: pairs int64 [P][4] = (a_first, La, b_first, Lb) on the device; with d[i][j] the frame distance of row a_first + i to row
+ *   b_first + j,
+ *     C[0][0] = d[0][0],  C[i][0] = d[i][0] + C[i-1][0],  C[0][j] = d[0][j] + C[0][j-1],
+ *     C[i][j] = d[i][j] + min(C[i-1][j], C[i-1][j-1], C[i][j-1])                              every + one f32 addition;
+ *   the predecessor of an inner cell is the diagonal one if it is <= both others, else the left one (i, j-1) if it is <= the upper
+ *   one, else the upper one; len[0][j] = j + 1, len[i][0] = i + 1, len[i][j] = len[predecessor] + 1 (the length of the path a
+ *   backtrack from the last cell with the same preference walks).  Per pair p: cost[p] = C[La-1][Lb-1], path_len[p] = len[La-1][Lb-1]
+ *   (int32), dist[p] = cost / (float)path_len, one correctly rounded f32 division.  cost and path_len may be NULL and are then not
+ *   written.  A pair one of whose rows holds a NaN or an infinity, or (metrics 0 and 1) has the squared norm 0 as computed, gets
+ *   dist = cost = NaN and path_len = -1.  A finite row whose squared norm as computed is above 2^116 (an infinity included) counts
+ *   as non-finite: below that every distance and every sum along a path of 255 cells is finite.  The same result goes to a pair whose
+ *   table row is out of range (a length outside [1, 128], a segment outside [0, N)): no address is formed from such a row.  No other
+ *   pair is touched.  The La x Lb distances and costs exist in LDS and registers only.  One call takes any P in the range: the
+ *   runtime refuses a grid of 2^32 threads or more, so the call goes out as ceil(P / 2^25) launches of at most 2^25 one-wave
+ *   workgroups (cpc_abx_count: ceil(T / 2^23) launches of 256 threads per task), in order on the stream.  CPC_EINVAL also for pairs
+ *   NULL or not 8-byte aligned, P outside [1, 2^31 - 1], dist NULL, dist, cost or path_len not 4-byte aligned.
+ *
+ * cpc_abx_count: tasks int64 [T][6] = (cell_off, n_c, s_p, n_p, s_q, n_q) on the device.  A cell's n_c x n_c block of DTW distances
+ *   starts at dist[cell_off] (row item = A or B, column item = X); group p is the items [s_p, s_p + n_p) of the cell, group q the
+ *   items [s_q, s_q + n_q).  out[t] (int64) = sum over x, a != x in p and b in q of 2 [d(a,x) < d(b,x)] + [d(a,x) == d(b,x)], with
+ *   d(a,x) = dist[cell_off + (s_p + a) n_c + s_p + x] and d(b,x) = dist[cell_off + (s_q + b) n_c + s_p + x]; d(x,x) is never read.
+ *   out[t] = -1 if a distance the task reads is NaN; out[t] = -2, and nothing read, unless 2 <= n_p <= 1024, 1 <= n_q <= 1024, both
+ *   groups lie inside [0, n_c) and the block inside [0, n_dist).  Integer arithmetic only: the result does not depend on the order.
+ *   CPC_EINVAL for dist, tasks or out NULL, dist not 4-byte aligned, tasks or out not 8-byte aligned, n_dist < 1, T outside
+ *   [1, 2^31 - 1].
+ * The calls never throw, allocate or synchronise.  stream is a hipStream_t.  (Added under ABI 9: no existing entry point changed.) */
+int cpc_frame_distance(const void* x, int dtype, long long N, int D, long long ldx, long long a_first, int La, long long b_first, int Lb,
+                       int metric, float* out, long long ldo, void* stream);
+int cpc_dtw(const void* x, int dtype, long long N, int D, long long ldx, const long long* pairs, long long P, int metric, float* dist,
+            float* cost, int* path_len, void* stream);
+int cpc_abx_count(const float* dist, long long n_dist, const long long* tasks, long long T, long long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
